@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """Benchmark of the occlusions-4d hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line with the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` and the workload's `config`).  --dump-outputs DIR then also writes what the
+last timed step returned (the implicit output, per query) as DIR/<name>.npy.  Everything else the line used to carry --
+the roofline leg and the extra objects listed below, the secondary grid, split-precision, schedule, host-boundary and
+exchange figures, the carla / training legs and the CPU baseline -- runs only with --full.
 
 N > 1: one process per GPU over RCCL.  Either launched by `python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...` (RANK / WORLD_SIZE in the environment), or from a bare shell: without WORLD_SIZE the script
@@ -19,12 +25,12 @@ N > 1 GPUs run BASELINE.json configs[3] ("GREATER dense grid 2 M queries sharded
 8 x MI355X"): num_sample 2097152 -> 2 125 568 grid queries, rank 0 encodes and broadcasts the
 abstract cloud, every rank decodes a contiguous 1/N slice (265 696 queries per GPU at N = 8):
 the total work is the same for N = 2, 4, 8 -> "scaling": "strong".  value = total queries /
-max-over-ranks time.  Each line also carries the other grid as a secondary leg, so that both
+max-over-ranks time.  With --full each line also carries the other grid as a secondary leg, so that both
 strong-scaling curves have all their points: `config4_single_gpu` on the N = 1 line (the 2 M
 grid on one GPU) and `strong_config2` on the N > 1 lines (the 534 528-query grid split N ways,
 where the serial 7.6 ms encode is the Amdahl term).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline      the dominant kernel = cross_attn16p_kernel (fused vector attention, 14
                 neighbours, D = 416), timed with HIP events on its launch stream.  achieved / frac
                 = the FLOP the kernel EXECUTES (after the exact-in-R refactoring of DESIGN.md 4,
@@ -266,12 +272,41 @@ def pmc_traffic(kind):
         return None, 'no PMC pass committed for this workload'
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all ranks' files together
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """--dump-outputs: writes every array of `arrays` (name -> tensor, rows = queries) as DIR/<name>.npy in float32
+    (N > 1: DIR/<name>_rank<r>.npy, each rank its own shard).  If the arrays of a rank exceed its share of
+    DUMP_LIMIT_BYTES, a fixed seeded sample of rows is written instead, ascending, with the row numbers in
+    DIR/<name>_rows.npy (float64, exact)."""
+    os.makedirs(dirname, exist_ok=True)
+    suffix = '_rank%d' % rank if world > 1 else ''
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    budget = DUMP_LIMIT_BYTES // world
+    for name, a in host.items():
+        rows = None
+        total = sum(x.nbytes for x in host.values())
+        if total > budget:
+            keep = max(1, int(a.shape[0] * budget / total))
+            rows = np.sort(np.random.default_rng(SEED + rank).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(dirname, name + suffix + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+        if rows is not None:
+            np.save(os.path.join(dirname, name + '_rows' + suffix + '.npy'), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--kind', default='greater', choices=['greater', 'carla'])
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned as DIR/<name>.npy (float32, <= 64 MB)')
+    ap.add_argument('--full', action='store_true', help='also run every measurement beyond the headline: roofline, '
+                    'informational legs, secondary configurations, CPU baseline (the --no-* options below select among '
+                    'them)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-alt', action='store_true', help='skip the opt-in split-bf16 logits measurement')
     ap.add_argument('--no-extra', action='store_true', help='skip every informational leg (secondary grid, pipelined, '
@@ -399,17 +434,21 @@ def main():
             elapsed, per_rank_s, (out, _) = timed(pipe_step, args.steps, max(1, args.warmup), finish=pipe_finish)
         else:
             elapsed, per_rank_s, (out, _) = timed(step, args.steps, args.warmup)
-        # Roofline leg: HIP events around every launch of the dominant kernel on its launch stream.
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {'implicit_output': out}, rank, world)
+        # Roofline leg (--full): HIP events around every launch of the dominant kernel on its launch stream.
         # The timed steps above interleave mini-batches on two streams, where an event bracket also
         # covers the other stream's kernels; this extra (untimed) step runs the same launches on ONE
         # stream so that the brackets are exclusive kernel durations.
-        timer = pk.ops.KernelTimer(lambda name, **sh: name == 'cross_attn' and sh.get('d') == 416)
-        pk.ops.set_kernel_timer(timer)
-        with pk.kernels(decode_streams=1):
-            step()
-        pk.ops.set_kernel_timer(None)
-        psum = timer.summary().get('cross_attn', dict(launches=0, total_ms=0.0, total_flops=0.0))
-        extra = not args.no_extra
+        psum = None
+        if args.full:
+            timer = pk.ops.KernelTimer(lambda name, **sh: name == 'cross_attn' and sh.get('d') == 416)
+            pk.ops.set_kernel_timer(timer)
+            with pk.kernels(decode_streams=1):
+                step()
+            pk.ops.set_kernel_timer(None)
+            psum = timer.summary().get('cross_attn', dict(launches=0, total_ms=0.0, total_flops=0.0))
+        extra = args.full and not args.no_extra
         # Secondary grid (informational): the other strong-scaling curve's point for this N.
         other = None
         if extra:
@@ -526,22 +565,25 @@ def main():
                                  what='perform_inference with host numpy inputs and outputs (PCIe inclusive), the '
                                       'previous result held while the next call runs')
             del res
-        # the exchange step, measured on one more (untimed) step: HIP events around the encoder (rank 0) and around
-        # the two broadcasts, per rank
-        timing = {}
-        pk.distributed.sharded_inference(pcl, queries, enc, dec, BATCH, inf['color_mode'], inf['predict_segmentation'],
-                                         'none', 13, timing=timing)
-        torch.cuda.synchronize()
-        ex = [timing['encode'][0].elapsed_time(timing['encode'][1]), timing['broadcast'][0].elapsed_time(timing['broadcast'][1])]
-        exchange = [ex]
-        if use_dist:
-            tt = torch.tensor(ex, dtype=torch.float64, device=device)
-            allt = [torch.empty_like(tt) for _ in range(world)]
-            dist.all_gather(allt, tt)
-            exchange = [[float(v) for v in x.tolist()] for x in allt]
-        # encode share, measured separately (informational; rank 0 is the rank that encodes)
+        # the exchange step (--full), measured on one more (untimed) step: HIP events around the encoder (rank 0) and
+        # around the two broadcasts, per rank
+        exchange = None
+        if args.full:
+            timing = {}
+            pk.distributed.sharded_inference(pcl, queries, enc, dec, BATCH, inf['color_mode'], inf['predict_segmentation'],
+                                             'none', 13, timing=timing)
+            torch.cuda.synchronize()
+            ex = [timing['encode'][0].elapsed_time(timing['encode'][1]),
+                  timing['broadcast'][0].elapsed_time(timing['broadcast'][1])]
+            exchange = [ex]
+            if use_dist:
+                tt = torch.tensor(ex, dtype=torch.float64, device=device)
+                allt = [torch.empty_like(tt) for _ in range(world)]
+                dist.all_gather(allt, tt)
+                exchange = [[float(v) for v in x.tolist()] for x in allt]
+        # encode share (--full), measured separately (informational; rank 0 is the rank that encodes)
         t_encode = None
-        if rank == 0:
+        if args.full and rank == 0:
             torch.cuda.synchronize()
             te = time.perf_counter()
             enc(pcl, False)
@@ -554,16 +596,6 @@ def main():
     if rank == 0:
         m_abs = pk.distributed.abstract_shape(enc, N_POINTS)[0]
         chunk = pk.inference.decode_chunk(BATCH)
-        calls = -(-(hi - lo) // chunk)
-        fl = as_written_flops(hi - lo, calls, m_abs, ia['d_out'])            # rank 0's share (it also encodes)
-        fl_exec = executed_flops(hi - lo, m_abs, ia['d_out'])
-        t_kernel = psum['total_ms'] * 1e-3
-        executed = psum['total_flops'] / t_kernel if t_kernel > 0 else 0.0
-        H = 416
-        as_written_pair = 2.0 * (3 * 32 + 32 * H + 2 * H * H + 2 * H * H)       # FLOP per (query, neighbour)
-        executed_pair = 2.0 * (32 * 2 * H + 2 * H * H + 32 * H)
-        as_written = executed * as_written_pair / executed_pair
-        traffic, traffic_source = pmc_traffic(args.kind)
         line = {
             'metric': '4D query-points/sec (encode+decode) at n_points=14336',
             'value': value, 'unit': 'query-points/s', 'n_gpus': world, 'steps': args.steps,
@@ -583,16 +615,33 @@ def main():
                                                'K encodes + K decodes)' if schedule == 'pipelined' else ''),
                        'scaling_note': 'strong scaling: the total work is fixed as N grows.  N = 1 runs configs[1] (534 528 '
                                        'queries, the configuration the metric is quoted on); N = 2, 4, 8 run configs[3] '
-                                       '(2 125 568 queries, the same total for every N).  Each line carries the other grid as a '
-                                       'secondary leg (config4_single_gpu / strong_config2), so both strong curves have their '
-                                       'N = 1 point.',
-                       'encode_ms_per_rank': [e[0] for e in exchange], 'broadcast_ms_per_rank': [e[1] for e in exchange],
+                                       '(2 125 568 queries, the same total for every N).  With --full each line carries the '
+                                       'other grid as a secondary leg (config4_single_gpu / strong_config2), so both strong '
+                                       'curves have their N = 1 point.',
                        'rccl_ranks': rccl_ranks, 'backend': ('rccl' if backend == 'nccl' else backend) if use_dist else None,
                        'rccl_info': rccl_log_excerpt(rccl_log) if rccl_log else None,
                        'ranks_share_one_gpu': share_gpu or None,
                        'per_rank_ms_per_step': [1e3 * t / args.steps for t in per_rank_s],
                        'decode_streams': pk.kernels.defaults().decode_streams, 'decode_chunk': chunk},
-            'roofline': {
+        }
+        d0 = pk.kernels.defaults()
+        if (d0.logit_precision, d0.trunk_precision) != ('f32', 'f32'):
+            # a profiling run with OCC4D_LOGIT_PRECISION / OCC4D_TRUNK_PRECISION as the PROCESS default: say so on the line
+            line['dtype'] = 'NOT the fp32 figure: process default precision logits %s / trunk %s (OCC4D_*_PRECISION)' % (
+                d0.logit_precision, d0.trunk_precision)
+        if args.full:
+            calls = -(-(hi - lo) // chunk)
+            fl = as_written_flops(hi - lo, calls, m_abs, ia['d_out'])            # rank 0's share (it also encodes)
+            fl_exec = executed_flops(hi - lo, m_abs, ia['d_out'])
+            t_kernel = psum['total_ms'] * 1e-3
+            executed = psum['total_flops'] / t_kernel if t_kernel > 0 else 0.0
+            H = 416
+            as_written_pair = 2.0 * (3 * 32 + 32 * H + 2 * H * H + 2 * H * H)       # FLOP per (query, neighbour)
+            executed_pair = 2.0 * (32 * 2 * H + 2 * H * H + 32 * H)
+            as_written = executed * as_written_pair / executed_pair
+            traffic, traffic_source = pmc_traffic(args.kind)
+            line['config'].update(encode_ms_per_rank=[e[0] for e in exchange], broadcast_ms_per_rank=[e[1] for e in exchange])
+            line['roofline'] = {
                 'bound': 'mfma', 'achieved': executed / 1e12, 'peak': FP32_MFMA_PEAK / 1e12, 'unit': 'TFLOP/s',
                 'frac': executed / FP32_MFMA_PEAK,
                 'achieved_as_written': as_written / 1e12, 'frac_as_written': as_written / FP32_MFMA_PEAK,
@@ -605,58 +654,55 @@ def main():
                 'launches': psum['launches'], 'avg_launch_ms': psum['total_ms'] / max(1, psum['launches']),
                 'flop_per_launch_executed': psum['total_flops'] / max(1, psum['launches']),
                 'flop_per_launch_as_written': psum['total_flops'] / max(1, psum['launches'])
-                * as_written_pair / executed_pair},
-            'pipeline': {
+                * as_written_pair / executed_pair}
+            line['pipeline'] = {
                 'executed_tflop_per_step_per_gpu': fl_exec / 1e12,
                 'executed_frac': fl_exec / (ms_per_step * 1e-3) / FP32_MFMA_PEAK,
                 'as_written_tflop_per_step_per_gpu': fl / 1e12,
                 'as_written_fp32_mfma_frac': fl / (ms_per_step * 1e-3) / FP32_MFMA_PEAK,
-                'encode_ms': 1e3 * t_encode},
-        }
-        d0 = pk.kernels.defaults()
-        if (d0.logit_precision, d0.trunk_precision) != ('f32', 'f32'):
-            # a profiling run with OCC4D_LOGIT_PRECISION / OCC4D_TRUNK_PRECISION as the PROCESS default: say so on the line
-            line['dtype'] = 'NOT the fp32 figure: process default precision logits %s / trunk %s (OCC4D_*_PRECISION)' % (
-                d0.logit_precision, d0.trunk_precision)
-            line['roofline']['note'] = ('priced against the fp32 MFMA peak although a split-precision kernel ran: not a figure of '
-                                        'merit; the split modes\' rooflines are the alt_precision* objects of a default run')
-        if other is not None:
-            line['config4_single_gpu' if world == 1 else 'strong_config2'] = other
-        if alt is not None:
-            line['alt_precision'] = alt
-        if alt_f16 is not None:
-            line['alt_precision_f16x3'] = alt_f16
-        if pipelined is not None:
-            line['sequential' if schedule == 'pipelined' else 'pipelined'] = pipelined
-        if host_boundary is not None:
-            line['host_boundary'] = host_boundary
-        # The headline is complete here: a copy goes to STDERR now, so that a harness time limit that cuts the secondary
-        # legs or the CPU baseline below short still leaves the measured figure in the log (stdout keeps its ONE line)
-        print('bench.py headline (secondary legs follow): ' + json.dumps({k: line[k] for k in (
-            'metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step')} | {'roofline_frac': line['roofline']['frac']}),
-            file=sys.stderr, flush=True)
-        # BASELINE configs[2] and configs[4] on the same driver-timed line: each leg is its own
-        # process on this GPU, K timed steps between fences exactly as above, its own `roofline` object.  (The CPU
-        # baseline starts after them: beside them its 16 threads cost the host-bound eager training step 1.5 ms.)
-        if world == 1 and extra and not args.no_secondary and args.kind == 'greater':
-            del out
-            torch.cuda.empty_cache()
-            line['carla_config3'] = secondary_leg(
-                'bench.py', ['--kind', 'carla', '--steps', '10', '--warmup', '3', '--no-extra', '--no-cpu-baseline'],
-                ['metric', 'value', 'unit', 'steps', 'warmup', 'ms_per_step', 'dtype', 'config', 'roofline', 'pipeline'])
-            line['train_config5'] = secondary_leg(
-                'bench_train.py', ['--steps', '10', '--warmup', '3'],
-                ['metric', 'value', 'unit', 'steps', 'warmup', 'ms_per_step', 'dtype', 'scaling', 'graph',
-                 'attention_backward', 'geometry_prefetch', 'gradient_overlap', 'peak_mem_gb', 'roofline', 'config',
-                 'losses'])
-            if 'error' not in line['train_config5']:
-                # the same step with its 416-input Linear layers, their data gradients and the forward attention kernel on
-                # the split-precision kernels (fp32-class, opt-in): informational, `train_config5.value` stays fp32
-                line['train_config5']['alt_precision'] = secondary_leg(
-                    'bench_train.py', ['--steps', '10', '--warmup', '3', '--precision', 'bf16x6'],
-                    ['value', 'ms_per_step', 'dtype', 'precision', 'peak_mem_gb', 'losses'])
-        if world == 1 and not args.no_cpu_baseline:
-            line['cpu_baseline'] = cpu_baseline(args.kind)
+                'encode_ms': 1e3 * t_encode}
+            if (d0.logit_precision, d0.trunk_precision) != ('f32', 'f32'):
+                line['roofline']['note'] = ('priced against the fp32 MFMA peak although a split-precision kernel ran: not a '
+                                            'figure of merit; the split modes\' rooflines are the alt_precision* objects of a '
+                                            'default run')
+            if other is not None:
+                line['config4_single_gpu' if world == 1 else 'strong_config2'] = other
+            if alt is not None:
+                line['alt_precision'] = alt
+            if alt_f16 is not None:
+                line['alt_precision_f16x3'] = alt_f16
+            if pipelined is not None:
+                line['sequential' if schedule == 'pipelined' else 'pipelined'] = pipelined
+            if host_boundary is not None:
+                line['host_boundary'] = host_boundary
+            # The headline is complete here: a copy goes to STDERR now, so that a time limit that cuts the secondary
+            # legs or the CPU baseline below short still leaves the measured figure in the log (stdout keeps its ONE line)
+            print('bench.py headline (secondary legs follow): ' + json.dumps({k: line[k] for k in (
+                'metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step')} | {'roofline_frac': line['roofline']['frac']}),
+                file=sys.stderr, flush=True)
+            # BASELINE configs[2] and configs[4] on the same driver-timed line: each leg is its own
+            # process on this GPU, K timed steps between fences exactly as above, its own `roofline` object.  (The CPU
+            # baseline starts after them: beside them its 16 threads cost the host-bound eager training step 1.5 ms.)
+            if world == 1 and extra and not args.no_secondary and args.kind == 'greater':
+                del out
+                torch.cuda.empty_cache()
+                line['carla_config3'] = secondary_leg(
+                    'bench.py', ['--kind', 'carla', '--steps', '10', '--warmup', '3', '--full', '--no-extra',
+                                 '--no-cpu-baseline'],
+                    ['metric', 'value', 'unit', 'steps', 'warmup', 'ms_per_step', 'dtype', 'config', 'roofline', 'pipeline'])
+                line['train_config5'] = secondary_leg(
+                    'bench_train.py', ['--steps', '10', '--warmup', '3'],
+                    ['metric', 'value', 'unit', 'steps', 'warmup', 'ms_per_step', 'dtype', 'scaling', 'graph',
+                     'attention_backward', 'geometry_prefetch', 'gradient_overlap', 'peak_mem_gb', 'roofline', 'config',
+                     'losses'])
+                if 'error' not in line['train_config5']:
+                    # the same step with its 416-input Linear layers, their data gradients and the forward attention kernel
+                    # on the split-precision kernels (fp32-class, opt-in): informational, `train_config5.value` stays fp32
+                    line['train_config5']['alt_precision'] = secondary_leg(
+                        'bench_train.py', ['--steps', '10', '--warmup', '3', '--precision', 'bf16x6'],
+                        ['value', 'ms_per_step', 'dtype', 'precision', 'peak_mem_gb', 'losses'])
+            if world == 1 and not args.no_cpu_baseline:
+                line['cpu_baseline'] = cpu_baseline(args.kind)
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.destroy_process_group()

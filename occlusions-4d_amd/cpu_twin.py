@@ -11,7 +11,7 @@ op order.  It is NOT a fallback: nothing in the package loads it unless a caller
 
 Without that call the product raises NativeLibraryError when libocc4d.so is missing and rejects CPU tensors (tests/
 test_abi.py).  While the twin is loaded, CUDA tensors are rejected instead.  Used by tests/test_cpu_twin.py: BASELINE
-configs[0] through the product modules, and the REFERENCE's own perform_inference driving them (container only).
+configs[0] through the product modules; oracle/check_reference_caller.py: the REFERENCE's own perform_inference driving them.
 """
 import contextlib
 import os

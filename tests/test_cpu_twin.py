@@ -2,20 +2,16 @@
 CPU twin compiled by g++ for config 1"; BASELINE configs[0]: "runs without a GPU").  Explicit opt-in only
 (occlusions4d_amd.cpu_twin.enable()); the product stays loud without the HIP library (test_abi.py).
 
-(i)  BASELINE configs[0] through the PRODUCT modules (PointCompletionNetV3, LocalPclResnetFC, perform_inference) on the
-     twin = the reference's golden run G10 (and the checkpoint fixtures G17).
-(ii) Container only: the REFERENCE's own eval/inference.py -- load_models and perform_inference -- driving the product
-     modules bound as INTEGRATION.md section A binds them: the drop-in boundary executed under the reference's caller."""
-import os
-
+BASELINE configs[0] through the PRODUCT modules (PointCompletionNetV3, LocalPclResnetFC, perform_inference) on the twin =
+the reference's golden run G10.  (The REFERENCE's own eval/inference.py driving the product modules, INTEGRATION.md
+section A, needs the reference's code and runs where it is mounted: oracle/check_reference_caller.py.)"""
 import numpy as np
 import pytest
 import torch
 
 import golden_cases as gc
 import occlusions4d_amd as pk
-from conftest import GOLDEN, load_golden
-from oracle import ref_import
+from conftest import load_golden
 
 
 @pytest.fixture
@@ -81,65 +77,6 @@ def test_config1_through_the_product_modules_on_the_twin(twin, case):
     near = int((np.abs(g['implicit_output'][:, 0] - 0.5) < 1e-4).sum())
     assert abs(res['output_solid'].shape[0] - int(g['n_solid'][0])) <= near
     assert res['output_air'].dtype == np.float64 and res['output_air'].shape[1] == 5
-
-
-@pytest.mark.skipif(not ref_import.available(), reason='the reference is only mounted in the build container')
-@pytest.mark.parametrize('case', gc.CKPT_CASES, ids=lambda c: c['name'])
-def test_the_references_own_caller_drives_the_product_modules(twin, case):
-    """INTEGRATION.md section A, executed: the reference's eval/inference.py with `model` / `implicit` bound to this
-    package.  ITS load_models (:23-80) builds the PRODUCT's networks from a reference-format checkpoint (constructor
-    kwargs, state_dict keys, legacy rename, fps_random_start override) and ITS perform_inference (:83-325) -- grid
-    sampling, batch loop, post-ops, threshold split -- calls the product's forwards.  The result must equal what the
-    same code returned with the reference's own modules (fixture G17)."""
-    ref = ref_import.load()
-    inf_mod = ref.inference
-    saved = (inf_mod.model, inf_mod.implicit)
-    inf_mod.model, inf_mod.implicit = pk.model, pk.implicit        # sys.modules['model'] / ['implicit'] of section A
-    real_load = torch.load
-    torch.load = lambda *a, **k: real_load(*a, **dict(k, weights_only=False))     # (torch >= 2.6 default; the reference predates it)
-    try:
-        (nets, _, _, pcl_args, _, epoch) = inf_mod.load_models(os.path.join(GOLDEN, gc.CKPT_DIR), torch.device('cpu'),
-                                                               epoch=case['epoch_arg'])
-    finally:
-        torch.load = real_load
-        inf_mod.model, inf_mod.implicit = saved
-    assert isinstance(nets[0], pk.model.PointCompletionNetV3) and isinstance(nets[1], pk.implicit.LocalPclResnetFC)
-    assert epoch == case['epoch'] and pcl_args['fps_random_start'] is False
-    for net in nets:
-        net.eval()
-    _, _, inf = gc.ckpt_model_args(case)
-    pcl = pk.configs.synthetic_pcl(gc.CKPT_INFER['kind'], gc.CKPT_INFER['n'], gc.CKPT_INFER['video_len'], gc.CKPT_INFER['seed'])
-    with torch.no_grad():                                            # (eval/test.py:32-34)
-        res = inf_mod.perform_inference(
-            pcl.clone(), None, None, nets, torch.device('cpu'), 'if', inf['min_z'], inf['cube_bounds'], inf['color_mode'],
-            gc.CKPT_INFER['time_idx'], None, sample_implicit=True, num_sample=gc.CKPT_INFER['num_sample'],
-            point_sample_mode='grid', batch_size=gc.CKPT_INFER['batch_size'], predict_segmentation=False,
-            track_mode='none', semantic_classes=13, density_threshold=0.5, data_kind=inf['data_kind'], cube_mode=4,
-            compress_air=True)
-    g = load_golden('g17_ckpt_' + case['name'])
-    assert np.array_equal(res['pcl_abstract'][:, :3], g['pcl_abstract'][:, :3])
-    assert np.abs(res['pcl_abstract'] - g['pcl_abstract']).max() < 1e-4
-    assert np.abs(res['implicit_output'] - g['implicit_output']).max() < 1e-4
-    assert res['output_solid'].shape[0] == int(g['n_solid'][0])
-
-
-@pytest.mark.skipif(not ref_import.available(), reason='the reference is only mounted in the build container')
-def test_the_references_perform_inference_on_config1(twin):
-    """The same at BASELINE configs[0]: the reference's perform_inference over the product's networks = G10."""
-    case = gc.INFER_CASES[0]
-    ref = ref_import.load()
-    g = load_golden('g10_infer_' + case['name'])
-    pcl, pa, ia, inf, esd, dsd = gc.infer_inputs(case)
-    enc = pk.model.PointCompletionNetV3(**pa).eval()
-    enc.load_state_dict(esd)
-    dec = pk.implicit.LocalPclResnetFC(**ia).eval()
-    dec.load_state_dict(dsd)
-    with torch.no_grad():
-        res = ref.inference.perform_inference(pcl.clone(), None, None, [enc, dec], torch.device('cpu'), 'if', inf['min_z'],
-                                              inf['cube_bounds'], inf['color_mode'], case['time_idx'], None, **_kw(case, inf))
-    assert np.array_equal(res['pcl_abstract'][:, :3], g['pcl_abstract'][:, :3])
-    assert np.abs(res['implicit_output'] - g['implicit_output']).max() < 1e-4
-    assert res['output_solid'].shape[0] == int(g['n_solid'][0]) and res['output_air'].shape == (8640 - res['output_solid'].shape[0], 5)
 
 
 def test_twin_nested_level_rule_for_repeated_picks(twin):

@@ -19,7 +19,7 @@ def test_bench_two_ranks_on_one_gpu():
     env.pop('WORLD_SIZE', None)
     env.pop('RANK', None)
     proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '1',
-                           '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=600)
+                           '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1, proc.stdout[-2000:]                    # rank 0 only
