@@ -553,7 +553,8 @@ int occ4d_broadcast_rows_f32(const float* vec, float scale, int n, int d, float*
 #define OCC4D_PATH_BF16X6_TRUNK 128 /* opt-in, fp32-class: the decoder's 416-input Linear layers on the same split (csrc/trunk_bf16x6.hip) */
 #define OCC4D_PATH_FUSED_INTERP 32 /* A/B only (slower): lin_z table term of block i + 1 in block i's epilogue */
 #define OCC4D_PATH_SPLIT_F16 256    /* with OCC4D_PATH_BF16X6 / _TRUNK: the split is fp16 x 2 pieces, 3 partial products (round 6;
-                                     * half the matrix instructions; inference forwards only; |w| < 255, |activation| < 65504) */
+                                     * half the matrix instructions; inference forwards only; |w| < 255.9, |activation| < 65504; the prepare calls fail with
+ * OCC4D_EINVAL for a weight outside the window) */
 
 /* Stage packers as device kernels (layouts: occ4d_resblock_f32 / occ4d_resblock4_f32 / occ4d_pt_cross_attn16p_f32).
  * w: (n_out, 416) row-major with row stride ldw. */

@@ -2,7 +2,7 @@
 // csrc/crossattn_bf16x6.hip (vector attention) and csrc/trunk_bf16x6.hip (the decoder's 416-input Linear layers).
 //
 //     x = x1 + x2 + x3 exactly   (x1 = x truncated to bf16, x2 = (x - x1) truncated, x3 = x - x1 - x2: 3 x 8 = 24 bits)
-//     a b ~ a1 b1 + a1 b2 + a2 b1 + a2 b2 + a1 b3 + a3 b1          (dropped: a2 b3, a3 b2, a3 b3 <= 2^-23 |a b|)
+//     a b ~ a1 b1 + a1 b2 + a2 b1 + a2 b2 + a1 b3 + a3 b1          (dropped: a2 b3 + a3 b2 + a3 b3 <= 2^-21 |a b|)
 #pragma once
 #include "common.hpp"
 
@@ -67,8 +67,14 @@ __device__ __forceinline__ Split split8(const f32x4 a, const f32x4 b) {
   split2(b.z, b.w, h[3], m[3], l[3]);
   return Split{u32x4{h[0], h[1], h[2], h[3]}, u32x4{m[0], m[1], m[2], m[3]}, u32x4{l[0], l[1], l[2], l[3]}};
 }
+// ReLU that keeps NaN: an operand outside the fp16 window turns its pieces into inf and -inf and the products into NaN,
+// and fmaxf(NaN, 0) = 0 would hand back a finite, wrong row.  v - min(v, 0) is v for v >= 0, 0 for v < 0 (exact) and NaN
+// for NaN, whatever the NaN's sign (the matrix pipe's NaN here has the sign bit set, so an integer maximum of the bit
+// patterns would drop it).  One VALU instruction more than fmaxf.  Not v_maximum3_f32 by inline asm: the operands are
+// often MFMA results, and the compiler inserts the MFMA -> VALU wait states only for instructions it knows.
+__device__ __forceinline__ float relu_nan(float v) { return v - fminf(v, 0.f); }
 __device__ __forceinline__ f32x4 relu4x(f32x4 v) {
-  v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+  v.x = relu_nan(v.x); v.y = relu_nan(v.y); v.z = relu_nan(v.z); v.w = relu_nan(v.w);
   return v;
 }
 
@@ -148,14 +154,19 @@ struct SplitBf16x6 {
 //     a b ~ a1 b1 + a1 b2 + a2 b1                                      (dropped: a2 b2 <= 2^-22 |a b|, typically 2^-25)
 // HALF the matrix instructions of the bf16 scheme (v_mfma_f32_16x16x32_f16 runs at the bf16 rate) and a third of its
 // split arithmetic (4 VALU per element pair: v_cvt_pk_f16_f32, 2 x v_fma_mix_f32, v_cvt_pk_f16_f32).  The price is
-// fp16's RANGE, which the bf16 pieces do not have to think about:
+// fp16's RANGE, which the bf16 pieces do not have to think about (the windows as tests/test_split_scheme.py and
+// tests/test_gpu_split_range.py test them):
 //   * weights are packed as the pieces of w * 2^8 (exact), so that the second piece of a weight of ordinary size
-//     (>= 2^-10) is a normal fp16 number; smaller ones are kept to an absolute 2^-33; |w| must stay below 255.
+//     (>= 2^-10) is a normal fp16 number; smaller ones are kept to an absolute 2^-33; |w| < 255.9375 (65520 / 2^8 rounds
+//     to inf).  The same for the merged query projection, which csrc/path.hip stores * 2^4 for the attention kernel:
+//     its row kernel packs it / 2^4 again and restores the factor in the epilogue.
 //     (The attention kernel's first GEMM packs its merged 832 x 32 matrix * 2^4 instead and keeps the hidden activations
-//     at 2^4 x their value up to the second GEMM -- no scaling instruction in the loop: |w| < 4094 there, entries below
+//     at 2^4 x their value up to the second GEMM -- no scaling instruction in the loop: |w| < 4095 there, entries below
 //     2^-6 kept to an absolute 2^-29, hidden activations below 4094.)
-//   * activations are split as they are: |x| must stay below 65504, and below |x| = 0.25 the second piece is an
+//   * activations are split as they are: |x| < 65504 (65520 rounds to inf), and below |x| = 0.25 the second piece is an
 //     fp16 subnormal (gfx950's matrix pipe does not flush them): absolute error <= 2^-25 instead of 2^-23 |x|.
+//   * outside a window the pieces are inf and -inf and the products NaN; relu4x keeps the NaN, so the rows it reaches come
+//     out non-finite.  Packed weight streams are checked for inf halves when the path-level weights are prepared.
 // Forward passes only -- gradient magnitudes do not live in that window.
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));

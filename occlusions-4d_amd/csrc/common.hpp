@@ -59,6 +59,12 @@ bool f16w_enabled();
 // block of csrc/resblock_f16x3.hip (A/B)
 bool f16_resblock_enabled();
 
+// trunk_bf16x6.hip: the fp16 split row kernel for a weight the caller multiplied by the power of two `prescale`: packed as
+// the unscaled weight (window |w / prescale| < 255.9), the factor restored in the epilogue (y = w x + b, w and b prescaled)
+int pack_rowlin_f16x3_prescaled(const float* w, int64_t ldw, int n_out, float prescale, float* packed, hipStream_t st);
+int rowlin_f16x3_prescaled(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed, const float* b,
+                           int n_out, float prescale, int relu_in, const float* res, int64_t ldr, int n, hipStream_t st);
+
 // path.hip: phase offset of the paired attention workgroups (units of s_sleep(127); OCC4D_CA16P_SKEW, default 6)
 int attn16p_skew();
 

@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256, 1) void cross_attn_f16w_kernel(const AttnWArgs
     for (int ks = 0; ks < 2; ++ks) {
       float v[8];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = fmaxf(h0[8 * ks + e] + h1[8 * ks + e], 0.f);
+      for (int e = 0; e < 8; ++e) v[e] = relu_nan(h0[8 * ks + e] + h1[8 * ks + e]);
       hs[ks] = split8w(v);
     }
   };

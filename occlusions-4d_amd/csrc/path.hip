@@ -3,9 +3,11 @@
 // the feature half of DownTransition (model/modules.py:152-158) and LocalPclResnetFC (model/implicit.py:271-445) -- driven
 // from C++ on the caller's stream, with the reference's parameters in the reference's layout.  The merged-weight algebra
 // of DESIGN.md 4 (i) (fp64 products, rounded once) and every stage packing of the MFMA kernels are device kernels here,
-// so that a binder needs nothing but this library.  No allocation, no synchronisation: three caller-provided buffers
-// (prepared / scene / workspace), laid out by the host-only *_floats() functions below.
+// so that a binder needs nothing but this library.  No allocation, and no synchronisation except the fp16 window check of
+// a prepare call under OCC4D_PATH_SPLIT_F16 (check_f16_stream): three caller-provided buffers (prepared / scene /
+// workspace), laid out by the host-only *_floats() functions below.
 #include <algorithm>
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "common.hpp"
@@ -178,6 +180,39 @@ int scale_f32(float* x, int64_t n, float s, hipStream_t st) {
   scale_f32_kernel<<<cdiv(n, 256), 256, 0, st>>>(x, n, s);
   return occ4d::check_launch("merged weights: scale");
 }
+
+// A packed fp16 piece stream (two halves per word) with an inf or NaN half: a weight outside the scheme's window, which
+// the kernels would turn into NaN products (the flag is cleared by a launch of its own, ahead of the scan's atomics).
+__global__ void f16_flag_clear_kernel(unsigned* flag) { flag[0] = 0u; }
+__global__ void f16_scan_kernel(const unsigned* __restrict__ words, int64_t n, unsigned* flag) {
+  unsigned bad = 0u;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const unsigned w = words[i];
+    bad |= ((w & 0x7c00u) == 0x7c00u) | ((w & 0x7c000000u) == 0x7c000000u);
+  }
+  if (bad) atomicOr(flag, 1u);
+}
+// Prepare time only (once per weight update, never per forward call): scan `floats` of packed stream, 4 bytes back to the
+// host.  `flag` is 4 bytes of device memory the caller does not need at this point.  Skipped while the stream is being
+// captured into a graph (no synchronisation is possible there).
+int check_f16_stream(const float* packed, int64_t floats, unsigned* flag, const char* who, const char* what, hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return OCC4D_OK;
+  f16_flag_clear_kernel<<<1, 1, 0, st>>>(flag);
+  TRY(occ4d::check_launch("f16 stream check: clear"));
+  const int blocks = (int)std::min<int64_t>(cdiv(floats, 256), 1024);
+  f16_scan_kernel<<<blocks, 256, 0, st>>>(reinterpret_cast<const unsigned*>(packed), floats, flag);
+  TRY(occ4d::check_launch("f16 stream check: scan"));
+  unsigned h = 0u;
+  if (hipMemcpyAsync(&h, flag, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    occ4d::set_error("%s: f16 stream check (%s): %s", who, what, hipGetErrorString(hipGetLastError()));
+    return OCC4D_ELAUNCH;
+  }
+  OCC4D_REQUIRE(h == 0u, "%s: %s has an entry outside the fp16 split scheme's window (|w| < 255.9 for a packed weight, "
+                "|w| < 4094 for the attention's merged Wp = W1 P2) or not finite: OCC4D_PATH_SPLIT_F16 cannot represent it",
+                who, what);
+  return OCC4D_OK;
+}
 int mm64(const double* a, const double* b, double* c, int m, int n, int k, hipStream_t st) {   // contiguous operands
   return occ4d_matmul_f64(a, k, 1, b, n, 1, c, m, n, k, st);
 }
@@ -195,16 +230,18 @@ int lin(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* b
 
 bool al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
 
-// the split-precision row kernel in either scheme (csrc/trunk_bf16x6.hip): bf16 x 3 pieces / fp16 x 2 pieces
+// the split-precision row kernel in either scheme (csrc/trunk_bf16x6.hip): bf16 x 3 pieces / fp16 x 2 pieces.  `prescale`:
+// the power of two the caller multiplied w and b with (fp16 scheme only): packed as w / prescale, restored in the epilogue
 int64_t split_packed_floats(bool f16, int n_out) {
   return f16 ? occ4d_rowlin_f16x3_packed_floats(n_out) : occ4d_rowlin_bf16x6_packed_floats(n_out);
 }
-int split_pack_rowlin(bool f16, const float* w, int64_t ldw, int n_out, float* packed, hipStream_t st) {
-  return f16 ? occ4d_pack_rowlin_f16x3_f32(w, ldw, n_out, packed, st) : occ4d_pack_rowlin_bf16x6_f32(w, ldw, n_out, packed, st);
+int split_pack_rowlin(bool f16, const float* w, int64_t ldw, int n_out, float* packed, hipStream_t st, float prescale = 1.f) {
+  return f16 ? occ4d::pack_rowlin_f16x3_prescaled(w, ldw, n_out, prescale, packed, st)
+             : occ4d_pack_rowlin_bf16x6_f32(w, ldw, n_out, packed, st);
 }
 int split_rowlin(bool f16, const float* x, int64_t ldx, float* y, int64_t ldy, const float* wpk, const float* b, int n_out,
-                 int relu_in, const float* res, int64_t ldr, int n, hipStream_t st) {
-  return f16 ? occ4d_rowlin_f16x3_f32(x, ldx, y, ldy, wpk, b, n_out, relu_in, res, ldr, n, st)
+                 int relu_in, const float* res, int64_t ldr, int n, hipStream_t st, float prescale = 1.f) {
+  return f16 ? occ4d::rowlin_f16x3_prescaled(x, ldx, y, ldy, wpk, b, n_out, prescale, relu_in, res, ldr, n, st)
              : occ4d_rowlin_bf16x6_f32(x, ldx, y, ldy, wpk, b, n_out, relu_in, res, ldr, n, st);
 }
 
@@ -216,6 +253,8 @@ struct LayerLayout {
   bool fold_pre, fused16p, fused_first, fused_self16, bf16x6, wq_rows, w3_rows, trunk4, x6rows;
   bool f16;                         // the split kernels' scheme: fp16 x 2 pieces instead of bf16 x 3 (OCC4D_PATH_SPLIT_F16)
   bool f16w;                        // ... its attention kernel on 32 x 32 x 16 instructions (csrc/crossattn_f16w.hip)
+  float wq_scale;                   // the power of two the merged query projection (wq, bq) is stored at: the fp16 attention
+                                    // kernel's hidden scale, else 1
   int64_t wq, bq, wk, wp, wq_packed, stream, stream6, w3_packed, wq_x6, w3_x6, scratch, total;
   int64_t s_A, s_B, s_C, s_C2, s_v, s_bq;      // doubles, inside the scratch region
 };
@@ -270,6 +309,7 @@ LayerLayout layer_layout(const occ4d_pt_layer_weights& w, int flags) {
   L.w3_x6 = L.x6rows ? take(split_packed_floats(L.f16, w.d_out)) : -1;
   L.stream = L.fused16p ? take(occ4d_pt_cross_attn16p_stream_floats()) : -1;
   L.f16w = L.bf16x6 && L.f16 && occ4d::f16w_enabled();
+  L.wq_scale = L.bf16x6 && L.f16 ? occ4d_pt_cross_attn_f16x3_hidden_scale() : 1.f;
   L.stream6 = L.bf16x6 ? take(L.f16w ? occ4d_pt_cross_attn_f16w_stream_floats()
                                      : L.f16 ? occ4d_pt_cross_attn_f16x3_stream_floats() : occ4d_pt_cross_attn_bf16x6_stream_floats()) : -1;
   L.w3_packed = L.w3_rows ? take(packed(w.d_out)) : -1;
@@ -288,7 +328,8 @@ LayerLayout layer_layout(const occ4d_pt_layer_weights& w, int flags) {
   return L;
 }
 
-int layer_prepare(const occ4d_pt_layer_weights& w, const LayerLayout& L, float* prep, hipStream_t st) {
+// `who`: the caller and the layer, for the error message of the fp16 window check
+int layer_prepare(const occ4d_pt_layer_weights& w, const LayerLayout& L, float* prep, hipStream_t st, const char* who) {
   const int D = L.D, D2 = L.D2, h = L.h;
   double* S = reinterpret_cast<double*>(prep + L.scratch);
   double *A = S + L.s_A, *B = S + L.s_B, *C = S + L.s_C, *C2 = S + L.s_C2, *v = S + L.s_v, *bq = S + L.s_bq;
@@ -318,8 +359,10 @@ int layer_prepare(const occ4d_pt_layer_weights& w, const LayerLayout& L, float* 
   TRY(to_f32(C2, (int64_t)2 * D * h, prep + L.wp, st));               // W1 P2
   if (L.bf16x6 && L.f16) {
     // the fp16 attention kernel keeps its hidden activations at HSCALE x their value: the matrices behind its init term
-    // (Aq = wq x + bq, Kt = wk f) are multiplied by that power of two here, once (exact), BEFORE they are packed
-    const float hs = occ4d_pt_cross_attn_f16x3_hidden_scale();
+    // (Aq = wq x + bq, Kt = wk f) are multiplied by that power of two here, once (exact).  The split row kernel packs wq
+    // divided by it again and restores it in its epilogue (split_pack_rowlin / split_rowlin `prescale`), so the merged
+    // projection keeps the |w| < 255.9 window of every packed matrix
+    const float hs = L.wq_scale;
     TRY(scale_f32(prep + L.wq, (int64_t)2 * D * L.Kq, hs, st));
     TRY(scale_f32(prep + L.bq, 2 * D, hs, st));
     TRY(scale_f32(prep + L.wk, (int64_t)2 * D * D2, hs, st));
@@ -329,7 +372,7 @@ int layer_prepare(const occ4d_pt_layer_weights& w, const LayerLayout& L, float* 
     else TRY(occ4d_pack_trunk_rows_f32(prep + L.wq, L.Kq, 2 * D, prep + L.wq_packed, st));
   }
   if (L.x6rows) {
-    TRY(split_pack_rowlin(L.f16, prep + L.wq, L.Kq, 2 * D, prep + L.wq_x6, st));
+    TRY(split_pack_rowlin(L.f16, prep + L.wq, L.Kq, 2 * D, prep + L.wq_x6, st, L.wq_scale));
     TRY(split_pack_rowlin(L.f16, w.post_w, D, w.d_out, prep + L.w3_x6, st));
   }
   if (L.fused16p) TRY(occ4d_pack_attn16p_stream_f32(w.attn2_w, prep + L.wp, w.pos2_w, prep + L.stream, st));
@@ -340,6 +383,21 @@ int layer_prepare(const occ4d_pt_layer_weights& w, const LayerLayout& L, float* 
   if (L.w3_rows) {
     if (L.trunk4) TRY(occ4d_pack_trunk4_rows_f32(w.post_w, D, w.d_out, prep + L.w3_packed, st));
     else TRY(occ4d_pack_trunk_rows_f32(w.post_w, D, w.d_out, prep + L.w3_packed, st));
+  }
+  if (L.f16) {       // the fp64 scratch is free again: its first word is the check's flag
+    unsigned* flag = reinterpret_cast<unsigned*>(prep + L.scratch);
+    char what[160];
+    if (L.x6rows) {
+      snprintf(what, sizeof(what), "%s, merged query projection W1 Wq", who);
+      TRY(check_f16_stream(prep + L.wq_x6, split_packed_floats(true, 2 * D), flag, what, "packed stream", st));
+      snprintf(what, sizeof(what), "%s, layer3 weight", who);
+      TRY(check_f16_stream(prep + L.w3_x6, split_packed_floats(true, w.d_out), flag, what, "packed stream", st));
+    }
+    if (L.bf16x6) {
+      snprintf(what, sizeof(what), "%s, attention weights (attn_mlp[2] W2, merged Wp = W1 P2, pos_mlp[2] P2)", who);
+      TRY(check_f16_stream(prep + L.stream6, L.f16w ? occ4d_pt_cross_attn_f16w_stream_floats()
+                                                    : occ4d_pt_cross_attn_f16x3_stream_floats(), flag, what, "packed stream", st));
+    }
   }
   return OCC4D_OK;
 }
@@ -375,9 +433,9 @@ int rowlin_any(bool trunk4, const float* x, int64_t ldx, float* y, int64_t ldy, 
 }
 
 int rowlin_x6(bool f16, const float* x, int64_t ldx, float* y, int64_t ldy, const float* wpk, const float* b, int n_out,
-              int relu_in, const float* res, int64_t ldr, int n, const Events& E, hipStream_t st) {
+              int relu_in, const float* res, int64_t ldr, int n, const Events& E, hipStream_t st, float prescale = 1.f) {
   E.before(OCC4D_PROFILE_ROWLIN);
-  const int rc = split_rowlin(f16, x, ldx, y, ldy, wpk, b, n_out, relu_in, res, ldr, n, st);
+  const int rc = split_rowlin(f16, x, ldx, y, ldy, wpk, b, n_out, relu_in, res, ldr, n, st, prescale);
   E.after(OCC4D_PROFILE_ROWLIN);
   return rc;
 }
@@ -450,7 +508,8 @@ int layer_forward(const occ4d_pt_layer_weights& w, const LayerLayout& L, const f
       float* ab = ws.take((int64_t)c * 2 * D);
       if (!dry) {
         if (L.x6rows)
-          TRY(rowlin_x6(L.f16, x + (int64_t)lo * ldx, ldx, ab, 2 * D, prep + L.wq_x6, prep + L.bq, 2 * D, 0, nullptr, 0, c, E, st));
+          TRY(rowlin_x6(L.f16, x + (int64_t)lo * ldx, ldx, ab, 2 * D, prep + L.wq_x6, prep + L.bq, 2 * D, 0, nullptr, 0, c, E, st,
+                         L.wq_scale));
         else if (L.wq_rows)
           TRY(rowlin_any(L.trunk4, x + (int64_t)lo * ldx, ldx, ab, 2 * D, prep + L.wq_packed, prep + L.bq, 2 * D, 0, nullptr, 0,
                          c, E, st));
@@ -812,7 +871,7 @@ extern "C" int64_t occ4d_pt_layer_prepared_floats(const occ4d_pt_layer_weights* 
 extern "C" int occ4d_pt_layer_prepare_f32(const occ4d_pt_layer_weights* w, float* prepared, int flags, void* stream) {
   TRY(check_layer(w, "occ4d_pt_layer_prepare_f32"));
   OCC4D_REQUIRE(prepared && al16(prepared), "occ4d_pt_layer_prepare_f32: prepared buffer missing or misaligned");
-  return layer_prepare(*w, layer_layout(*w, flags), prepared, (hipStream_t)stream);
+  return layer_prepare(*w, layer_layout(*w, flags), prepared, (hipStream_t)stream, "occ4d_pt_layer_prepare_f32: layer");
 }
 extern "C" int64_t occ4d_pt_layer_scene_floats(const occ4d_pt_layer_weights* w, int m) {
   if (check_layer(w, "occ4d_pt_layer_scene_floats") || m < 0) return -1;
@@ -941,7 +1000,27 @@ extern "C" int occ4d_decoder_prepare_f32(const occ4d_decoder_weights* w, float* 
     TRY(split_pack_rowlin(L.f16, w->fc0_w[i], TRUNK, TRUNK, prepared + L.w0x[i], st));
     TRY(split_pack_rowlin(L.f16, w->fc1_w[i], TRUNK, TRUNK, prepared + L.w1x[i], st));
   }
-  for (int j = 0; j < L.nC; ++j) TRY(layer_prepare(w->cross[j], L.cl[j], prepared + L.cross[j], st));
+  if (L.f16 && (L.f16block || L.x6trunk)) {
+    unsigned* flag = reinterpret_cast<unsigned*>(prepared + L.total);       // (the ALIGN floats behind the layout)
+    char what[96];
+    for (int i = 0; i < L.nB; ++i) {
+      snprintf(what, sizeof(what), "block %d fc_0 / fc_1 weights", i);
+      if (L.f16block) {
+        TRY(check_f16_stream(prepared + L.w0x[i], occ4d_resblock_f16x3_packed_floats(), flag, "occ4d_decoder_prepare_f32",
+                             what, st));
+      } else {
+        snprintf(what, sizeof(what), "block %d fc_0 weight", i);
+        TRY(check_f16_stream(prepared + L.w0x[i], split_packed_floats(true, TRUNK), flag, "occ4d_decoder_prepare_f32", what, st));
+        snprintf(what, sizeof(what), "block %d fc_1 weight", i);
+        TRY(check_f16_stream(prepared + L.w1x[i], split_packed_floats(true, TRUNK), flag, "occ4d_decoder_prepare_f32", what, st));
+      }
+    }
+  }
+  for (int j = 0; j < L.nC; ++j) {
+    char who[64];
+    snprintf(who, sizeof(who), "occ4d_decoder_prepare_f32: cross-attention layer %d", j);
+    TRY(layer_prepare(w->cross[j], L.cl[j], prepared + L.cross[j], st, who));
+  }
   return OCC4D_OK;
 }
 extern "C" int64_t occ4d_decoder_scene_floats(const occ4d_decoder_weights* w, int m) {

@@ -42,6 +42,7 @@ struct RowlinX6Args {
   int rowgroups, per;                     // groups of 256 rows; groups per XCD share
   const float* mask; int64_t ldm;         // training data gradients: output zeroed where mask <= 0 (or null)
   int res_post;                           // with a mask: res is added AFTER the mask (a skip connection's gradient)
+  float out_scale;                        // the accumulators' factor in the epilogue: S::INV_WSCALE (x a power of two)
 };
 
 template <typename S, bool RELU_IN>
@@ -168,7 +169,7 @@ __global__ __launch_bounds__(512, 2) void rowlin_split_kernel(const RowlinX6Args
       for (int t = 0; t < YT; ++t) mk[t] = *reinterpret_cast<const f32x4*>(a.mask + (int64_t)rowc * a.ldm + ch0 + 16 * t);
 #pragma unroll
       for (int t = 0; t < YT; ++t) {
-        f32x4 v = S::WSCALE == 1.f ? acc[rt][t] : acc[rt][t] * S::INV_WSCALE;
+        f32x4 v = S::WSCALE == 1.f ? acc[rt][t] : acc[rt][t] * a.out_scale;
         if (a.bias) v += *reinterpret_cast<const f32x4*>(a.bias + ch0 + 16 * t);
         if (a.res && !a.res_post) v += r[t];
         v.x = mk[t].x > 0.f ? v.x : 0.f; v.y = mk[t].y > 0.f ? v.y : 0.f;
@@ -180,7 +181,7 @@ __global__ __launch_bounds__(512, 2) void rowlin_split_kernel(const RowlinX6Args
     }
 #pragma unroll
     for (int t = 0; t < YT; ++t) {
-      f32x4 v = S::WSCALE == 1.f ? acc[rt][t] : acc[rt][t] * S::INV_WSCALE;
+      f32x4 v = S::WSCALE == 1.f ? acc[rt][t] : acc[rt][t] * a.out_scale;
       if (a.bias) v += *reinterpret_cast<const f32x4*>(a.bias + ch0 + 16 * t);
 #ifndef OCC4D_X6T_ABL_NORES
       if (a.res) v += r[t];
@@ -194,7 +195,8 @@ __global__ __launch_bounds__(512, 2) void rowlin_split_kernel(const RowlinX6Args
 }
 
 template <typename S>
-__global__ void pack_rowlin_split_kernel(const float* __restrict__ w, int64_t ldw, int n_out, unsigned* __restrict__ out) {
+__global__ void pack_rowlin_split_kernel(const float* __restrict__ w, int64_t ldw, int n_out, unsigned* __restrict__ out,
+                                         float scale) {
   constexpr int NP = S::NP, YSF = YG<S>::SF, YSTAGE = YG<S>::STAGE;
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t total = (int64_t)(n_out / YCB) * YKS * YSTAGE;
@@ -203,7 +205,7 @@ __global__ void pack_rowlin_split_kernel(const float* __restrict__ w, int64_t ld
   const int frag = (int)((e / YFW) % YSF), stage = (int)((e / YSTAGE) % YKS), cb = (int)(e / ((int64_t)YKS * YSTAGE));
   const int c = lane & 15, g = lane >> 4, t = frag / NP, p = frag % NP;
   const float* row = w + (int64_t)(YCB * cb + 16 * t + c) * ldw + 32 * stage + 8 * g + 2 * word;
-  out[e] = S::piece(row[0], p) | (S::piece(row[1], p) << 16);
+  out[e] = S::piece_scaled(row[0], p, scale) | (S::piece_scaled(row[1], p, scale) << 16);
 }
 
 }  // namespace
@@ -212,19 +214,21 @@ namespace {
 template <typename S> int64_t packed_floats(int n_out) { return (int64_t)(n_out / YCB) * YKS * YG<S>::STAGE; }
 
 template <typename S>
-int pack_rowlin(const char* who, const float* w, int64_t ldw, int n_out, float* packed, void* stream) {
+int pack_rowlin(const char* who, const float* w, int64_t ldw, int n_out, float* packed, void* stream,
+                float prescale = 1.f) {
   OCC4D_REQUIRE(w && packed && n_out >= YCB && n_out % YCB == 0 && 8 % (n_out / YCB) == 0 && ldw >= YK,
                 "%s: (%d, %d) weight with n_out in {208, 416, 832, 1664} expected", who, n_out, YK);
   const int64_t total = packed_floats<S>(n_out);
   pack_rowlin_split_kernel<S><<<occ4d::cdiv(total, 256), 256, 0, (hipStream_t)stream>>>(w, ldw, n_out,
-                                                                                        reinterpret_cast<unsigned*>(packed));
+                                                                                        reinterpret_cast<unsigned*>(packed),
+                                                                                        S::WSCALE / prescale);
   return occ4d::check_launch(who);
 }
 
 template <typename S>
 int rowlin_split_launch(const char* who, const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed,
                         const float* b, int n_out, int relu_in, const float* res, int64_t ldr, int res_post,
-                        const float* mask, int64_t ldm, int n, void* stream) {
+                        const float* mask, int64_t ldm, int n, void* stream, float prescale = 1.f) {
   if (n == 0) return OCC4D_OK;
   OCC4D_REQUIRE(x && y && w_packed && n > 0, "%s: null pointer", who);
   OCC4D_REQUIRE(n_out >= YCB && n_out % YCB == 0 && 8 % (n_out / YCB) == 0 && ldy >= n_out && ldx >= YK && ldx % 4 == 0 &&
@@ -234,7 +238,7 @@ int rowlin_split_launch(const char* who, const float* x, int64_t ldx, float* y, 
   OCC4D_REQUIRE(!mask || (ldm >= n_out && ldm % 4 == 0 && ((uintptr_t)mask % 16) == 0),
                 "%s: mask rows must be 16-byte aligned with ldm %% 4 == 0 and ldm >= n_out", who);
   RowlinX6Args a{x, ldx, y, ldy, reinterpret_cast<const unsigned*>(w_packed), b, res, ldr, n, n_out / YCB, 0, 0,
-                 mask, ldm, res_post};
+                 mask, ldm, res_post, S::INV_WSCALE * prescale};
   a.rowgroups = (int)occ4d::cdiv(n, YROWS);
   a.per = (int)occ4d::cdiv(a.rowgroups, 8 / a.nblk);
   hipStream_t st = (hipStream_t)stream;
@@ -267,6 +271,21 @@ extern "C" int occ4d_rowlin_f16x3_f32(const float* x, int64_t ldx, float* y, int
   return rowlin_split_launch<SplitF16x3>("occ4d_rowlin_f16x3_f32", x, ldx, y, ldy, w_packed, b, n_out, relu_in, res, ldr, 0,
                                          nullptr, 0, n, stream);
 }
+
+// Internal (csrc/path.hip): the fp16 scheme for a weight the caller has multiplied by a power of two `prescale` (the merged
+// query projection of a layer whose attention kernel takes its query term at the hidden scale, see csrc/bf16x6.hpp).
+// The pieces are those of w / prescale * WSCALE -- the packed stream of the unscaled weight, so the window stays
+// |w / prescale| < 255.9 -- and the epilogue multiplies by INV_WSCALE * prescale: y = w x + b with the prescaled w, b.
+namespace occ4d {
+int pack_rowlin_f16x3_prescaled(const float* w, int64_t ldw, int n_out, float prescale, float* packed, hipStream_t st) {
+  return pack_rowlin<SplitF16x3>("pack_rowlin_f16x3_prescaled", w, ldw, n_out, packed, st, prescale);
+}
+int rowlin_f16x3_prescaled(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed, const float* b,
+                           int n_out, float prescale, int relu_in, const float* res, int64_t ldr, int n, hipStream_t st) {
+  return rowlin_split_launch<SplitF16x3>("rowlin_f16x3_prescaled", x, ldx, y, ldy, w_packed, b, n_out, relu_in, res, ldr, 0,
+                                         nullptr, 0, n, st, prescale);
+}
+}  // namespace occ4d
 
 // The same with the epilogue of a training data gradient: y = [mask > 0] ([relu](x) W^T + b [+ res]) [+ res], `res`
 // before (res_after_mask = 0) or after the mask (the contracts of occ4d_rowlin4_masked_f32 / _masked_skip_f32).

@@ -28,7 +28,9 @@ PRECISIONS = ('f32', 'bf16x6', 'f16x3')
 # 'f32'     every GEMM on v_mfma_f32_16x16x4_f32 (the measured `value` of bench.py)
 # 'bf16x6'  bf16 x 3 pieces per operand, 6 partial products, fp32 accumulate: fp32-class, no range restriction
 # 'f16x3'   fp16 x 2 pieces per operand, 3 partial products, fp32 accumulate (round 6): half the matrix instructions of
-#           bf16x6; inference forwards only; |weight| < 255, |activation| < 65504 (csrc/bf16x6.hpp)
+#           bf16x6; inference forwards only; |weight| < 255.9 (merged W1 Wq included; merged W1 P2 < 4095),
+#           |activation| < 65504, |attention hidden| < 4094 (csrc/bf16x6.hpp).  A weight outside is rejected when the
+#           weights are prepared; an activation outside makes its rows NaN
 
 
 def _env_flag(name, default):
