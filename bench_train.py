@@ -6,6 +6,9 @@ gradient all-reduce on RCCL.  Separate from bench.py (whose single JSON line is 
 inference metric): prints one JSON line with the step time.
 
     python bench_train.py [--steps K --warmup W]            (1 GPU)
+    python bench_train.py --kind greater                     (the published GREATER training command instead: no norm, one
+                                                              abstract level, G = 5, n_points 14336, video_len 12, density +
+                                                              colour (rgb_nosigmoid) + tracking losses)
     python bench_train.py --gpus N                           (re-launches itself as N ranks on 127.0.0.1)
     python -m torch.distributed.run --nproc-per-node N bench_train.py --gpus N
 
@@ -28,6 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import occlusions4d_amd as pk  # noqa: E402
 
 N_POINTS, FRAMES, QUERIES, SEED = 28672, 4, 17203, 1830
+N_POINTS_GREATER = 14336
 PEAK_F32_MFMA = 157.3      # TFLOP/s, MI355X fp32 matrix peak (MI355X_MICROARCH.md)
 
 
@@ -108,6 +112,7 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--kind', choices=['carla', 'greater'], default='carla', help='carla: BASELINE config 5 (density + segmentation losses); greater: the published GREATER training command (density 1 / colour 1 / tracking 1, rgb_nosigmoid, G = 5 decoder, n_points 14336)')
     ap.add_argument('--no-checkpoint', action='store_true', help='store the attention pair tensors (merged form; OCC4D_STORED_ATTENTION_FORM=as_written for the round-1 path) instead of recomputing them in backward')
     ap.add_argument('--per-frame', action='store_true', help='decode the target frames one after the other (the reference\'s loop) instead of in one batched decoder call')
     ap.add_argument('--no-prefetch', action='store_true', help='do not prefetch the next step\'s FPS chain / kNNs under this step\'s backward')
@@ -119,6 +124,8 @@ def main():
                          'generators only, like a dataloader); --sampler-serial draws them in front of the step')
     ap.add_argument('--sampler-serial', action='store_true', help='with --sampler: sample, synchronise, then step')
     args = ap.parse_args()
+    if args.kind != 'carla' and args.sampler:
+        ap.error('--sampler draws CARLA supervision points (semantic balancing); use it with --kind carla')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         return self_launch(args.gpus)
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -156,25 +163,39 @@ def main():
     selection = dict(checkpoint_attention=not args.no_checkpoint)     # kernels.Selection fields of this step (no globals)
     if args.precision == 'bf16x6':
         selection.update(train_precision='bf16x6', logit_precision='bf16x6')   # (logit: the recompute path's fused forward kernel)
-    pa, ia, inf = pk.configs.model_args('carla', N_POINTS)
+    greater = args.kind == 'greater'
+    n_points = N_POINTS_GREATER if greater else N_POINTS
+    pa, ia, inf = pk.configs.model_args(args.kind, n_points)
     esd, dsd = pk.configs.synthetic_weights(pa, ia, SEED)
     enc = pk.model.PointCompletionNetV3(**pa).to(device).train()
     dec = pk.implicit.LocalPclResnetFC(**ia).to(device).train()
     enc.load_state_dict(esd)
     dec.load_state_dict(dsd)
-    pcl = pk.configs.synthetic_pcl('carla', N_POINTS, 12, SEED + rank).to(device)
+    pcl = pk.configs.synthetic_pcl(args.kind, n_points, 12, SEED + rank).to(device)
     rng = np.random.default_rng(SEED + 100 + rank)
-    (x0, x1), (y0, y1), (z0, z1) = (0.0, 40.0), (-16.0, 16.0), (-1.0, 6.4)
+    (x0, x1), (y0, y1), (z0, z1) = ((-5.0, 5.0), (-5.0, 5.0), (-1.0, 5.0)) if greater else ((0.0, 40.0), (-16.0, 16.0), (-1.0, 6.4))
     q = np.concatenate([rng.uniform([x0, y0, z0], [x1, y1, z1], size=(FRAMES, QUERIES, 3)),
                         np.broadcast_to(np.arange(FRAMES, dtype=np.float64)[:, None, None], (FRAMES, QUERIES, 1))], -1)
-    target = np.concatenate([rng.integers(0, 2, size=(FRAMES, QUERIES, 1)), rng.uniform(size=(FRAMES, QUERIES, 3)),
-                             np.zeros((FRAMES, QUERIES, 1)), rng.integers(-1, 13, size=(FRAMES, QUERIES, 1))], -1)
+    if greater:
+        # targets with the -1 "not available" markers the data loaders produce (tests/golden_cases.py:loss_inputs): missing
+        # colours, untracked points; air rows carry zero colours
+        dens = (rng.uniform(size=(FRAMES, QUERIES, 1)) < 0.45).astype(np.float64)
+        rgb = rng.uniform(size=(FRAMES, QUERIES, 3))
+        rgb[rng.uniform(size=(FRAMES, QUERIES)) < 0.2] = -1.0
+        rgb = np.where(dens > 0.5, rgb, 0.0)
+        target = np.concatenate([dens, rgb, rng.integers(-1, 2, size=(FRAMES, QUERIES, 1)),
+                                 rng.integers(-1, 13, size=(FRAMES, QUERIES, 1))], -1)
+    else:
+        target = np.concatenate([rng.integers(0, 2, size=(FRAMES, QUERIES, 1)), rng.uniform(size=(FRAMES, QUERIES, 3)),
+                                 np.zeros((FRAMES, QUERIES, 1)), rng.integers(-1, 13, size=(FRAMES, QUERIES, 1))], -1)
     q = torch.from_numpy(q.astype(np.float32)).to(device)
     target = torch.from_numpy(target.astype(np.float32)).to(device)
     # static_shapes: the loss's masked means by weighting instead of boolean indexing (training.implicit_loss) -- the
     # form without data-dependent shapes; it removes the 12 device->host reads (one per boolean index) that
     # stall the host between forward and backward.  OCC4D_BENCH_INDEXED_LOSS=1: the reference's indexing form.
     lkw = dict(density_lw=1.0, segmentation_lw=0.6, static_shapes=os.environ.get('OCC4D_BENCH_INDEXED_LOSS') != '1')
+    if greater:
+        lkw.update(color_lw=1.0, segmentation_lw=0.0, tracking_lw=1.0, color_mode='rgb_nosigmoid')
     step = pk.training.TrainStep(enc, dec, lr=1e-3, grad_clip=0.2, loss_kwargs=lkw, kernel_selection=selection)
 
     def fence():
@@ -276,8 +297,8 @@ def main():
         fence()
         executed = sum(v['total_flops'] for v in summ.values())
         top = max(summ.items(), key=lambda kv: kv[1]['total_ms']) if summ else None
-        m_abs = pk.distributed.abstract_shape(enc, N_POINTS)[0]
-        written = as_written_flops(pa, ia, N_POINTS, FRAMES * QUERIES, m_abs)
+        m_abs = pk.distributed.abstract_shape(enc, n_points)[0]
+        written = as_written_flops(pa, ia, n_points, FRAMES * QUERIES, m_abs)
         sec = elapsed / args.steps
         roof = dict(bound='mfma', peak=PEAK_F32_MFMA, unit='TFLOP/s',
                     achieved=executed / sec / 1e12, frac=executed / sec / 1e12 / PEAK_F32_MFMA,
@@ -297,13 +318,18 @@ def main():
                                             'six times): frac against the fp32 MFMA peak is informational for this mode')
     if rank == 0:
         print(json.dumps({
-            'metric': 'training step (BASELINE config 5: CARLA-4D, batch 1/GPU, n_points=28672, 4 x 17203 queries)',
+            'metric': ('training step (published GREATER command, batch 1/GPU, n_points=14336, 4 x 17203 queries)' if greater else
+                       'training step (BASELINE config 5: CARLA-4D, batch 1/GPU, n_points=28672, 4 x 17203 queries)'),
+            'kind': args.kind,
             'value': world * args.steps / elapsed, 'unit': 'examples/s', 'n_gpus': world, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True,
             'scaling': 'weak', 'dtype': 'f32' if args.precision == 'f32' else 'f32 weight gradients; forward Linears, their data gradients, the forward attention kernel (and any pair-tensor recompute) on bf16 x 3 pieces, 6 products, f32 accumulate (fp32-class)', 'precision': args.precision, 'data': 'synthetic', 'losses': losses, 'sampler_ms_per_step': sampler_ms, 'sampler': (None if not args.sampler else 'in front of the step (serial)' if args.sampler_serial else "next step's points drawn on a side stream beside this step (host time per step in sampler_ms_per_step)"), 'graph': False, 'loss_read': 'after the timed region', 'geometry_prefetch': bool(nxt), 'gradient_overlap': (('parameter gradients on a second stream beside the data-gradient chain, at most %.0f GB of operands held for it' % (pk.autograd.GRADIENT_OVERLAP_BYTES / 2 ** 30)) if pk.autograd.GRADIENT_OVERLAP else False), 'frames_batched': bool(step.batch_frames), 'attention_backward': ('stored pair tensors (%s form)' % pk.kernels.defaults().stored_attention_form) if args.no_checkpoint else {'all': 'fused forward kernel keeps a, logits and pe; backward walks them in equal chunks of at most %d queries, nothing recomputed', 'logits': 'fused forward kernel keeps its logits; a and pe recomputed in backward in equal chunks of at most %d queries', 'none': 'recompute in backward (equal chunks of at most %d queries)'}[pk.kernels.defaults().store_pairs] % pk.kernels.defaults().checkpoint_chunk,
             'peak_mem_gb': torch.cuda.max_memory_allocated() / 2 ** 30,
             'roofline': roof,
-            'config': {'workload': 'CARLA-4D training step (BASELINE configs[4]): batch 1 per GPU, n_points=%d, %d x %d '
+            'config': {'workload': ('GREATER training step (README command: no norm, one abstract level, G = 5): batch 1 per GPU, '
+                                    'n_points=%d, %d x %d supervision queries, density + colour (rgb_nosigmoid) + tracking losses, '
+                                    'AdamW, clip 0.2' % (n_points, FRAMES, QUERIES)) if greater else
+                                   'CARLA-4D training step (BASELINE configs[4]): batch 1 per GPU, n_points=%d, %d x %d '
                                    'supervision queries, density + segmentation losses, AdamW, clip 0.2' % (N_POINTS, FRAMES, QUERIES),
                        'parallelism': 'single GPU' if world == 1 else 'dp%d (one process per GPU, one flat gradient all-reduce)' % world,
                        'rccl_ranks': rccl_ranks, 'backend': backend if use_dist else None,

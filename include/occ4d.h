@@ -668,11 +668,38 @@ int occ4d_pt_cross_attn_f16w_f32(const float* aq, int64_t ld_aq, const float* qp
  *   loss[0] = sum_cells [ density_lw mean_i BCEwithLogits(out[i, 0], target[i, 0])
  *                         + segmentation_lw mean_{label_i >= 0} CE(out[i, g - semantic_classes :], label_i) ] / cells
  * grad (cells, n, g) (row stride ldg) or NULL: d loss / d out.  workspace: occ4d_implicit_loss_workspace_floats(cells) floats.
- * Deterministic (fixed-order partial sums).  Colour / tracking terms are not covered (weights 0 in the published configs). */
+ * Deterministic (fixed-order partial sums).  The two terms of the published CARLA command; the published GREATER command also
+ * weights colour and tracking: occ4d_implicit_loss_terms_f32 below. */
 int64_t occ4d_implicit_loss_workspace_floats(int cells);
 int occ4d_implicit_loss_f32(const float* out, int64_t ldo, const float* target, int64_t ldt, int cells, int n, int g, int label_col,
                             int semantic_classes, float density_lw, float segmentation_lw, float* workspace, float* loss,
                             float* grad, int64_t ldg, void* stream);
+/* All four terms of the training loss, value, per-term values and gradient in two launches (csrc/loss.hip; loss.py:50-194,
+ * 243-250, 276-277 with the pre-loss squash of pipeline.py:198-212 folded in and differentiated through).  out (cells, n, g) RAW
+ * decoder outputs (row stride ldo); target (cells, n, 6) (row stride ldt) = (density, R, G, B, mark_track, segm).  A cell is one
+ * (frame, example).  color_mode: 0 rgb (sigmoid of channels 1:4), 1 rgb_nosigmoid (clamp of 1:4 to [0, 1]; gradient on the closed
+ * interval only), 2 hsv (12 hue logits 1:13, clamp of saturation / value 13:15), 3 bins (9 logits 1:10).  Per cell, solid =
+ * target[0] >= 0.1:
+ *   density       mean over all rows of BCEwithLogits(out[0], target[0])
+ *   colour        over rows solid AND target[1] >= 0.  rgb*: mean |o - (R, G, B)| over rows x 3.  hsv: (H, S, V) = rgb_to_hsv of
+ *                 the target (utils/utils.py:169-191), hue class round(H / 360 * 12) (half to even; 12 -> 0);
+ *                 ( [CE(hue) over rows with S >= 0.2 and V >= 0.2] / 2 if the cell has >= 16 such rows, else 0
+ *                   + mean |o[13] - S| + mean |o[14] - V| ) / 3.  bins: class = 6 hue bins, or black (V < 0.2) / gray
+ *                 (0.2 <= V < 0.6) / white (0.6 <= V) where S < 0.3 or V < 0.3; mean CE / 3.
+ *   segmentation  mean over rows with target[5] >= 0 of CE(out[g - semantic_classes :], target[5])
+ *   tracking      mean over rows solid AND target[4] >= 0 of BCEwithLogits(out[track_idx], target[4]), track_idx = 4 / 4 / 15 / 10
+ * loss[0] = sum_cells sum_terms weight * term / cells.  terms[4] = the unweighted terms averaged over the cells, in the order
+ * colour, density, segmentation, tracking (what the reference logs, loss.py:255-294); 0 for a term whose weight is 0.  A term
+ * with weight 0 is not evaluated and its channels need not exist; a weighted term whose selection is empty in some cell makes the
+ * results non-finite, as the reference's mean over an empty selection.  grad (cells, n, g) (row stride ldg) or NULL:
+ * d loss[0] / d out.  Requires weights >= 0, g wide enough for the weighted terms' channels, and the semantic_classes
+ * segmentation channels behind them.  workspace: occ4d_implicit_loss_terms_workspace_floats(cells) floats.  No atomics:
+ * bit-reproducible from call to call. */
+int64_t occ4d_implicit_loss_terms_workspace_floats(int cells);
+int occ4d_implicit_loss_terms_f32(const float* out, int64_t ldo, const float* target, int64_t ldt, int cells, int n, int g,
+                                  int color_mode, int semantic_classes, float density_lw, float color_lw, float segmentation_lw,
+                                  float tracking_lw, float* workspace, float* loss, float* terms, float* grad, int64_t ldg,
+                                  void* stream);
 
 /* ResnetBlockFC (model/implicit.py:92-101), width 416, relu, as ONE launch in the fp16 two-piece scheme (csrc/resblock_f16x3.hip,
  * round 6): y = x + W1 relu(W0 relu(x) + b0) + b1 with the hidden activation in registers (the two-launch form moves it through

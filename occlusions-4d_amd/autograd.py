@@ -433,6 +433,25 @@ class ImplicitLossFn(Function):
         return grad * g, None, None, None, None
 
 
+class ImplicitLossTermsFn(Function):
+    """training.implicit_loss's four terms as one library call (ops.implicit_loss_terms_fused) on the RAW decoder outputs ->
+    (total, terms (4,)): the gradient is formed with the value and scaled by the incoming scalar in backward; the per-term
+    values are for logging and carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, out, target, color_mode, semantic_classes, density_lw, color_lw, segmentation_lw, tracking_lw):
+        loss, terms, grad = ops.implicit_loss_terms_fused(out, target, color_mode, semantic_classes, density_lw, color_lw,
+                                                          segmentation_lw, tracking_lw, want_grad=out.requires_grad)
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(terms)
+        return loss.reshape(()), terms
+
+    @staticmethod
+    def backward(ctx, g, _g_terms):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None, None, None, None, None, None
+
+
 class PosHiddenFn(Function):
     """r = relu(P1 (pos_i - pos2_j) + c1); gradients to P1, c1 only (coordinates are data)."""
 

@@ -429,7 +429,7 @@ def rowlin_bf16x6(x, w, b=None, relu_in=False, res=None, out=None, packed=None, 
 
 def implicit_loss_fused(out, target, semantic_classes, density_lw, segmentation_lw, want_grad=True):
     """occ4d_implicit_loss_f32: density BCE-with-logits + masked segmentation cross entropy over (cells, n, g) raw decoder
-    outputs (training.implicit_loss's terms with non-zero weight in the published configurations) -> (loss (1,), d loss / d out
+    outputs (the two terms of the published CARLA command; all four: implicit_loss_terms_fused) -> (loss (1,), d loss / d out
     or None), two launches."""
     out, target = _dev(out, name='out'), _dev(target, name='target')
     assert out.dim() == 3 and target.dim() == 3 and out.is_contiguous() and target.is_contiguous()
@@ -443,6 +443,30 @@ def implicit_loss_fused(out, target, semantic_classes, density_lw, segmentation_
                                          int(semantic_classes), float(density_lw), float(segmentation_lw), _ptr(ws), _ptr(loss),
                                          _ptr(grad), g, _stream()))
     return loss, grad
+
+
+COLOR_MODES = {'rgb': 0, 'rgb_nosigmoid': 1, 'hsv': 2, 'bins': 3}      # color_mode argument of occ4d_implicit_loss_terms_f32
+
+
+def implicit_loss_terms_fused(out, target, color_mode, semantic_classes, density_lw, color_lw, segmentation_lw, tracking_lw,
+                              want_grad=True):
+    """occ4d_implicit_loss_terms_f32: all four terms of training.implicit_loss (density BCE, colour in the mode's form with the
+    pre-loss squash folded in, masked segmentation cross entropy, tracking BCE) over (cells, n, g) RAW decoder outputs and
+    (cells, n, 6) targets -> (loss (1,), terms (4,) = unweighted colour / density / segmentation / tracking means, d loss / d out
+    or None), two launches.  color_mode: a name of COLOR_MODES or its number."""
+    out, target = _dev(out, name='out'), _dev(target, name='target')
+    assert out.dim() == 3 and target.dim() == 3 and out.is_contiguous() and target.is_contiguous()
+    cells, n, g = out.shape
+    assert tuple(target.shape) == (cells, n, 6), 'target (cells, n, 6) = (density, R, G, B, mark_track, segm)'
+    L = _lib.lib()
+    ws = torch.empty((int(L.occ4d_implicit_loss_terms_workspace_floats(cells)),), dtype=torch.float32, device=out.device)
+    scalars = torch.empty((5,), dtype=torch.float32, device=out.device)
+    loss, terms = scalars[:1], scalars[1:]
+    grad = torch.empty_like(out) if want_grad else None
+    _lib.check(L.occ4d_implicit_loss_terms_f32(_ptr(out), g, _ptr(target), 6, cells, n, g, int(COLOR_MODES.get(color_mode, color_mode)),
+                                               int(semantic_classes), float(density_lw), float(color_lw), float(segmentation_lw),
+                                               float(tracking_lw), _ptr(ws), _ptr(loss), _ptr(terms), _ptr(grad), g, _stream()))
+    return loss, terms, grad
 
 
 def resblock_f16x3(x, w0, b0, w1, b1, out=None, packed=None):

@@ -24,7 +24,7 @@ from . import autograd, kernels, ops
 from .point_transformer_layer import invalidate_weight_caches
 
 
-FUSED_LOSS = os.environ.get('OCC4D_FUSED_LOSS', '1') == '1'      # density + segmentation terms as one library call (csrc/loss.hip)
+FUSED_LOSS = os.environ.get('OCC4D_FUSED_LOSS', '1') == '1'      # the loss terms, value and gradient, as one library call (csrc/loss.hip)
 
 
 def _masked_mean(values, mask):
@@ -111,8 +111,24 @@ def _color_term(o, y, keep, color_mode, static_shapes):
     return mean(F.cross_entropy(o[:, 1:10], target, reduction='none'), keep) / 3.0
 
 
+def _fused_loss_layout(g, color_mode, semantic_classes, density_lw, color_lw, segmentation_lw, tracking_lw):
+    """Whether occ4d_implicit_loss_terms_f32 takes this channel layout (its argument contract, include/occ4d.h): the weighted
+    terms' channels exist and the segmentation classes sit behind them.  Anything else stays on the torch path below."""
+    if min(density_lw, color_lw, segmentation_lw, tracking_lw) < 0.0:
+        return False
+    used = 1
+    if color_lw > 0.0:
+        used = TRACK_IDX[color_mode]              # (one past the last colour channel)
+    if tracking_lw > 0.0:
+        used = TRACK_IDX[color_mode] + 1
+    if g < used:
+        return False
+    return segmentation_lw <= 0.0 or 1 <= semantic_classes <= g - used
+
+
 def implicit_loss(implicit_output, implicit_target, density_lw=1.0, color_lw=0.0, segmentation_lw=0.0,
-                  tracking_lw=0.0, color_mode='rgb', semantic_classes=13, static_shapes=False, squashed=False):
+                  tracking_lw=0.0, color_mode='rgb', semantic_classes=13, static_shapes=False, squashed=False,
+                  return_terms=False):
     """loss.MyLosses.per_example + entire_batch (loss.py:200-294) on the RAW decoder outputs.
 
     implicit_output (T,N,G) or (T,B,N,G) logits (density, R, G, B, mark_track, segm?); implicit_target
@@ -123,24 +139,32 @@ def implicit_loss(implicit_output, implicit_target, density_lw=1.0, color_lw=0.0
     where density >= 0.1 AND mark_track >= 0 (:175-194) -- the per-(example, frame) values are averaged
     (:243-250) and summed with their weights (:276-277).
     static_shapes=True computes the masked means by weighting instead of boolean indexing (no host sync, no
-    data-dependent shapes): the form a captured step needs, and the one the eager step uses to avoid its host reads."""
+    data-dependent shapes): the form a captured step needs, and the one the eager step uses to avoid its host reads.
+    return_terms=True: (total, terms) with terms a detached (4,) tensor on the outputs' device -- the unweighted colour /
+    density / segmentation / tracking means the reference logs every step (:255-294), 0 for a term without weight; no
+    host read is added for it."""
     if implicit_output.dim() == 3:
         implicit_output, implicit_target = implicit_output[:, None], implicit_target[:, None]
-    if not squashed and color_lw > 0.0:
-        implicit_output = squash_for_loss(implicit_output, color_mode)
     if color_mode not in TRACK_IDX:
         raise ValueError('Unknown color_mode: ' + str(color_mode))
     track_idx = TRACK_IDX[color_mode]    # the tracking logit sits behind the colour channels (utils.get_track_idx)
-    if (FUSED_LOSS and implicit_output.is_cuda and color_lw == 0.0 and tracking_lw == 0.0 and not ops._lib.is_twin()
+    if (FUSED_LOSS and implicit_output.is_cuda and not ops._lib.is_twin() and not (squashed and color_lw > 0.0)
             and implicit_output.dtype == torch.float32 and implicit_target.dtype == torch.float32
-            and semantic_classes < implicit_output.shape[-1]):
-        # the two terms the published configurations weight, value and gradient, as one library call (csrc/loss.hip, round 6:
-        # ~60 element-wise launches and 6.6 ms of host time per step otherwise); same means over the same points
+            and implicit_target.shape[-1] == 6
+            and _fused_loss_layout(implicit_output.shape[-1], color_mode, semantic_classes, density_lw, color_lw,
+                                   segmentation_lw, tracking_lw)):
+        # every weighted term, the squash included, value and gradient, as one library call of two launches (csrc/loss.hip;
+        # the two-term form of round 6 replaced ~60 element-wise launches and 6.6 ms of host time per step); same means over
+        # the same points as the eager form below (an empty selection gives a non-finite total in both)
         (nf, nb, n, g) = implicit_output.shape
-        return autograd.ImplicitLossFn.apply(implicit_output.reshape(nf * nb, n, g).contiguous(),
-                                             implicit_target.reshape(nf * nb, n, -1).contiguous(), int(semantic_classes),
-                                             float(density_lw), float(segmentation_lw))
+        total, terms = autograd.ImplicitLossTermsFn.apply(
+            implicit_output.reshape(nf * nb, n, g).contiguous(), implicit_target.reshape(nf * nb, n, 6).contiguous(),
+            color_mode, int(semantic_classes), float(density_lw), float(color_lw), float(segmentation_lw), float(tracking_lw))
+        return (total, terms) if return_terms else total
+    if not squashed and color_lw > 0.0:
+        implicit_output = squash_for_loss(implicit_output, color_mode)
     total = implicit_output.new_zeros(())
+    sums = [0.0, 0.0, 0.0, 0.0]          # (colour, density, segmentation, tracking) over the cells, for return_terms
     (nf, nb) = implicit_output.shape[:2]
     cells = nf * nb
     for t in range(nf):
@@ -148,9 +172,12 @@ def implicit_loss(implicit_output, implicit_target, density_lw=1.0, color_lw=0.0
             o, y = implicit_output[t, b], implicit_target[t, b]
             solid = y[:, 0] >= 0.1
             if density_lw > 0.0:
-                total = total + density_lw * F.binary_cross_entropy_with_logits(o[:, 0], y[:, 0]) / cells
+                term = F.binary_cross_entropy_with_logits(o[:, 0], y[:, 0])
+                sums[1] = sums[1] + term.detach()
+                total = total + density_lw * term / cells
             if color_lw > 0.0:
                 term = _color_term(o, y, solid & (y[:, 1] >= 0.0), color_mode, static_shapes)
+                sums[0] = sums[0] + term.detach()
                 total = total + color_lw * term / cells
             if segmentation_lw > 0.0:
                 lab = y[:, -1].to(torch.int64)
@@ -160,6 +187,7 @@ def implicit_loss(implicit_output, implicit_target, density_lw=1.0, color_lw=0.0
                     term = _masked_mean(ce, keep)
                 else:
                     term = F.cross_entropy(o[keep][:, -semantic_classes:], lab[keep])
+                sums[2] = sums[2] + term.detach()
                 total = total + segmentation_lw * term / cells
             if tracking_lw > 0.0:
                 keep = solid & (y[:, 4] >= 0.0)
@@ -169,8 +197,12 @@ def implicit_loss(implicit_output, implicit_target, density_lw=1.0, color_lw=0.0
                     term = _masked_mean(bce, keep)
                 else:
                     term = F.binary_cross_entropy_with_logits(o[keep, track_idx], y[keep, 4])
+                sums[3] = sums[3] + term.detach()
                 total = total + tracking_lw * term / cells
-    return total
+    if not return_terms:
+        return total
+    zero = total.new_zeros(())
+    return total, torch.stack([s if torch.is_tensor(s) else zero for s in sums]).detach() / cells
 
 
 class Participation:
@@ -422,6 +454,9 @@ class TrainStep:
         self.grad_clip = grad_clip
         self.loss_kwargs = loss_kwargs or {}
         self.participation = Participation()
+        # the last step's unweighted (colour, density, segmentation, tracking) terms, what the reference logs every step
+        # (loss.py:255-294): a (4,) device tensor, not read by the step itself
+        self.last_loss_terms = None
 
     batch_frames = True
 
@@ -443,7 +478,8 @@ class TrainStep:
         else:
             out = torch.stack([self.implicit_net(points_query[t], pcl_abstract[0], features_global[0], None)[0]
                                for t in range(T_)])
-        return implicit_loss(out, implicit_target, **self.loss_kwargs)
+        loss, self.last_loss_terms = implicit_loss(out, implicit_target, return_terms=True, **self.loss_kwargs)
+        return loss
 
     def __call__(self, pcl_input, points_query, implicit_target, next_pcl_input=None):
         """`next_pcl_input` (optional): the NEXT step's point cloud, already resident.  Its farthest-point chain and
