@@ -32,7 +32,7 @@ extern "C" {
 #define OCC4D_EINVAL (-1)   /* bad argument (maps to AssertionError / ValueError) */
 #define OCC4D_ELAUNCH (-2)  /* HIP launch failure */
 
-#define OCC4D_ABI_VERSION 4
+#define OCC4D_ABI_VERSION 5
 
 int occ4d_abi_version(void);
 const char* occ4d_last_error(void);
@@ -523,6 +523,17 @@ int occ4d_adamw_clip_f32(float* params_flat, float* exp_avg, float* exp_avg_sq, 
                          const int64_t* offsets, const int64_t* numels, int n_tensors, const int32_t* chunk_tensor,
                          const int32_t* chunk_start, int n_chunks, float lr, float beta1, float beta2, float eps,
                          float weight_decay, float max_norm, float* workspace, void* stream);
+/* The same step with PER-TENSOR hyper-parameters (tensors of different param_groups in one launch sequence) and a gradient
+ * scale.  Buffers, chunk tables and workspace as above, except that grad_ptrs holds 5 n_tensors 64-bit words: behind the
+ * n_tensors addresses, tensor t owns 8 floats (word n_tensors + 4 t on): 1 - beta1^k, sqrt(1 - beta2^k), lr, beta1,
+ * beta2, eps, weight_decay, one unused.  The caller checks their ranges (lr, eps >= 0, betas in [0, 1)).
+ * Every gradient is read as g * grad_scale (1 = off; 1 / world after a SUM all-reduce, or an un-scale factor), in the norm
+ * (total_norm is the norm of the scaled gradients) and in the update.  With the same hyper-parameters in every row and
+ * grad_scale = 1 the results equal occ4d_adamw_clip_f32's bit for bit. */
+int occ4d_adamw_clip_groups_f32(float* params_flat, float* exp_avg, float* exp_avg_sq, const int64_t* grad_ptrs,
+                                const int64_t* offsets, const int64_t* numels, int n_tensors, const int32_t* chunk_tensor,
+                                const int32_t* chunk_start, int n_chunks, float max_norm, float grad_scale,
+                                float* workspace, void* stream);
 int occ4d_axpby_f32(const float* a, int64_t lda, float alpha, const float* b, int64_t ldb, float beta, int n, int d,
                     float* out, int64_t ldo, void* stream);
 int occ4d_broadcast_rows_f32(const float* vec, float scale, int n, int d, float* out, int64_t ldo, void* stream);

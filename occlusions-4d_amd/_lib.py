@@ -5,7 +5,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libocc4d.so')
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 OK, EINVAL, ELAUNCH = 0, -1, -2
 
@@ -188,6 +188,7 @@ SIGNATURES = {
                                   C.c_int64, _s]),
     'occ4d_adamw_chunk': (C.c_int, []),
     'occ4d_adamw_clip_f32': (C.c_int, [_f, _f, _f, _i, _i, _i, C.c_int, _i, _i, C.c_int] + [C.c_float] * 6 + [_f, _s]),
+    'occ4d_adamw_clip_groups_f32': (C.c_int, [_f, _f, _f, _i, _i, _i, C.c_int, _i, _i, C.c_int] + [C.c_float] * 2 + [_f, _s]),
     'occ4d_broadcast_rows_f32': (C.c_int, [_f, C.c_float, C.c_int, C.c_int, _f, C.c_int64, _s]),
     # packers + path-level entry points
     'occ4d_pack_trunk_rows_f32': (C.c_int, [_f, C.c_int64, C.c_int, _f, _s]),

@@ -12,6 +12,7 @@ forward and backward kernel is libocc4d.so.  Query points and their targets are 
 the training-time point sampler that draws them (utils/geometry.py:578-1105, rank 2 of 8(f)) is
 geometry.GuidedImplicitPointSampler (bench_train.py --sampler runs it inside the step).
 """
+import copy
 import math
 import os
 
@@ -327,24 +328,50 @@ class SideStreamSampler:
         return q, tgt
 
 
-class FusedClipAdamW:
+_UNSET = object()
+
+
+class FusedClipAdamW(torch.optim.Optimizer):
     """clip_grad_norm_(max_norm) + torch.optim.AdamW.step() for all parameters as ONE library call of three launches and no
-    host read (occ4d_adamw_clip_f32, csrc/optim.hip; train.py:107-109, 287-293).
+    host read (occ4d_adamw_clip_groups_f32, csrc/optim.hip; train.py:107-109, 287-293).
 
     The parameters become views of one flat fp32 buffer (`p.data` is re-pointed once, here; values unchanged) and the two
     moment buffers are flat beside it; gradients stay wherever the backward pass left them -- a table of their addresses
-    (pinned host array -> one small asynchronous upload) is the only per-step host work: ~0.3 ms against ~15 ms for the
-    ~150-tensor foreach path of torch (profiles/r05_train_phases.txt).  A parameter whose .grad is None is skipped
-    entirely (no decay, no moment update), as torch does.  The gradients are NOT scaled in memory: the clip coefficient
-    is applied inside the update (`last_norm` / `last_coef` stay on the device for whoever wants to log them)."""
+    and per-tensor hyper-parameters (pinned host array -> one small asynchronous upload) is the only per-step host work:
+    ~0.3 ms against ~15 ms for the ~150-tensor foreach path of torch (profiles/r05_train_phases.txt).  A parameter whose
+    .grad is None is skipped entirely (no decay, no moment update), as torch does.  The gradients are NOT scaled in
+    memory: the clip coefficient is applied inside the update (`last_norm` / `last_coef` stay on the device for whoever
+    wants to log them).
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        self.params = [p for p in params]
-        assert self.params and all(p.is_cuda and p.dtype == torch.float32 for p in self.params), 'CUDA fp32 parameters'
-        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+    It is a torch.optim.Optimizer: `params` is an iterable of tensors or a list of group dicts with their own lr / betas /
+    eps / weight_decay, read from `param_groups` at EVERY step (an lr scheduler's change acts on the next step; tensors
+    of all groups are updated by the same launch).  `max_norm` (None = no clip) is a group default too, so that a bare
+    `step()` -- what `GradScaler(enabled=False).step(optimizer)` calls -- clips.  `state[p]` holds torch's entries for every
+    parameter that has had a gradient: `exp_avg` / `exp_avg_sq` are VIEWS of the flat moment buffers, `step` is a host
+    integer here and the float32 scalar tensor torch writes in `state_dict()`, whose layout is torch.optim.AdamW's (the
+    moments there are copies).  `load_state_dict()` takes that layout from torch.optim.AdamW or from this class (any
+    device) and copies into the flat buffers; the flat layout this class wrote earlier ('exp_avg' without 'state') still
+    loads.  Refused: amsgrad, maximize, capturable, differentiable, Adam's coupled weight decay, a device-tensor lr (a
+    host read per step), add_param_group() after construction (the flat layout is fixed), and a step after the module
+    was moved or cast (`net.half()`, `net.to(device)`: the modules then read other storage than the step updates)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
+                 capturable=False, differentiable=False, max_norm=None):
+        # the group keys of THIS torch's AdamW (they differ between releases), so that state_dict() is its layout
+        defaults = dict(torch.optim.AdamW([torch.zeros(1)]).defaults)
+        defaults.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
+                        capturable=capturable, differentiable=differentiable, max_norm=max_norm)
+        self._layout_fixed = False
+        super().__init__(params, defaults)
+        self._layout_fixed = True                                           # (add_param_group raises from here on)
+        for k, group in enumerate(self.param_groups):
+            self._hyper(k, group)
+        self.params = [p for group in self.param_groups for p in group['params']]
+        assert all(p.is_cuda and p.dtype == torch.float32 for p in self.params), 'CUDA fp32 parameters'
         self.steps = 0
-        self.counts = [0] * len(self.params)                                # updates per parameter (torch's state['step'])
         dev = self.params[0].device
+        assert all(p.device == dev for p in self.params), 'parameters on one device'
+        T = len(self.params)
         numels = [p.numel() for p in self.params]
         offsets, total = [], 0
         for n in numels:
@@ -357,6 +384,10 @@ class FusedClipAdamW:
             p.data = view
         self.exp_avg = torch.zeros_like(self.flat)
         self.exp_avg_sq = torch.zeros_like(self.flat)
+        self._moments = [(self.exp_avg[off:off + n].view(p.shape), self.exp_avg_sq[off:off + n].view(p.shape))
+                         for p, off, n in zip(self.params, offsets, numels)]
+        self._entries = [None] * T                                          # state[p] of parameter i once it has had a gradient
+        self._where = [(self.flat.data_ptr() + 4 * off, n) for off, n in zip(offsets, numels)]
         chunk = int(ops._lib.lib().occ4d_adamw_chunk())
         ct, cs = [], []
         for t, n in enumerate(numels):
@@ -367,11 +398,37 @@ class FusedClipAdamW:
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)      # noqa: E731
         self._offsets, self._numels, self._chunk_tensor, self._chunk_start = i64(offsets), i64(numels), i32(ct), i32(cs)
         self._n_chunks = len(ct)
-        # the address table is uploaded asynchronously: a ring of pinned staging arrays, each reused only after the upload
-        # that read it has run (the host may be several steps ahead of the device)
-        self._staging = [[torch.zeros((2 * len(self.params),), dtype=torch.int64, pin_memory=True), None] for _ in range(4)]
-        self._grad_ptrs = torch.zeros((2 * len(self.params),), dtype=torch.int64, device=dev)
+        # the table ([0, T): gradient addresses; behind them 8 floats per tensor: bias1, sqrt(bias2), lr, beta1, beta2, eps,
+        # weight_decay, unused) is uploaded asynchronously: a ring of pinned staging arrays, each reused only after the
+        # upload that read it has run (the host may be several steps ahead of the device)
+        self._staging = [[torch.zeros((5 * T,), dtype=torch.int64, pin_memory=True), None] for _ in range(4)]
+        self._grad_ptrs = torch.zeros((5 * T,), dtype=torch.int64, device=dev)
         self._ws = torch.zeros((self._n_chunks + 2,), dtype=torch.float32, device=dev)
+
+    @staticmethod
+    def _hyper(k, group):
+        """(lr, beta1, beta2, eps, weight_decay) of param_groups[k] as floats; ValueError for what the step does not do."""
+        for flag in ('amsgrad', 'maximize', 'capturable', 'differentiable'):
+            if group.get(flag):
+                raise ValueError('FusedClipAdamW: param_groups[%d] sets %s=True, which the fused step does not implement'
+                                 % (k, flag))
+        if group.get('decoupled_weight_decay', True) is False:
+            raise ValueError('FusedClipAdamW: param_groups[%d] asks for Adam\'s coupled weight decay (AdamW only)' % k)
+        lr = group['lr']
+        if torch.is_tensor(lr) and lr.is_cuda:
+            raise ValueError('FusedClipAdamW: param_groups[%d]: lr is a device tensor (a host read in every step)' % k)
+        lr, b1, b2 = float(lr), float(group['betas'][0]), float(group['betas'][1])
+        eps, wd = float(group['eps']), float(group['weight_decay'])
+        if not (lr >= 0.0 and eps >= 0.0 and 0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0 and wd >= 0.0):
+            raise ValueError('FusedClipAdamW: param_groups[%d]: lr=%r, betas=(%r, %r), eps=%r, weight_decay=%r (need lr, eps, '
+                             'weight_decay >= 0 and betas in [0, 1))' % (k, lr, b1, b2, eps, wd))
+        return lr, b1, b2, eps, wd
+
+    def add_param_group(self, param_group):
+        if getattr(self, '_layout_fixed', False):
+            raise RuntimeError('FusedClipAdamW: the flat parameter layout is fixed at construction; build a new optimizer '
+                               'over all parameter groups instead of adding one')
+        super().add_param_group(param_group)
 
     @property
     def last_norm(self):
@@ -388,49 +445,128 @@ class FusedClipAdamW:
             elif p.grad is not None:
                 p.grad.zero_()
 
-    def step(self, max_norm=None):
+    def _set_count(self, i, k):
+        """Parameter i has had k updates; k = 0: no state entry (torch's state of a parameter that never had a gradient)."""
+        if k == 0:
+            self.state.pop(self.params[i], None)
+            self._entries[i] = None
+            return
+        st = self._entries[i]
+        if st is None:
+            st = self._entries[i] = self.state[self.params[i]]
+            st.update(step=0, exp_avg=self._moments[i][0], exp_avg_sq=self._moments[i][1])
+        st['step'] = k
+
+    def step(self, closure=None, max_norm=_UNSET, grad_scale=1.0):
+        """`max_norm` unset: the groups' default (None / 0 = no clip).  `grad_scale`: every gradient is read as
+        g * grad_scale, in the norm and in the update (1 / world after a SUM all-reduce, or an un-scale factor)."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        groups = self.param_groups
+        if max_norm is _UNSET:
+            max_norm = groups[0]['max_norm']
+            if any(g['max_norm'] != max_norm for g in groups[1:]):
+                raise ValueError('FusedClipAdamW: the clip is over the gradients of ALL groups; they need one max_norm')
+        T = len(self.params)
+        if sum(len(g['params']) for g in groups) != T:
+            raise RuntimeError('FusedClipAdamW: param_groups were changed after construction (the flat layout is fixed)')
+        for i, (p, (ptr, n)) in enumerate(zip(self.params, self._where)):
+            if p.data_ptr() != ptr or p.dtype != torch.float32 or p.numel() != n:
+                raise RuntimeError('FusedClipAdamW: parameter %d no longer lives in the optimizer\'s flat buffer: the module '
+                                   'was moved or cast (.to / .half / .cpu) after the optimizer was built; build the '
+                                   'optimizer after that' % i)
+        hyper = [self._hyper(k, g) for k, g in enumerate(groups)]           # (all checked before any count moves)
         self.steps += 1
         slot = self._staging[self.steps % len(self._staging)]
         if slot[1] is not None:
             slot[1].synchronize()
-        b1, b2 = self.betas
-        T = len(self.params)
-        table = slot[0].numpy()                                             # [0, T): addresses; [T, 2 T): (bias1, sqrt(bias2)) pairs
-        bias = table[T:].view(np.float32).reshape(T, 2)
+        table = slot[0].numpy()
+        rows = table[T:].view(np.float32).reshape(T, 8)
         keep = []                                                           # (non-contiguous gradients: packed copies, kept alive)
-        for i, p in enumerate(self.params):
-            g = p.grad
-            if g is None:
-                table[i] = 0
-                continue
-            if not g.is_contiguous():
-                g = g.contiguous()
-                keep.append(g)
-            assert g.dtype == torch.float32 and g.is_cuda
-            table[i] = g.data_ptr()
-            k = self.counts[i] = self.counts[i] + 1
-            bias[i, 0] = 1.0 - b1 ** k
-            bias[i, 1] = math.sqrt(1.0 - b2 ** k)
+        i = 0
+        for group, (lr, b1, b2, eps, wd) in zip(groups, hyper):
+            members = group['params']
+            rows[i:i + len(members), 2:7] = (lr, b1, b2, eps, wd)
+            for p in members:
+                g = p.grad
+                if g is None:
+                    table[i] = 0
+                    i += 1
+                    continue
+                if not g.is_contiguous():
+                    g = g.contiguous()
+                    keep.append(g)
+                assert g.dtype == torch.float32 and g.is_cuda
+                table[i] = g.data_ptr()
+                st = self._entries[i]
+                k = 1 if st is None else st['step'] + 1
+                self._set_count(i, k)
+                rows[i, 0] = 1.0 - b1 ** k
+                rows[i, 1] = math.sqrt(1.0 - b2 ** k)
+                i += 1
         self._grad_ptrs.copy_(slot[0], non_blocking=True)
         L = ops._lib
-        L.check(L.lib().occ4d_adamw_clip_f32(
+        L.check(L.lib().occ4d_adamw_clip_groups_f32(
             ops._ptr(self.flat), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq), ops._ptr(self._grad_ptrs),
-            ops._ptr(self._offsets), ops._ptr(self._numels), len(self.params), ops._ptr(self._chunk_tensor),
-            ops._ptr(self._chunk_start), self._n_chunks, self.lr, b1, b2, self.eps, self.weight_decay,
-            float(max_norm) if max_norm else 0.0, ops._ptr(self._ws), ops._stream()))
+            ops._ptr(self._offsets), ops._ptr(self._numels), T, ops._ptr(self._chunk_tensor),
+            ops._ptr(self._chunk_start), self._n_chunks, float(max_norm) if max_norm else 0.0, float(grad_scale),
+            ops._ptr(self._ws), ops._stream()))
         slot[1] = torch.cuda.Event()
         slot[1].record()
         del keep
+        return loss
 
     def state_dict(self):
-        return dict(step=self.steps, counts=list(self.counts), exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(),
-                    lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
+        """torch.optim.AdamW's layout (loadable by it for the same parameter list); the moments are copies."""
+        sd = super().state_dict()
+        for group in sd['param_groups']:
+            group.pop('max_norm', None)                                     # (not a key of torch's groups)
+        sd['state'] = {i: dict(step=torch.tensor(float(st['step']), dtype=torch.float32), exp_avg=st['exp_avg'].clone(),
+                               exp_avg_sq=st['exp_avg_sq'].clone()) for i, st in sd['state'].items()}
+        return sd
 
     def load_state_dict(self, sd):
-        self.steps = int(sd['step'])
-        self.counts = list(sd.get('counts', [self.steps] * len(self.params)))
-        self.exp_avg.copy_(sd['exp_avg'])
-        self.exp_avg_sq.copy_(sd['exp_avg_sq'])
+        T = len(self.params)
+        if 'state' not in sd and 'exp_avg' in sd:                           # the flat layout this class wrote earlier
+            counts = [int(k) for k in sd.get('counts', [int(sd['step'])] * T)]
+            assert len(counts) == T
+            self.exp_avg.copy_(sd['exp_avg'])
+            self.exp_avg_sq.copy_(sd['exp_avg_sq'])
+            self.steps = int(sd['step'])
+            for i, k in enumerate(counts):
+                self._set_count(i, k)
+            return
+        groups, saved = self.param_groups, sd['param_groups']
+        if len(groups) != len(saved):
+            raise ValueError('loaded state dict has a different number of parameter groups')
+        if any(len(g['params']) != len(s['params']) for g, s in zip(groups, saved)):
+            raise ValueError('loaded state dict contains a parameter group that doesn\'t match the size of optimizer\'s group')
+        merged = [dict(g, **{k: copy.deepcopy(v) for k, v in s.items() if k != 'params'}) for g, s in zip(groups, saved)]
+        for k, group in enumerate(merged):
+            self._hyper(k, group)                                           # (refused before anything is changed)
+        index = {pid: i for i, pid in enumerate(pid for s in saved for pid in s['params'])}
+        entries = {}
+        for pid, st in sd['state'].items():
+            if pid not in index:
+                raise ValueError('loaded state dict has state for a parameter (%r) that no group lists' % (pid,))
+            i = index[pid]
+            if any(tuple(st[name].shape) != tuple(self.params[i].shape) for name in ('exp_avg', 'exp_avg_sq')):
+                raise ValueError('loaded state of parameter %d does not have its shape %s' % (i, tuple(self.params[i].shape)))
+            entries[i] = st
+        for i, (m, v) in enumerate(self._moments):
+            st = entries.get(i)
+            if st is None:
+                m.zero_()
+                v.zero_()
+                self._set_count(i, 0)
+            else:
+                m.copy_(st['exp_avg'])
+                v.copy_(st['exp_avg_sq'])
+                self._set_count(i, int(round(float(st['step']))))
+        for group, new in zip(groups, merged):
+            group.update(new)                                               # (in place: a scheduler may hold the dicts)
 
 
 class TrainStep:
@@ -438,19 +574,27 @@ class TrainStep:
     gradient all-reduce, clip (train.py:107-109, max norm 0.2), optimiser step."""
 
     def __init__(self, pcl_net, implicit_net, lr=1e-3, weight_decay=1e-2, grad_clip=0.2, loss_kwargs=None,
-                 kernel_selection=None, fused_optimizer=True):
+                 kernel_selection=None, fused_optimizer=True, param_groups=None):
         """`kernel_selection`: dict of kernels.Selection fields this step's forward runs under (e.g.
         dict(train_precision='bf16x6', logit_precision='bf16x6', checkpoint_attention=False)); the backward pass follows
-        it through the autograd Functions.  None = the calling thread's scope."""
+        it through the autograd Functions.  None = the calling thread's scope.
+        `param_groups`: a list of optimizer group dicts, or a callable (pcl_net, implicit_net) -> such a list, in place
+        of the single group of all parameters (`lr` / `weight_decay` are the defaults of keys a group leaves out)."""
         self.kernel_selection = dict(kernel_selection or {})
         self.pcl_net, self.implicit_net = pcl_net, implicit_net
         self.params = list(pcl_net.parameters()) + list(implicit_net.parameters())
         # clip + AdamW as one library call over flat buffers (round 6); fused_optimizer=False: torch's own two calls
         self.fused = bool(fused_optimizer) and all(p.is_cuda for p in self.params)
+        groups = self.params
+        if param_groups is not None:
+            groups = param_groups(pcl_net, implicit_net) if callable(param_groups) else param_groups
+            groups = [dict(g, params=list(g['params'])) for g in groups]
+            if sorted(id(p) for g in groups for p in g['params']) != sorted(id(p) for p in self.params):
+                raise ValueError('param_groups must list every parameter of the two networks exactly once')
         if self.fused:
-            self.optimizer = FusedClipAdamW(self.params, lr=lr, weight_decay=weight_decay)
+            self.optimizer = FusedClipAdamW(groups, lr=lr, weight_decay=weight_decay)
         else:
-            self.optimizer = torch.optim.AdamW(self.params, lr=lr, weight_decay=weight_decay)
+            self.optimizer = torch.optim.AdamW(groups, lr=lr, weight_decay=weight_decay)
         self.grad_clip = grad_clip
         self.loss_kwargs = loss_kwargs or {}
         self.participation = Participation()
@@ -501,3 +645,25 @@ class TrainStep:
             self.optimizer.step()
         invalidate_weight_caches()             # merged inference matrices / per-scene tables are stale now
         return loss.detach()
+
+
+def checkpoint_dict(step, lr_scheduler, epoch, args, pcl_args, dset_args, implicit_args):
+    """The reference's checkpoint dict (train.py:339-350) of a TrainStep: optimizer and scheduler state in torch's layout,
+    'scaler' as a disabled GradScaler writes it; torch.save() it and inference.load_models reads the file."""
+    nets = {name: {k: v.detach().cpu() for k, v in net.state_dict().items()}
+            for name, net in (('pcl_net', step.pcl_net), ('implicit_net', step.implicit_net))}
+    return {'optimizer': step.optimizer.state_dict(), 'lr_scheduler': lr_scheduler.state_dict(), 'scaler': {},
+            'epoch': epoch, 'args': args, 'pcl_args': pcl_args, 'dset_args': dset_args, 'implicit_args': implicit_args,
+            'pcl_net': nets['pcl_net'], 'implicit_net': nets['implicit_net']}
+
+
+def resume(step, lr_scheduler, checkpoint):
+    """train.py:323-331 for a TrainStep: networks (copied in place, so the optimizer's flat views stay), optimizer and
+    scheduler from a checkpoint dict; returns the epoch to start with."""
+    step.pcl_net.load_state_dict(checkpoint['pcl_net'])
+    step.implicit_net.load_state_dict({(('pt_blocks.0.' + k[len('pt_block.'):]) if k.startswith('pt_block.') else k): v
+                                       for k, v in checkpoint['implicit_net'].items()})      # (legacy key rename)
+    step.optimizer.load_state_dict(checkpoint['optimizer'])
+    lr_scheduler.load_state_dict(checkpoint['lr_scheduler'])
+    invalidate_weight_caches()
+    return checkpoint['epoch'] + 1
