@@ -1,17 +1,94 @@
-"""ctypes binding of libocc4d.so (include/occ4d.h).  Fails loudly when the library is
-missing or stale: the product has no CPU / PyTorch fallback path."""
+"""ctypes binding of libocc4d.so.  The argument types of every entry point and the integer constants are DERIVED from
+include/occ4d.h when this module is imported (parse_constants / parse_prototypes below): the header is the one place
+where the C ABI is written down; only the four struct layouts are restated here.  Fails loudly when the header or the
+library is missing or stale: the product has no CPU / PyTorch fallback path."""
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libocc4d.so')
-ABI_VERSION = 5
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d.h')
 
-OK, EINVAL, ELAUNCH = 0, -1, -2
 
-_f = C.c_void_p      # device float*
-_i = C.c_void_p      # device int32*/int64*
-_s = C.c_void_p      # hipStream_t
+class NativeLibraryError(RuntimeError):
+    pass
+
+
+def _strip_comments(text):
+    return re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', text, flags=re.S))
+
+
+def parse_constants(text):
+    """{'ABI_VERSION': 5, 'PATH_TRUNK4': 16, ...}: every `#define OCC4D_<NAME> <integer>` of the header text (the value may
+    stand in parentheses).  A define with any other value raises; one without a value (the include guard) is none."""
+    out = {}
+    for name, value in re.findall(r'^[ \t]*#[ \t]*define[ \t]+OCC4D_(\w+)[ \t]+(\S.*?)[ \t]*$', _strip_comments(text), flags=re.M):
+        m = re.fullmatch(r'\(\s*(-?\d+)\s*\)|(-?\d+)', value)
+        if not m:
+            raise NativeLibraryError('include/occ4d.h: cannot parse `#define OCC4D_%s %s` as an integer' % (name, value))
+        out[name] = int(m.group(1) or m.group(2))
+    return out
+
+
+_SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'int64_t': C.c_int64, 'unsigned': C.c_uint, 'float': C.c_float,
+            'double': C.c_double}
+_POINTEES = set(_SCALARS) | {'void', 'unsigned long long'}
+_NOT_A_NAME = {'const', 'unsigned', 'signed', 'long', 'short', 'char', 'int', 'float', 'double', 'void', 'struct'}
+
+
+def _ctype(decl, structs, what, is_return=False):
+    """ctypes type of one parameter (or of the return type) `decl`; `what` names the declaration in the error."""
+    m = re.fullmatch(r'(?:const\s+)?(unsigned long long|\w+)\s*(\*?)\s*(\w*)', ' '.join(decl.split()))
+    if not m or m.group(3) in _NOT_A_NAME or (is_return and m.group(3)):
+        raise NativeLibraryError('include/occ4d.h: cannot parse `%s` in %s' % (decl.strip(), what))
+    base, star = m.group(1), m.group(2)
+    if not star and base in _SCALARS:
+        return _SCALARS[base]
+    if star and base in structs:
+        return C.POINTER(structs[base])
+    if star and is_return and base == 'char':
+        return C.c_char_p
+    if star and base in _POINTEES:
+        return C.c_void_p           # device or host: the header cannot tell, and c_void_p takes an address, byref() and arrays
+    raise NativeLibraryError('include/occ4d.h: unknown type `%s` in %s' % (decl.strip(), what))
+
+
+def parse_prototypes(text, structs):
+    """name -> (restype, [argtypes]) of every `<type> occ4d_<name>(<parameters>);` of the header text.  `structs`: C struct name
+    -> ctypes.Structure for the struct pointers.  Strict: once comments, preprocessor lines, the extern "C" braces and the
+    typedef struct bodies are gone, EVERYTHING left must be such a prototype with known types; else NativeLibraryError."""
+    text = re.sub(r'^[ \t]*#.*$', '', _strip_comments(text), flags=re.M)
+    text = re.sub(r'typedef\s+struct\b[^{};]*\{[^{}]*\}\s*\w+\s*;', '', text)
+    text = re.sub(r'extern\s+"C"\s*\{|^[ \t]*\}[ \t]*$', '', text, flags=re.M)
+    *decls, rest = text.split(';')
+    if rest.strip():
+        raise NativeLibraryError('include/occ4d.h: declaration without `;`: `%s`' % ' '.join(rest.split())[:120])
+    out = {}
+    for decl in decls:
+        what = '`%s`' % ' '.join(decl.split())[:120]
+        m = re.fullmatch(r'\s*([\w\s*]+?)\s*\b(occ4d_\w+)\s*\(([^()]*)\)\s*', decl)
+        if not m or m.group(2) in out:
+            raise NativeLibraryError('include/occ4d.h: cannot parse the declaration %s' % what)
+        params = [] if m.group(3).strip() == 'void' else m.group(3).split(',')
+        out[m.group(2)] = (_ctype(m.group(1), structs, what, is_return=True), [_ctype(p, structs, what) for p in params])
+    return out
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        _HEADER = _f.read()
+except OSError as e:
+    raise NativeLibraryError('include/occ4d.h not found at %s (%s): the ctypes binding is derived from it' % (HEADER_PATH, e))
+
+# ABI_VERSION, OK / EINVAL / ELAUNCH, PATH_*, PROFILE_*, MAX_BLOCKS, MAX_CROSS: the header's `#define OCC4D_*` become module
+# attributes of the same name without the prefix (tests/test_abi.py pins their values)
+CONSTANTS = parse_constants(_HEADER)
+globals().update(CONSTANTS)
+ABI_VERSION, OK, EINVAL, ELAUNCH = (CONSTANTS[k] for k in ('ABI_VERSION', 'OK', 'EINVAL', 'ELAUNCH'))
+MAX_BLOCKS, MAX_CROSS = CONSTANTS['MAX_BLOCKS'], CONSTANTS['MAX_CROSS']
+PROFILE_KINDS = {'cross_attn': CONSTANTS['PROFILE_CROSS_ATTN'], 'resblock': CONSTANTS['PROFILE_RESBLOCK'],
+                 'rowlin': CONSTANTS['PROFILE_ROWLIN']}
 
 
 class LinearArgs(C.Structure):
@@ -27,14 +104,6 @@ class LinearArgs(C.Structure):
         ('add_rows', C.c_void_p), ('ld_add', C.c_int64), ('add_div', C.c_int32),
         ('sub_rows', C.c_void_p), ('ld_sub', C.c_int64), ('sub_idx', C.c_void_p),
     ]
-
-
-# path-level entry points (include/occ4d.h, last section)
-PATH_DEFAULT, PATH_UNFUSED, PATH_FIRST_GEN, PATH_GENERIC_LINEAR, PATH_TRUNK4, PATH_FUSED_INTERP, PATH_BF16X6, PATH_BF16X6_TRUNK = 0, 1, 2, 8, 16, 32, 64, 128
-PATH_SPLIT_F16 = 256
-PROFILE_CROSS_ATTN, PROFILE_RESBLOCK, PROFILE_ROWLIN = 1, 2, 3
-MAX_BLOCKS, MAX_CROSS = 16, 4
-PROFILE_KINDS = {'cross_attn': PROFILE_CROSS_ATTN, 'resblock': PROFILE_RESBLOCK, 'rowlin': PROFILE_ROWLIN}
 
 
 class PtLayerWeights(C.Structure):
@@ -60,230 +129,47 @@ class DecoderWeights(C.Structure):
                [('cross_after', C.c_int32 * MAX_CROSS), ('cross', PtLayerWeights * MAX_CROSS)]
 
 
-_LW, _DW, _EV = C.POINTER(PtLayerWeights), C.POINTER(DecoderWeights), C.POINTER(LaunchEvents)
-
 # name -> (restype, argtypes): every symbol include/occ4d.h declares
-SIGNATURES = {
-    'occ4d_abi_version': (C.c_int, []),
-    'occ4d_is_cpu_twin': (C.c_int, []),
-    'occ4d_last_error': (C.c_char_p, []),
-    'occ4d_knn_f32': (C.c_int, [_f, C.c_int64, C.c_int, _f, C.c_int64, C.c_int, C.c_int, C.c_int, _i, C.c_int,
-                                _f, _s]),
-    'occ4d_fps_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, _i, _i, _s]),
-    'occ4d_fps_start_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, C.c_int, _i, _i, _s]),
-    'occ4d_fps_coop_workspace_bytes': (C.c_int64, []),
-    'occ4d_fps_coop_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _i, _i, _s, _s]),
-    'occ4d_copy_rows_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, C.c_int, C.c_int, _s]),
-    'occ4d_fill_rows_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, C.c_float, _s]),
-    'occ4d_nested_fps_level_i32': (C.c_int, [_i, _i, C.c_int, C.c_int, _i, _i, _s]),
-    'occ4d_fps_repair_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, C.c_int, _i, _i, _s, _s]),
-    'occ4d_fps_coop_debug': (C.c_int, [C.c_uint, C.c_int]),
-    'occ4d_linear_f32': (C.c_int, [C.POINTER(LinearArgs), _s]),
-    'occ4d_pt_pos_hidden_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _i, C.c_int, C.c_int, _f, _f, C.c_int,
-                                          _f, _s]),
-    'occ4d_pt_attn_in_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _i, C.c_int, C.c_int, C.c_int, _f, _s]),
-    'occ4d_pt_softmax_agg_f32': (C.c_int, [_f, _f, C.c_int64, _f, _i, C.c_int, C.c_int, C.c_int, C.c_float, _f,
-                                           C.c_int64, _s]),
-    'occ4d_pt_cross_attn_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, C.c_int64, _i, _f, C.c_int64, _f,
-                                          C.c_int64, _f, _f, _f, _f, _f, _f, _f, _f, C.c_int64, C.c_int, C.c_int,
-                                          C.c_int, C.c_int, C.c_float, _s]),
-    'occ4d_pt_self_attn16_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, C.c_int64, _i, _f, C.c_int64, _f,
-                                           C.c_int64, _f, _f, _f, _f, _f, _f, _f, C.c_int64, C.c_int, C.c_int,
-                                           C.c_int, C.c_int, C.c_float, _s]),
-    'occ4d_matmul_f64': (C.c_int, [_f, C.c_int64, C.c_int64, _f, C.c_int64, C.c_int64, _f, C.c_int, C.c_int, C.c_int, _s]),
-    'occ4d_pt_cross_attn16p_stream_floats': (C.c_int64, []),
-    'occ4d_pt_cross_attn16p_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, C.c_int64, _i, _f, C.c_int64, _f,
-                                             C.c_int64, _f, _f, _f, _f, C.c_int64, C.c_int, C.c_int, C.c_int,
-                                             C.c_int, C.c_float, C.c_int, _s]),
-    'occ4d_pt_cross_attn16p_logits_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, C.c_int64, _i, _f, C.c_int64, _f,
-                                                    C.c_int64, _f, _f, _f, _f, C.c_int64, _f, _f, _f, _f, C.c_int, C.c_int,
-                                                    C.c_int, C.c_int, C.c_float, C.c_int, _s]),
-    'occ4d_pt_cross_attn_bf16x6_logits_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, C.c_int64, _i, _f, C.c_int64, _f,
-                                                        C.c_int64, _f, _f, _f, _f, C.c_int64, _f, _f, _f, _f, C.c_int, C.c_int,
-                                                        C.c_int, C.c_int, C.c_float, _s]),
-    'occ4d_implicit_loss_workspace_floats': (C.c_int64, [C.c_int]),
-    'occ4d_implicit_loss_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                          C.c_float, _f, _f, _f, C.c_int64, _s]),
-    'occ4d_implicit_loss_terms_workspace_floats': (C.c_int64, [C.c_int]),
-    'occ4d_implicit_loss_terms_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                C.c_float, C.c_float, C.c_float, C.c_float, _f, _f, _f, _f, C.c_int64, _s]),
-    'occ4d_resblock_f16x3_packed_floats': (C.c_int64, []),
-    'occ4d_pack_resblock_f16x3_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _s]),
-    'occ4d_resblock_f16x3_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _f, _f, C.c_int, _s]),
-    'occ4d_pt_pair_mlp_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _i, _f, _f, _f, _f, _f, C.c_int, C.c_int,
-                                        C.c_int, C.c_int, C.c_int, _s]),
-    'occ4d_layernorm_f32': (C.c_int, [_f, C.c_int64, _f, _f, C.c_float, C.c_int, _f, C.c_int64, C.c_int, C.c_int,
-                                      _s]),
-    'occ4d_maxpool_gather_f32': (C.c_int, [_f, C.c_int64, _i, C.c_int, C.c_int, C.c_int, _f, C.c_int64, _s]),
-    'occ4d_gather_rows_f32': (C.c_int, [_f, C.c_int64, _i, C.c_int, C.c_int, _f, C.c_int64, _s]),
-    'occ4d_mean_rows_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, _f, _s]),
-    'occ4d_posenc_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, _f, C.c_int64, _s]),
-    'occ4d_interp_weights_f32': (C.c_int, [_f, C.c_int, C.c_int, _f, _s]),
-    'occ4d_interp_add_f32': (C.c_int, [_f, C.c_int64, _f, _f, C.c_int64, _i, _f, C.c_int, C.c_int, C.c_int, _s]),
-    'occ4d_trunk_width': (C.c_int, []),
-    'occ4d_trunk_packed_floats': (C.c_int64, [C.c_int]),
-    'occ4d_resblock_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _f, _f, _f, _f, _f, C.c_int64, _i, _f, C.c_int,
-                                     C.c_int, _s]),
-    'occ4d_rowlin_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _f, C.c_int, C.c_int, _f, C.c_int64, _f, _f,
-                                   C.c_int64, _i, _f, C.c_int, C.c_int, _s]),
-    'occ4d_rowlin_masked_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _f, C.c_int, C.c_int, _f, C.c_int64, _f,
-                                          C.c_int64, C.c_int, _s]),
-    'occ4d_rowlin4_masked_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _f, C.c_int, C.c_int, _f, C.c_int64, _f,
-                                          C.c_int64, C.c_int, _s]),
-    'occ4d_rowlin4_masked_skip_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _f, C.c_int, C.c_int, _f, C.c_int64, _f,
-                                               C.c_int64, C.c_int, _s]),
-    'occ4d_trunk4_packed_floats': (C.c_int64, [C.c_int]),
-    'occ4d_resblock4_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _f, _f, _f, _f, _f, C.c_int64, _i, _f, C.c_int,
-                                      C.c_int, _s]),
-    'occ4d_rowlin4_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _f, C.c_int, C.c_int, _f, C.c_int64, _f, _f,
-                                    C.c_int64, _i, _f, C.c_int, C.c_int, _s]),
-    'occ4d_squash_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int32), _s]),
-    'occ4d_grid_points_f32': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                        C.c_float, C.c_float, _f, _s]),
-    'occ4d_split_count_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_float, _i, _i, _s]),
-    'occ4d_radius_grid_workspace_bytes': (C.c_int64, [C.c_int]),
-    'occ4d_radius_grid_build_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_float, _f, _s]),
-    'occ4d_radius_far_f32': (C.c_int, [_f, C.c_int64, C.c_int, _f, C.c_float, _f, _s]),
-    'occ4d_knn_grid_f32': (C.c_int, [_f, C.c_int64, C.c_int, _f, C.c_int64, C.c_int, C.c_int, C.c_int, _i, _f, _f, _s]),
-    'occ4d_compact_count_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_float, C.c_int, _i, _i, _s]),
-    'occ4d_compact_rows_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, _f, C.c_int64, C.c_float, C.c_int, _i, _f, _f,
-                                         _s]),
-    'occ4d_split_write_f32': (C.c_int, [_f, _f, C.c_int64, C.c_int, C.c_int, C.c_float, _i, C.c_int, C.c_int, _f, _f,
-                                        _s]),
-    # backward pass
-    'occ4d_linear_wgrad_workspace': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
-    'occ4d_linear_wgrad_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, C.c_int, C.c_int, C.c_int, _f, C.c_int, _f,
-                                         C.c_int, _s]),
-    'occ4d_linear_wgrad_bias_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _f, _f,
-                                              C.c_int, _f, C.c_int, _s]),
-    'occ4d_colsum_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, _f, C.c_int, _f, C.c_int, _s]),
-    'occ4d_bn_workspace_doubles': (C.c_int64, [C.c_int, C.c_int]),
-    'occ4d_bn_train_fwd_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, _f, _f, C.c_float, _f, _f, _f, C.c_int64, _f, _s]),
-    'occ4d_bn_train_bwd_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, C.c_int64, C.c_int, C.c_int, _f, _f, _f, C.c_float, _f,
-                                         C.c_int64, _f, _f, _f, _s]),
-    'occ4d_swish_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, _f, C.c_int64, _s]),
-    'occ4d_swish_bwd_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, C.c_int, C.c_int, _f, C.c_int64, _s]),
-    'occ4d_relu_mask_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, C.c_int, C.c_int, _f, C.c_int64, _s]),
-    'occ4d_scatter_add_rows_f32': (C.c_int, [_f, C.c_int64, _i, C.c_int, C.c_int, C.c_float, _f, C.c_int64, _s]),
-    'occ4d_segment_sum_f32': (C.c_int, [_f, C.c_int, C.c_int, C.c_int, _f, C.c_int64, _s]),
-    'occ4d_maxpool_gather_bwd_f32': (C.c_int, [_f, C.c_int64, _i, C.c_int, C.c_int, C.c_int, _f, C.c_int64, _f,
-                                               C.c_int64, _s]),
-    'occ4d_layernorm_bwd_f32': (C.c_int, [_f, C.c_int64, _f, _f, C.c_int64, C.c_float, C.c_int, C.c_int, _f,
-                                          C.c_int64, _f, _f, _s]),
-    'occ4d_pt_softmax_agg_bwd_f32': (C.c_int, [_f, _f, C.c_int64, _f, _i, C.c_int, C.c_int, C.c_int, C.c_float, _f,
-                                               C.c_int64, _f, _f, _f, C.c_int64, _s]),
-    'occ4d_pt_pos_hidden_bwd_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _i, C.c_int, C.c_int, C.c_int, _f, _f,
-                                              _f, _f, _s]),
-    'occ4d_interp_bwd_f32': (C.c_int, [_f, C.c_int64, _i, _f, C.c_int, C.c_int, C.c_int, _f, C.c_int64, _s]),
-    'occ4d_segment_gather_sum_f32': (C.c_int, [_f, C.c_int64, _i, _i, _f, C.c_int, C.c_int, C.c_int, C.c_float, _f,
-                                               C.c_int64, _s]),
-    'occ4d_segments_workspace_ints': (C.c_int64, [C.c_int]),
-    'occ4d_segments_build_i32': (C.c_int, [_i, C.c_int64, C.c_int, _i, _i, _i, _s]),
-    'occ4d_segment_sum_sorted_f32': (C.c_int, [_f, C.c_int64, _i, _i, C.c_int, C.c_int, C.c_int, C.c_float, _f, C.c_int64,
-                                               _s]),
-    'occ4d_pt_pos_hidden_bwd_det_workspace': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
-    'occ4d_pt_pos_hidden_bwd_det_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _i, C.c_int, C.c_int, C.c_int, _f, _f,
-                                                  _f, _f, _f, _s]),
-    'occ4d_axpby_f32': (C.c_int, [_f, C.c_int64, C.c_float, _f, C.c_int64, C.c_float, C.c_int, C.c_int, _f,
-                                  C.c_int64, _s]),
-    'occ4d_adamw_chunk': (C.c_int, []),
-    'occ4d_adamw_clip_f32': (C.c_int, [_f, _f, _f, _i, _i, _i, C.c_int, _i, _i, C.c_int] + [C.c_float] * 6 + [_f, _s]),
-    'occ4d_adamw_clip_groups_f32': (C.c_int, [_f, _f, _f, _i, _i, _i, C.c_int, _i, _i, C.c_int] + [C.c_float] * 2 + [_f, _s]),
-    'occ4d_broadcast_rows_f32': (C.c_int, [_f, C.c_float, C.c_int, C.c_int, _f, C.c_int64, _s]),
-    # packers + path-level entry points
-    'occ4d_pack_trunk_rows_f32': (C.c_int, [_f, C.c_int64, C.c_int, _f, _s]),
-    'occ4d_pack_trunk_cols_f32': (C.c_int, [_f, C.c_int64, _f, _s]),
-    'occ4d_pack_trunk4_rows_f32': (C.c_int, [_f, C.c_int64, C.c_int, _f, _s]),
-    'occ4d_pack_trunk4_cols_f32': (C.c_int, [_f, C.c_int64, _f, _s]),
-    'occ4d_pack_attn16p_stream_f32': (C.c_int, [_f, _f, _f, _f, _s]),
-    'occ4d_pt_cross_attn_bf16x6_stream_floats': (C.c_int64, []),
-    'occ4d_debug_x6_stamps': (C.c_int, [C.c_void_p, C.c_int]),
-    'occ4d_rowlin_bf16x6_packed_floats': (C.c_int64, [C.c_int]),
-    'occ4d_pack_rowlin_bf16x6_f32': (C.c_int, [_f, C.c_int64, C.c_int, _f, _s]),
-    'occ4d_rowlin_bf16x6_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _f, C.c_int, C.c_int, _f, C.c_int64, C.c_int, _s]),
-    'occ4d_pt_pair_mlp_bf16x6_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _i, _f, _f, _f, _f, _f, C.c_int, C.c_int, C.c_int,
-                                              C.c_int, _s]),
-    'occ4d_rowlin_bf16x6_masked_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _f, C.c_int, C.c_int, _f, C.c_int64, C.c_int,
-                                                _f, C.c_int64, C.c_int, _s]),
-    'occ4d_pack_attn_bf16x6_stream_f32': (C.c_int, [_f, _f, _f, _f, _s]),
-    'occ4d_pt_cross_attn_bf16x6_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, C.c_int64, _i, _f, C.c_int64, _f, C.c_int64,
-                                                 _f, _f, _f, _f, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _s]),
-    'occ4d_pt_cross_attn_f16x3_stream_floats': (C.c_int64, []),
-    'occ4d_pack_attn_f16x3_stream_f32': (C.c_int, [_f, _f, _f, _f, _s]),
-    'occ4d_pt_cross_attn_f16x3_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, C.c_int64, _i, _f, C.c_int64, _f, C.c_int64,
-                                                _f, _f, _f, _f, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _s]),
-    'occ4d_pt_cross_attn_f16x3_hidden_scale': (C.c_float, []),
-    'occ4d_pt_cross_attn_f16x3_prescaled_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, C.c_int64, _i, _f, C.c_int64, _f,
-                                                          C.c_int64, _f, _f, _f, _f, C.c_int64, C.c_int, C.c_int, C.c_int,
-                                                          C.c_int, C.c_float, _s]),
-    'occ4d_pt_cross_attn_f16w_stream_floats': (C.c_int64, []),
-    'occ4d_pack_attn_f16w_stream_f32': (C.c_int, [_f, _f, _f, _f, _s]),
-    'occ4d_pt_cross_attn_f16w_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, C.c_int64, _i, _f, C.c_int64, _f, C.c_int64,
-                                               _f, _f, _f, _f, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _s]),
-    'occ4d_rowlin_f16x3_packed_floats': (C.c_int64, [C.c_int]),
-    'occ4d_pack_rowlin_f16x3_f32': (C.c_int, [_f, C.c_int64, C.c_int, _f, _s]),
-    'occ4d_rowlin_f16x3_f32': (C.c_int, [_f, C.c_int64, _f, C.c_int64, _f, _f, C.c_int, C.c_int, _f, C.c_int64, C.c_int, _s]),
-    'occ4d_pt_layer_prepared_floats': (C.c_int64, [_LW, C.c_int]),
-    'occ4d_pt_layer_prepare_f32': (C.c_int, [_LW, _f, C.c_int, _s]),
-    'occ4d_pt_layer_scene_floats': (C.c_int64, [_LW, C.c_int]),
-    'occ4d_pt_layer_scene_f32': (C.c_int, [_LW, _f, _f, C.c_int64, C.c_int, _f, C.c_int, _s]),
-    'occ4d_pt_layer_workspace_floats': (C.c_int64, [_LW, C.c_int, C.c_int, C.c_int, C.c_int]),
-    'occ4d_pt_layer_fwd_f32': (C.c_int, [_LW, _f, _f, C.c_int64, _f, C.c_int64, C.c_int, _f, C.c_int64, _f, C.c_int64,
-                                         C.c_int, C.c_int, _i, _f, _f, C.c_int64, _f, C.c_int, _EV, _s]),
-    'occ4d_pt_layer_fwd_logits_f32': (C.c_int, [_LW, _f, _f, C.c_int64, _f, C.c_int64, C.c_int, _f, C.c_int64, _f, C.c_int64,
-                                                C.c_int, C.c_int, _i, _f, _f, C.c_int64, _f, _f, _f, _f, C.c_int, _EV, _s]),
-    'occ4d_down_pool_fwd_f32': (C.c_int, [_f, C.c_int64, C.c_int, C.c_int, _f, _f, C.c_int, C.c_int, _f, _f, _f, _f,
-                                          C.c_float, _i, C.c_int, C.c_int, _f, C.c_int64, _f, _s]),
-    'occ4d_decoder_prepared_floats': (C.c_int64, [_DW, C.c_int]),
-    'occ4d_decoder_prepare_f32': (C.c_int, [_DW, _f, C.c_int, _s]),
-    'occ4d_decoder_scene_floats': (C.c_int64, [_DW, C.c_int]),
-    'occ4d_decoder_prepare_scene_f32': (C.c_int, [_DW, _f, _f, C.c_int64, _f, C.c_int64, _f, C.c_int, _f, C.c_int, _s]),
-    'occ4d_decoder_query_workspace_floats': (C.c_int64, [_DW, C.c_int, C.c_int, C.c_int]),
-    'occ4d_decoder_query_fwd_f32': (C.c_int, [_DW, _f, _f, C.c_int, _f, C.c_int64, C.c_int, _i, _i, _f, C.c_int64, _f,
-                                              C.c_int64, _f, C.c_int, _EV, _s]),
-    'occ4d_knn_dists_f32': (C.c_int, [_f, C.c_int64, C.c_int, _f, C.c_int64, C.c_int, _i, C.c_int, C.c_int, _f, _s]),
-}
+SIGNATURES = parse_prototypes(_HEADER, {'occ4d_linear_args': LinearArgs, 'occ4d_pt_layer_weights': PtLayerWeights,
+                                        'occ4d_launch_events': LaunchEvents, 'occ4d_decoder_weights': DecoderWeights})
 
 _lib = None
 _twin = False            # True only after an explicit load_cpu_twin(): host pointers, no streams (cpu_twin.py)
-
-
-class NativeLibraryError(RuntimeError):
-    pass
 
 
 def is_twin():
     return _twin
 
 
-def _missing(name):
+def bind(handle, missing=None):
+    """Sets restype / argtypes of every symbol of SIGNATURES on a loaded library and returns it.  A symbol the library does
+    not export is a stale library (NativeLibraryError) unless `missing` is given: then missing(name) stands in for it."""
+    for name, (res, args) in SIGNATURES.items():
+        try:
+            fn = getattr(handle, name)
+        except AttributeError:
+            if missing is None:
+                raise NativeLibraryError('libocc4d.so is stale: symbol %s missing; rebuild it' % name)
+            setattr(handle, name, missing(name))
+            continue
+        fn.restype = res
+        fn.argtypes = args
+    return handle
+
+
+def _not_in_twin(name):
     def stub(*_a, **_k):
         raise NotImplementedError('%s is not part of the CPU twin (libocc4d_cpu.so holds the inference path only)' % name)
     return stub
 
 
-class _TwinHandle:
-    """The twin's exports with the argument types of SIGNATURES; an entry point the twin does not have raises
-    NotImplementedError when CALLED (the HIP library, in contrast, must export every symbol of the header)."""
-
-    def __init__(self, handle):
-        for name, (res, args) in SIGNATURES.items():
-            try:
-                fn = getattr(handle, name)
-            except AttributeError:
-                setattr(self, name, _missing(name))
-                continue
-            fn.restype = res
-            fn.argtypes = args
-            setattr(self, name, fn)
-
-
 def load_cpu_twin(path):
     """Replaces the process's library handle by the g++ twin at `path`.  Only cpu_twin.enable() calls this; nothing in
-    the package does so on its own (no fallback: without this call a missing libocc4d.so raises NativeLibraryError)."""
+    the package does so on its own (no fallback: without this call a missing libocc4d.so raises NativeLibraryError).
+    An entry point the twin does not have raises NotImplementedError when CALLED (the HIP library, in contrast, must
+    export every symbol of the header)."""
     global _lib, _twin
-    handle = C.CDLL(path)
-    twin = _TwinHandle(handle)
+    twin = bind(C.CDLL(path), missing=_not_in_twin)
     if twin.occ4d_abi_version() != ABI_VERSION or twin.occ4d_is_cpu_twin() != 1:
         raise NativeLibraryError('%s is not the CPU twin of ABI version %d' % (path, ABI_VERSION))
     _lib, _twin = twin, True
@@ -304,14 +190,7 @@ def lib():
         raise NativeLibraryError(
             'libocc4d.so not found at %s -- build it with `python occlusions-4d_amd/build.py` '
             '(or __graft_entry__.build()); this package has no CPU/PyTorch fallback.' % LIB_PATH)
-    handle = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(handle, name)
-        except AttributeError:
-            raise NativeLibraryError('libocc4d.so is stale: symbol %s missing; rebuild it' % name)
-        fn.restype = res
-        fn.argtypes = args
+    handle = bind(C.CDLL(LIB_PATH))
     if handle.occ4d_abi_version() != ABI_VERSION:
         raise NativeLibraryError('libocc4d.so ABI version %d != expected %d; rebuild it'
                                  % (handle.occ4d_abi_version(), ABI_VERSION))

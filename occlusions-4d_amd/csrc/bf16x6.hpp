@@ -1,49 +1,21 @@
-// Shared device helpers of the split-precision (bf16 x 3 pieces, 6 partial products, fp32 accumulate) kernels:
+// Device helpers of the split-precision (bf16 x 3 pieces, 6 partial products, fp32 accumulate) kernels:
 // csrc/crossattn_bf16x6.hip (vector attention) and csrc/trunk_bf16x6.hip (the decoder's 416-input Linear layers).
 //
 //     x = x1 + x2 + x3 exactly   (x1 = x truncated to bf16, x2 = (x - x1) truncated, x3 = x - x1 - x2: 3 x 8 = 24 bits)
 //     a b ~ a1 b1 + a1 b2 + a2 b1 + a2 b2 + a1 b3 + a3 b1          (dropped: a2 b3 + a3 b2 + a3 b3 <= 2^-21 |a b|)
+// Vector types, fragment DMA and lane swaps: csrc/tile.hpp.
 #pragma once
-#include "common.hpp"
+#include "tile.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ unsigned lds_addr_x(const unsigned* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned*)p;
-}
-// one 1 KB fragment, global (L2) -> LDS by DMA (see csrc/crossattn16p.hip: scalar base + lane offset, inline asm so that
-// the compiler's LDS wait bookkeeping does not see it; ordering = dma_wait_x() + the stage barrier)
-__device__ __forceinline__ void dma_frag_x(const unsigned* __restrict__ src_frag, unsigned lds_dst, unsigned lane16) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(lane16), "s"(lds_dst), "s"(src_frag) : "memory");
-}
-__device__ __forceinline__ void dma_wait_x() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 __device__ __forceinline__ f32x4 mm(const u32x4 a, const u32x4 b, const f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
 struct Split { u32x4 h, m, l; };
-
-// gfx950 lane-swap exchanges (16-lane rows r0..r3 of a wave), as in csrc/crossattn16p.hip:
-//   swap16(x, y) -> lo = (x.r0, y.r0, x.r2, y.r2), hi = (x.r1, y.r1, x.r3, y.r3)
-//   swap32(x, y) -> lo = (x.r0, x.r1, y.r0, y.r1), hi = (x.r2, x.r3, y.r2, y.r3)
-struct PairX { float lo, hi; };
-__device__ __forceinline__ PairX swap16x(float x, float y) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-  return PairX{__uint_as_float(r[0]), __uint_as_float(r[1])};
-}
-__device__ __forceinline__ PairX swap32x(float x, float y) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-  return PairX{__uint_as_float(r[0]), __uint_as_float(r[1])};
-}
 
 // two fp32 -> the packed bf16 pairs of their three truncation pieces (even element in the low half); the two
 // subtractions are packed (v_pk_add_f32): on gfx950 every VALU instruction of a wave costs matrix-pipe time

@@ -31,12 +31,10 @@
 // Per-channel softmax over a query's neighbours: 7 live in a lane's registers, the other 7 in
 // lane ^ 32 -> one cross-half exchange per reduction.  The 9th query's four per-row-tile partial
 // softmaxes (max, sum, weighted sum) are merged through LDS after the main loop.
-#include "common.hpp"
+#include "tile.hpp"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HB = 32;        // hidden block (k-tile of GEMM2)
 constexpr int LDW = 36;       // padded LDS row (floats): stride 9 x 16 B -> conflict-free ds_read_b128

@@ -30,11 +30,9 @@
 // (srcC = 0), not by 104 moves; (4) DMA addresses are scalar base + one constant lane offset.
 #include <type_traits>
 
-#include "common.hpp"
+#include "tile.hpp"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PD = 416;                   // channels
 constexpr int PTD = PD / 16;              // 26 channel tiles
@@ -67,51 +65,12 @@ struct Attn16pArgs {
   const float* c2;                        // STORE == 2: pos_mlp[2].bias (the kernel's own GEMM3 starts from 0)
 };
 
-__device__ __forceinline__ unsigned lds_addr_p(const float* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
-}
-
-// One fragment (1 KB), global (L2) -> LDS by DMA: scalar base (wave-uniform fragment address) + this lane's 16 bytes,
-// LDS destination in M0.  No VALU instruction: on gfx950 the fp32 MFMAs and the plain VALU share the SIMD's vector
-// issue (profiles/micro/valu_beside_mfma.hip: every VALU instruction beside a saturated v_mfma_f32_16x16x4_f32 stream
-// costs its ~4 cycles in full), so address arithmetic in the stage loop is paid for in matrix throughput.  Inline asm
-// on purpose (csrc/trunk.hip: with the builtin every fragment wait degrades to lgkmcnt(0)); ordering comes from
-// dma_wait_p() + the stage barrier.
-__device__ __forceinline__ void dma_frag_p(const float* __restrict__ src_frag, unsigned lds_dst, unsigned lane16) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(lane16), "s"(lds_dst), "s"(src_frag) : "memory");
-}
-// this wave's 7 fragments of a stage: fragments wave + 4 i
+// this wave's 7 fragments of a stage: fragments wave + 4 i (dma_frag, csrc/tile.hpp; ordering comes from dma_wait() + the
+// stage barrier)
 __device__ __forceinline__ void dma_stage_p(const float* __restrict__ src, const float* dst, int wave, unsigned lane16) {
 #pragma unroll
   for (int i = 0; i < PSF / 4; ++i)
-    dma_frag_p(src + (wave + 4 * i) * PFRAG, lds_addr_p(dst) + (unsigned)(wave + 4 * i) * (PFRAG * 4), lane16);
-}
-__device__ __forceinline__ void dma_wait_p() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// 8 MFMAs on two accumulators, alternating
-__device__ __forceinline__ void mm_ab_p(const f32x4 a, const f32x4 b0, const f32x4 b1, f32x4& c0, f32x4& c1) {
-  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b0.x, c0, 0, 0, 0);
-  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b1.x, c1, 0, 0, 0);
-  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b0.y, c0, 0, 0, 0);
-  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b1.y, c1, 0, 0, 0);
-  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b0.z, c0, 0, 0, 0);
-  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b1.z, c1, 0, 0, 0);
-  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b0.w, c0, 0, 0, 0);
-  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b1.w, c1, 0, 0, 0);
-}
-// the same with the operands swapped: the fragments are the A operand, so that the result is TRANSPOSED -- lane (g, c)
-// holds channels 4 g .. 4 g + 3 of pair row c (one float4 per row: the training kernel's stores)
-__device__ __forceinline__ void mm_ba_p(const f32x4 b, const f32x4 a0, const f32x4 a1, f32x4& c0, f32x4& c1) {
-  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b.x, c0, 0, 0, 0);
-  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b.x, c1, 0, 0, 0);
-  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b.y, c0, 0, 0, 0);
-  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b.y, c1, 0, 0, 0);
-  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, b.z, c0, 0, 0, 0);
-  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, b.z, c1, 0, 0, 0);
-  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, b.w, c0, 0, 0, 0);
-  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b.w, c1, 0, 0, 0);
+    dma_frag(src + (wave + 4 * i) * PFRAG, lds_addr(dst) + (unsigned)(wave + 4 * i) * (PFRAG * 4), lane16);
 }
 // GEMM1 of a stage: K = 32 on ONE accumulator (a second accumulator would cost four VALU adds per stage; the dependent
 // chain's 8 cycles per MFMA are the co-resident wave's)
@@ -124,19 +83,6 @@ __device__ __forceinline__ void mm_g1_p(const f32x4 a0, const f32x4 a1, const f3
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b1.y, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, b1.z, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b1.w, c, 0, 0, 0);
-}
-
-// gfx950 lane-swap exchanges (16-lane rows r0..r3 of a wave):
-//   swap16(x, y) -> lo = (x.r0, y.r0, x.r2, y.r2), hi = (x.r1, y.r1, x.r3, y.r3)
-//   swap32(x, y) -> lo = (x.r0, x.r1, y.r0, y.r1), hi = (x.r2, x.r3, y.r2, y.r3)
-struct Pair { float lo, hi; };
-__device__ __forceinline__ Pair swap16(float x, float y) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-  return Pair{__uint_as_float(r[0]), __uint_as_float(r[1])};
-}
-__device__ __forceinline__ Pair swap32(float x, float y) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-  return Pair{__uint_as_float(r[0]), __uint_as_float(r[1])};
 }
 
 // STORE (training forward): 1 = the logits also go to HBM, row q K + slot, so that backward does not run GEMM2 again
@@ -256,7 +202,7 @@ __global__ __launch_bounds__(256, 2) void cross_attn16p_kernel(const Attn16pArgs
     const bool o_writer = (g & 1) == 0 && qm < a.N;
     float* const sp_lane = s_part + (wave * 3) * PD + c;
     const bool ninth_writer = g3 && (ps == 0 || wave < 3);
-    dma_wait_p();
+    dma_wait();
     __syncthreads();
 #ifdef OCC4D_CA16P_STAMP
     ts[1 + 3 * ps] = __builtin_amdgcn_s_memtime();
@@ -290,14 +236,14 @@ __global__ __launch_bounds__(256, 2) void cross_attn16p_kernel(const Attn16pArgs
 #endif
 #ifndef OCC4D_CA16P_ABL_NODMA
         if (gq >= 2 && gq <= 8)
-          dma_frag_p(nsrc + (wave + 4 * (gq - 2)) * PFRAG, lds_addr_p(nxt) + (unsigned)(wave + 4 * (gq - 2)) * (PFRAG * 4), lane16);
+          dma_frag(nsrc + (wave + 4 * (gq - 2)) * PFRAG, lds_addr(nxt) + (unsigned)(wave + 4 * (gq - 2)) * (PFRAG * 4), lane16);
 #endif
         __builtin_amdgcn_sched_barrier(0);
         if (gq == 0) {
           mm_g1_p(ca, cb, r_lo, r_hi, h);
         } else {
           if (FIRST) acc[2 * (gq - 1)] = acc[2 * (gq - 1) + 1] = f32x4{0.f, 0.f, 0.f, 0.f};   // (folds into srcC = 0)
-          mm_ab_p(h, ca, cb, acc[2 * (gq - 1)], acc[2 * (gq - 1) + 1]);
+          mfma16x2_a(h, ca, cb, acc[2 * (gq - 1)], acc[2 * (gq - 1) + 1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (gq == 0) {
@@ -312,18 +258,18 @@ __global__ __launch_bounds__(256, 2) void cross_attn16p_kernel(const Attn16pArgs
     asm volatile("; OCC4D_MARK loop");
     // two stages per loop trip so that the LDS buffers are compile-time objects; one barrier per stage
     stage(std::true_type{}, 0, buf0, buf1);
-    dma_wait_p();
+    dma_wait();
     __syncthreads();
     stage(std::false_type{}, 1, buf1, buf0);
-    dma_wait_p();
+    dma_wait();
     __syncthreads();
 #pragma clang loop unroll(disable)
     for (int s = 2; s < PHS; s += 2) {
       stage(std::false_type{}, s, buf0, buf1);
-      dma_wait_p();
+      dma_wait();
       __syncthreads();
       stage(std::false_type{}, s + 1, buf1, buf0);
-      dma_wait_p();
+      dma_wait();
       __syncthreads();
     }
 #ifdef OCC4D_CA16P_STAMP
@@ -366,7 +312,7 @@ __global__ __launch_bounds__(256, 2) void cross_attn16p_kernel(const Attn16pArgs
           }
           __builtin_amdgcn_sched_barrier(0);
 #ifndef OCC4D_CA16P_ABL_NOG3
-          mm_ab_p(kh ? r_hi : r_lo, ca, cb, pe[2 * p], pe[2 * p + 1]);
+          mfma16x2_a(kh ? r_hi : r_lo, ca, cb, pe[2 * p], pe[2 * p + 1]);
 #endif
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -472,7 +418,7 @@ __global__ __launch_bounds__(256, 2) void cross_attn16p_kernel(const Attn16pArgs
     chunk(I4{}, I4{}, I0{}, buf0);
     chunk(std::integral_constant<int, 8>{}, I4{}, I0{}, buf0);
     chunk(std::integral_constant<int, 12>{}, I2{}, I0{}, buf0);
-    dma_wait_p();
+    dma_wait();
     __syncthreads();
     // pass B's first hidden stage lands in buf0 under the second half of pass A's epilogue
     if (ps == 0) dma_stage_p(a.wstream, buf0, wave, lane16);
@@ -574,7 +520,7 @@ __global__ __launch_bounds__(256, 2) void pair_mlp_kernel(const PairMlpArgs a) {
     const unsigned l_off = ((unsigned)p * (unsigned)PD + 4u * g) * 4u;
     f32x4 ia = slice(a.aq, aq_off);
     f32x4 ik = slice(a.kt, kt_off);
-    dma_wait_p();
+    dma_wait();
     __syncthreads();
 
     auto stage = [&](auto firstc, const int s, const float* __restrict__ cur, const float* nxt) {
@@ -596,13 +542,13 @@ __global__ __launch_bounds__(256, 2) void pair_mlp_kernel(const PairMlpArgs a) {
         if (gq == 0) ia = slice(a.aq + 16 * sn, aq_off);
         if (gq == 1) ik = slice(a.kt + 16 * sn, kt_off);
         if (gq >= 2 && gq <= 8)
-          dma_frag_p(nsrc + (wave + 4 * (gq - 2)) * PFRAG, lds_addr_p(nxt) + (unsigned)(wave + 4 * (gq - 2)) * (PFRAG * 4), lane16);
+          dma_frag(nsrc + (wave + 4 * (gq - 2)) * PFRAG, lds_addr(nxt) + (unsigned)(wave + 4 * (gq - 2)) * (PFRAG * 4), lane16);
         __builtin_amdgcn_sched_barrier(0);
         if (gq == 0) {
           mm_g1_p(ca, cb, r_lo, r_hi, h);
         } else {
           if (FIRST) acc[2 * (gq - 1)] = acc[2 * (gq - 1) + 1] = f32x4{0.f, 0.f, 0.f, 0.f};
-          mm_ba_p(h, ca, cb, acc[2 * (gq - 1)], acc[2 * (gq - 1) + 1]);
+          mfma16x2_b(ca, cb, h, acc[2 * (gq - 1)], acc[2 * (gq - 1) + 1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (gq == 0) {
@@ -616,23 +562,23 @@ __global__ __launch_bounds__(256, 2) void pair_mlp_kernel(const PairMlpArgs a) {
     };
     asm volatile("; OCC4D_MARK loop");
     stage(std::true_type{}, 0, buf0, buf1);
-    dma_wait_p();
+    dma_wait();
     __syncthreads();
     stage(std::false_type{}, 1, buf1, buf0);
-    dma_wait_p();
+    dma_wait();
     __syncthreads();
 #pragma clang loop unroll(disable)
     for (int s = 2; s < PHS; s += 2) {
       stage(std::false_type{}, s, buf0, buf1);
-      dma_wait_p();
+      dma_wait();
       __syncthreads();
       stage(std::false_type{}, s + 1, buf1, buf0);
-      dma_wait_p();
+      dma_wait();
       __syncthreads();
     }
     asm volatile("; OCC4D_MARK epilogue");
     // ---- epilogue: the logits, then pe = P2 r + c2 on the two P2 stages (buf0 holds the first, the second lands in
-    // buf1 under it).  GEMM2 / GEMM3 ran with the fragments as the A operand (mm_ba_p): lane (g, c) holds channels
+    // buf1 under it).  GEMM2 / GEMM3 ran with the fragments as the A operand (mfma16x2_b): lane (g, c) holds channels
     // 16 t + 4 g .. + 3 of pair row c in every accumulator tile
     dma_stage_p(a.wstream + (int64_t)(PHS + 1) * PSTAGE, buf1, wave, lane16);
 #pragma unroll
@@ -650,10 +596,10 @@ __global__ __launch_bounds__(256, 2) void pair_mlp_kernel(const PairMlpArgs a) {
         const int t = T0 + 2 * pr;
         f32x4 e0 = *reinterpret_cast<const f32x4*>(a.c2 + 16 * t + 4 * g);
         f32x4 e1 = *reinterpret_cast<const f32x4*>(a.c2 + 16 * (t + 1) + 4 * g);
-        mm_ba_p(r_lo, *reinterpret_cast<const f32x4*>(fp + (4 * pr) * PFRAG),
-                *reinterpret_cast<const f32x4*>(fp + (4 * pr + 2) * PFRAG), e0, e1);
-        mm_ba_p(r_hi, *reinterpret_cast<const f32x4*>(fp + (4 * pr + 1) * PFRAG),
-                *reinterpret_cast<const f32x4*>(fp + (4 * pr + 3) * PFRAG), e0, e1);
+        mfma16x2_b(*reinterpret_cast<const f32x4*>(fp + (4 * pr) * PFRAG),
+                   *reinterpret_cast<const f32x4*>(fp + (4 * pr + 2) * PFRAG), r_lo, e0, e1);
+        mfma16x2_b(*reinterpret_cast<const f32x4*>(fp + (4 * pr + 1) * PFRAG),
+                   *reinterpret_cast<const f32x4*>(fp + (4 * pr + 3) * PFRAG), r_hi, e0, e1);
 #ifdef OCC4D_PM_ABL_NOPE
         if (e0.x == 123.456f)
 #endif
@@ -664,7 +610,7 @@ __global__ __launch_bounds__(256, 2) void pair_mlp_kernel(const PairMlpArgs a) {
       }
     };
     pe_tiles(std::integral_constant<int, 0>{}, std::integral_constant<int, PTA / 2>{}, buf0);
-    dma_wait_p();
+    dma_wait();
     __syncthreads();
     if (ps == 0) dma_stage_p(a.wstream, buf0, wave, lane16);   // pass B's first hidden stage
     pe_tiles(std::integral_constant<int, PTA>{}, std::integral_constant<int, PTB / 2>{}, buf1);
@@ -729,8 +675,8 @@ __global__ __launch_bounds__(256) void pair_hidden_kernel(const PairMlpArgs a) {
     const bool second = t >= PTA;
     const float* fp = ws + (int64_t)(PHS + (second ? 1 : 0)) * PSTAGE + (int64_t)(4 * (second ? pr - PTA / 2 : pr)) * PFRAG;
     f32x4 e0 = ld(a.c2 + 16 * t + 4 * g), e1 = ld(a.c2 + 16 * (t + 1) + 4 * g);
-    mm_ba_p(r_lo, ld(fp), ld(fp + 2 * PFRAG), e0, e1);
-    mm_ba_p(r_hi, ld(fp + PFRAG), ld(fp + 3 * PFRAG), e0, e1);
+    mfma16x2_b(ld(fp), ld(fp + 2 * PFRAG), r_lo, e0, e1);
+    mfma16x2_b(ld(fp + PFRAG), ld(fp + 3 * PFRAG), r_hi, e0, e1);
     *reinterpret_cast<f32x4*>(po + 16 * t) = e0;
     *reinterpret_cast<f32x4*>(po + 16 * (t + 1)) = e1;
   }

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(512, 2) void cross_attn_split_kernel(const AttnX6Ar
   // this wave's i-th fragment of a stage (PARTS per wave and stage; the tail repeats the last fragment: same bytes, same place)
   auto dma_part = [&](int stage_no, const unsigned* dst, int i) {
     const int f = min(wave + XWAVES * i, XSF - 1);                                  // wave-uniform
-    dma_frag_x(wst + (int64_t)stage_no * XSTAGE + f * XFW, lds_addr_x(dst) + (unsigned)f * (XFW * 4), lane16);
+    dma_frag(wst + (int64_t)stage_no * XSTAGE + f * XFW, lds_addr(dst) + (unsigned)f * (XFW * 4), lane16);
   };
 #pragma unroll
   for (int i = 0; i < PARTS; ++i) dma_part(0, buf0, i);
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(512, 2) void cross_attn_split_kernel(const AttnX6Ar
 #pragma unroll
     for (int t = 0; t < XT; ++t) acc[rt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
   ts[1] = __builtin_amdgcn_s_memtime();
-  dma_wait_x();
+  dma_wait();
   __builtin_amdgcn_s_barrier();                       // barrier 0: stage 0 is complete
   ts[2] = __builtin_amdgcn_s_memtime();
   if (grp_b) {                                        // (A issues its part of stage 1 inside stage 0, tile by tile)
@@ -286,12 +286,12 @@ __global__ __launch_bounds__(512, 2) void cross_attn_split_kernel(const AttnX6Ar
 #endif
       S::mm_x2(hs[0], hs[1], bc, acc[0][t], acc[1][t]);
       if (t == 6 && grp_b) {
-        dma_wait_x();
+        dma_wait();
         __builtin_amdgcn_s_barrier();
       }
     }
     if (!grp_b) {
-      dma_wait_x();
+      dma_wait();
       __builtin_amdgcn_s_barrier();
     }
   };
@@ -383,11 +383,11 @@ __global__ __launch_bounds__(512, 2) void cross_attn_split_kernel(const AttnX6Ar
       }
       float mx[2];
       {
-        const PairX p1 = swap16x(lm[0], lm[1]);
+        const Pair p1 = swap16(lm[0], lm[1]);
         const float m1 = fmaxf(p1.lo, p1.hi);            // rows: (A01, B01, A23, B23)
-        const PairX p2 = swap32x(m1, m1);
+        const Pair p2 = swap32(m1, m1);
         const float m2 = fmaxf(p2.lo, p2.hi);            // rows: (A, B, A, B)
-        const PairX p3 = swap16x(m2, m2);
+        const Pair p3 = swap16(m2, m2);
         mx[0] = p3.lo;
         mx[1] = p3.hi;
       }
@@ -408,13 +408,13 @@ __global__ __launch_bounds__(512, 2) void cross_attn_split_kernel(const AttnX6Ar
         num[x] = fmaf(own23, n23[x], fmaf(e1, val[x][1], e0 * val[x][0]));
       }
       {
-        const PairX a1 = swap16x(den[0], num[0]);
+        const Pair a1 = swap16(den[0], num[0]);
         const float xa = a1.lo + a1.hi;                  // rows: (dA01, nA01, dA23, nA23)
-        const PairX b1 = swap16x(den[1], num[1]);
+        const Pair b1 = swap16(den[1], num[1]);
         const float xb = b1.lo + b1.hi;
-        const PairX z1 = swap32x(xa, xb);
+        const Pair z1 = swap32(xa, xb);
         const float z = z1.lo + z1.hi;                   // rows: (dA, nA, dB, nB)
-        const PairX z2 = swap16x(z, z);                  // lo = (dA, dA, dB, dB), hi = (nA, nA, nB, nB)
+        const Pair z2 = swap16(z, z);                  // lo = (dA, dA, dB, dB), hi = (nA, nA, nB, nB)
         const float o = z2.hi * __builtin_amdgcn_rcpf(z2.lo);
         if (o_lane && !(single && g >= 2)) orow[16 * tA] = o;
       }

@@ -34,7 +34,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int WD = 416;                   // channels
 constexpr int WHID = 2 * WD;              // hidden units of attn_mlp
@@ -90,7 +89,7 @@ __global__ __launch_bounds__(256, 1) void cross_attn_f16w_kernel(const AttnWArgs
 
   auto dma_part = [&](int stage_no, const unsigned* dst, int i) {               // this wave's i-th fragment of a stage
     const int f = wave + WWAVES * i;                                              // (wave-uniform; 4 x 14 = 56)
-    dma_frag_x(a.wstream + (int64_t)stage_no * WSTAGE + f * WFW, lds_addr_x(dst) + (unsigned)f * (WFW * 4), lane16);
+    dma_frag(a.wstream + (int64_t)stage_no * WSTAGE + f * WFW, lds_addr(dst) + (unsigned)f * (WFW * 4), lane16);
   };
 #pragma unroll
   for (int i = 0; i < WPARTS; ++i) dma_part(0, ring[0], i);
@@ -185,7 +184,7 @@ __global__ __launch_bounds__(256, 1) void cross_attn_f16w_kernel(const AttnWArgs
     h0 = mm32(ah, rs[0].hi, h0); h1 = mm32(bh, rs[1].hi, h1);
     finish_gemm1(h0, h1);
   }
-  dma_wait_x();
+  dma_wait();
   __builtin_amdgcn_s_barrier();                       // stage 0 is complete
 
   // The init slices are fetched by inline asm and waited for by hand: the compiler does not see the DMA instructions (inline asm
@@ -275,7 +274,7 @@ __global__ __launch_bounds__(256, 1) void cross_attn_f16w_kernel(const AttnWArgs
 #endif
       __builtin_amdgcn_sched_barrier(0);               // (a step's reads stay one step ahead: no hoisting of all 56 fragments)
     }
-    dma_wait_x();
+    dma_wait();
     __builtin_amdgcn_s_barrier();
   };
 #pragma clang loop unroll(disable)
@@ -333,9 +332,9 @@ __global__ __launch_bounds__(256, 1) void cross_attn_f16w_kernel(const AttnWArgs
       mx = (!isa[r] && !isb[r]) ? fmaxf(mx, am[r]) : mx;
     }
     {                                                  // both queries' maxima in every lane
-      const PairX p1 = swap32x(ma, mb);                // lo = (ma.lower, mb.lower), hi = (ma.upper, mb.upper)
+      const Pair p1 = swap32(ma, mb);                // lo = (ma.lower, mb.lower), hi = (ma.upper, mb.upper)
       const float m1 = fmaxf(p1.lo, p1.hi);            // lower lanes: max A, upper lanes: max B
-      const PairX p2 = swap32x(m1, m1);
+      const Pair p2 = swap32(m1, m1);
       ma = p2.lo;                                      // (m1.lower everywhere)
       mb = p2.hi;
     }
@@ -351,9 +350,9 @@ __global__ __launch_bounds__(256, 1) void cross_attn_f16w_kernel(const AttnWArgs
       else { dx += e; nx = fmaf(e, val[r], nx); }
     }
     {
-      const PairX d1 = swap32x(da, db);
+      const Pair d1 = swap32(da, db);
       const float den = d1.lo + d1.hi;                 // lower lanes: A, upper lanes: B
-      const PairX n1 = swap32x(na, nb);
+      const Pair n1 = swap32(na, nb);
       const float num = n1.lo + n1.hi;
       if (o_ok) orow[32 * t] = num * __builtin_amdgcn_rcpf(den);
     }

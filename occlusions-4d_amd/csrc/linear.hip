@@ -16,12 +16,10 @@
 // step i consumes element i of both, i.e. the k order inside a group is
 // (0,4),(1,5),(2,6),(3,7).  A and B use the same map, so the product is exact; only
 // the fp32 summation order differs from a serial dot product.
-#include "common.hpp"
+#include "tile.hpp"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128;
 #ifndef OCC4D_LINEAR_BK

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(512, 2) void pair_mlp_bf16x6_kernel(const PairX6Arg
 
   auto dma_part = [&](int stage_no, const unsigned* dst, int i) {
     const int f = min(wave + ZWAVES * i, ZSF - 1);                                  // wave-uniform; the tail repeats 44
-    dma_frag_x(wst + (int64_t)stage_no * ZSTAGE + f * ZFW, lds_addr_x(dst) + (unsigned)f * (ZFW * 4), lane16);
+    dma_frag(wst + (int64_t)stage_no * ZSTAGE + f * ZFW, lds_addr(dst) + (unsigned)f * (ZFW * 4), lane16);
   };
 #pragma unroll
   for (int i = 0; i < 6; ++i) dma_part(0, buf0, i);
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(512, 2) void pair_mlp_bf16x6_kernel(const PairX6Arg
   for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
     for (int t = 0; t < ZT; ++t) acc[rt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  dma_wait_x();
+  dma_wait();
   __builtin_amdgcn_s_barrier();                       // barrier 0: stage 0 is complete
   if (grp_b) {
 #pragma unroll
@@ -158,12 +158,12 @@ __global__ __launch_bounds__(512, 2) void pair_mlp_bf16x6_kernel(const PairX6Arg
       }
       mm6x2_b(ch, cm, cl, hs[0], hs[1], acc[0][t], acc[1][t]);
       if (t == 6 && grp_b) {
-        dma_wait_x();
+        dma_wait();
         __builtin_amdgcn_s_barrier();
       }
     }
     if (!grp_b) {
-      dma_wait_x();
+      dma_wait();
       __builtin_amdgcn_s_barrier();
     }
   };

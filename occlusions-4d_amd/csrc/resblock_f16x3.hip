@@ -74,7 +74,7 @@ __global__ __launch_bounds__(512, 2) void resblock_f16x3_kernel(const ResblockX3
 #pragma unroll
     for (int i = 0; i < RPARTS; ++i) {
       const int f = min(wave + RWAVES * i, RSF - 1);
-      dma_frag_x(a.wstream + (int64_t)stage_no * RSTAGE + f * RFW, lds_addr_x(dst) + (unsigned)f * (RFW * 4), lane16);
+      dma_frag(a.wstream + (int64_t)stage_no * RSTAGE + f * RFW, lds_addr(dst) + (unsigned)f * (RFW * 4), lane16);
     }
   };
   dma_stage(0, buf0);
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(512, 2) void resblock_f16x3_kernel(const ResblockX3
   f32x4 h[RT];
 #pragma unroll
   for (int t = 0; t < RT; ++t) h[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  dma_wait_x();
+  dma_wait();
   __builtin_amdgcn_s_barrier();
   auto stage1 = [&](const int ks, const unsigned* __restrict__ cur, const unsigned* nxt) {
     dma_stage(ks + 1, nxt);                                           // (stage 13 = layer 2's first: the stream goes on)
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(512, 2) void resblock_f16x3_kernel(const ResblockX3
 #endif
       mm3_t2(w0, w1, xs, h[2 * tp], h[2 * tp + 1]);
     }
-    dma_wait_x();
+    dma_wait();
 #ifndef OCC4D_RB_ABL_NOBAR
     __builtin_amdgcn_s_barrier();
 #endif
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(512, 2) void resblock_f16x3_kernel(const ResblockX3
         const u32x4 wl[2] = {wn[0][0], wn[0][1]};                     // (tile 12: loaded by the last prefetch above)
         acc[RT / 2 - 1] = mm3_t(wl, hs[T], acc[RT / 2 - 1]);
       }
-      dma_wait_x();
+      dma_wait();
 #ifndef OCC4D_RB_ABL_NOBAR
       __builtin_amdgcn_s_barrier();
 #endif

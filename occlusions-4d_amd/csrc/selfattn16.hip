@@ -22,11 +22,10 @@
 //               pairs = the 16 lanes of a DPP row (quad_perm / row_half_mirror / row_mirror butterflies: no LDS), one
 //               float4 store per 4 channels.  attn_mlp[2].bias is not added: constant over the neighbour axis of the
 //               softmax, it cancels.
-#include "common.hpp"
+#include "tile.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct SelfAttnArgs {
   const float* aq; int64_t ld_aq;        // (n, 2d)  (W1 Wq) x + merged bias

@@ -22,11 +22,9 @@
 // (64 lanes x 16 B, lane-linear: conflict-free ds_read_b128, contiguous global_load_lds_dwordx4), two
 // stage buffers of 52 KB: while a stage's MFMAs read one buffer the DMA fills the other; one
 // s_waitcnt vmcnt(0) + barrier per stage ("my part of the next stage has landed" + "everybody's has").
-#include "common.hpp"
+#include "tile.hpp"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TH = 416;                      // trunk width the kernels are built for
 constexpr int TKG = TH / 16;                 // 26 channel groups of 16
@@ -51,64 +49,20 @@ struct TrunkArgs {
   const float* mask; int64_t ldm;            // rowlin: output rows zeroed where mask <= 0 (ReLU mask of a data gradient), or null
 };
 
-// LDS byte address of a __shared__ object (wave-uniform, for M0)
-__device__ __forceinline__ unsigned lds_addr(const float* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
-}
-
-// One stage = 52 fragments of 1 KB, global (L2) -> LDS by DMA; wave w moves fragments w, w + 8, ...: one
-// global_load_lds_dwordx4 per fragment (LDS destination = M0 base + lane * 16, source address per lane).
-// Issued through inline asm ON PURPOSE: with the __builtin the compiler, knowing that an asynchronous LDS write is
-// in flight, degrades every s_waitcnt of the fragment ds_reads to lgkmcnt(0) -- each group of MFMAs then waits
-// for the reads issued just before it (a full LDS round trip per 8 MFMAs; measured: a wave running alone kept the
-// matrix pipe 65 % busy).  The asm is invisible to that bookkeeping; the stage protocol supplies the ordering:
-// dma_wait() (s_waitcnt vmcnt(0)) + barrier before anybody reads the buffer, barrier before it is overwritten.
-// (round 3: scalar fragment address + one constant lane offset -- no VALU address arithmetic: on gfx950 the fp32 MFMAs
-// and the plain VALU share the SIMD's vector issue, profiles/micro/valu_beside_mfma.hip)
-__device__ __forceinline__ void dma_one(const float* __restrict__ src_frag, unsigned lds_dst, int lane) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"((unsigned)lane * 16u), "s"(lds_dst), "s"(src_frag) : "memory");
-}
+// One stage = 52 fragments of 1 KB, global (L2) -> LDS by DMA (dma_frag, csrc/tile.hpp); wave w moves fragments w,
+// w + 8, ...  Ordering: dma_wait() + barrier before anybody reads the buffer, barrier before it is overwritten.
 __device__ __forceinline__ void dma_stage(const float* __restrict__ src, const float* dst, int wave, int lane) {
 #pragma unroll
   for (int i = 0; i < 7; ++i) {
     const int c = wave + 8 * i;                       // wave-uniform
-    if (c < STAGE_FRAGS) dma_one(src + c * FRAG_FLOATS, lds_addr(dst) + (unsigned)c * (FRAG_FLOATS * 4), lane);
+    if (c < STAGE_FRAGS) dma_frag(src + c * FRAG_FLOATS, lds_addr(dst) + (unsigned)c * (FRAG_FLOATS * 4), (unsigned)lane * 16u);
   }
 }
 
 // the i-th of this wave's (up to 7) fragments of a stage: fragment wave + 8 i (i = 6 exists for waves 0-3 only)
-__device__ __forceinline__ void dma_frag(const float* __restrict__ src, const float* dst, int wave, int lane, int i) {
+__device__ __forceinline__ void dma_part(const float* __restrict__ src, const float* dst, int wave, int lane, int i) {
   const int c = wave + 8 * i;                         // wave-uniform
-  if (c < STAGE_FRAGS) dma_one(src + c * FRAG_FLOATS, lds_addr(dst) + (unsigned)c * (FRAG_FLOATS * 4), lane);
-}
-
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ f32x4 mfma4(const f32x4 w, const f32x4 v, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, v.x, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, v.y, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, v.z, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, v.w, acc, 0, 0, 0);
-  return acc;
-}
-
-// two accumulators advanced alternately: consecutive MFMAs never depend on each other (40-cycle latency vs 32-cycle issue)
-__device__ __forceinline__ void mfma4x2(const f32x4 wa, const f32x4 wb, const f32x4 v, f32x4& acc_a, f32x4& acc_b) {
-  acc_a = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.x, v.x, acc_a, 0, 0, 0);
-  acc_b = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.x, v.x, acc_b, 0, 0, 0);
-  acc_a = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.y, v.y, acc_a, 0, 0, 0);
-  acc_b = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.y, v.y, acc_b, 0, 0, 0);
-  acc_a = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.z, v.z, acc_a, 0, 0, 0);
-  acc_b = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.z, v.z, acc_b, 0, 0, 0);
-  acc_a = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.w, v.w, acc_a, 0, 0, 0);
-  acc_b = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.w, v.w, acc_b, 0, 0, 0);
-}
-
-__device__ __forceinline__ f32x4 relu4(f32x4 v) {
-  v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-  return v;
+  if (c < STAGE_FRAGS) dma_frag(src + c * FRAG_FLOATS, lds_addr(dst) + (unsigned)c * (FRAG_FLOATS * 4), (unsigned)lane * 16u);
 }
 
 // out[t] += zconst + sum_j zw[row, j] * ztab[zidx[row, j], 16 t + 4 g ..]   (one neighbour at a time: 26 gathers in flight)
@@ -193,7 +147,7 @@ __global__ __launch_bounds__(512, 2) void resblock_kernel(const TrunkArgs a) {
         // the other buffer's DMA, one fragment every third group, between MFMAs: issued back to back right after the
         // barrier, the eight waves' 52 KB queued up in the CU's single vector-memory path and every wave's
         // instruction stream -- MFMAs included -- sat behind its own stalled VMEM issue
-        if (t >= 2 && t <= 20 && (t - 2) % 3 == 0) dma_frag(a.w1p + (int64_t)j * STAGE_FLOATS, bufB, wave, lane, (t - 2) / 3);
+        if (t >= 2 && t <= 20 && (t - 2) % 3 == 0) dma_part(a.w1p + (int64_t)j * STAGE_FLOATS, bufB, wave, lane, (t - 2) / 3);
 #endif
         const f32x4 ca = wa, cb = wb;
         if (t + 1 < TKG) {
@@ -201,7 +155,7 @@ __global__ __launch_bounds__(512, 2) void resblock_kernel(const TrunkArgs a) {
           wb = *reinterpret_cast<const f32x4*>(fa + (TKG + t + 1) * FRAG_FLOATS);
         }
         __builtin_amdgcn_sched_barrier(0);
-        mfma4x2(ca, cb, xr[t], h0, h1);
+        mfma16x2_b(ca, cb, xr[t], h0, h1);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -222,7 +176,7 @@ __global__ __launch_bounds__(512, 2) void resblock_kernel(const TrunkArgs a) {
       for (int q = 0; q < TKG; ++q) {
         const int p = q >> 1, tt = q & 1;
 #ifndef OCC4D_TR_NODMA
-        if (q >= 2 && q <= 20 && (q - 2) % 3 == 0) dma_frag(a.w0p + (int64_t)(j + 1) * STAGE_FLOATS, bufA, wave, lane, (q - 2) / 3);
+        if (q >= 2 && q <= 20 && (q - 2) % 3 == 0) dma_part(a.w0p + (int64_t)(j + 1) * STAGE_FLOATS, bufA, wave, lane, (q - 2) / 3);
 #endif
         const f32x4 ca = wa, cb = wb;
         if (q + 1 < TKG) {
@@ -231,7 +185,7 @@ __global__ __launch_bounds__(512, 2) void resblock_kernel(const TrunkArgs a) {
           wb = *reinterpret_cast<const f32x4*>(fb + (4 * pn + 2 + tn) * FRAG_FLOATS);
         }
         __builtin_amdgcn_sched_barrier(0);
-        mfma4x2(ca, cb, tt ? h1 : h0, yacc[2 * p], yacc[2 * p + 1]);
+        mfma16x2_b(ca, cb, tt ? h1 : h0, yacc[2 * p], yacc[2 * p + 1]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -287,14 +241,14 @@ __device__ __forceinline__ void rowlin_stage(const TrunkArgs& a, int s, const fl
     f32x4 wb = *reinterpret_cast<const f32x4*>(frag + TKG * FRAG_FLOATS);
 #pragma unroll
     for (int t = 0; t < TKG; ++t) {
-      if (t >= 2 && t <= 20 && (t - 2) % 3 == 0) dma_frag(next_src, next_dst, wave, lane, (t - 2) / 3);   // (see resblock_kernel)
+      if (t >= 2 && t <= 20 && (t - 2) % 3 == 0) dma_part(next_src, next_dst, wave, lane, (t - 2) / 3);   // (see resblock_kernel)
       const f32x4 ca = wa, cb = wb;
       if (t + 1 < TKG) {
         wa = *reinterpret_cast<const f32x4*>(frag + (t + 1) * FRAG_FLOATS);
         wb = *reinterpret_cast<const f32x4*>(frag + (TKG + t + 1) * FRAG_FLOATS);
       }
       __builtin_amdgcn_sched_barrier(0);
-      mfma4x2(ca, cb, xr[t], o0, o1);
+      mfma16x2_b(ca, cb, xr[t], o0, o1);
       __builtin_amdgcn_sched_barrier(0);
     }
   }

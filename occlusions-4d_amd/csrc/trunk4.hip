@@ -15,11 +15,9 @@
 // Residual block  y = x + W1 relu(W0 relu(x) + b0) + b1  as a loop over 26 hidden chunks of 16: stage A:
 // h = relu(W0[16 j .., :] relu(x) + b0) (104 MFMAs on two accumulators over the even / odd K groups), stage B:
 // yacc += W1[:, 16 j ..] h (104 MFMAs into the 26 output tiles, initialised with x + b1).
-#include "common.hpp"
+#include "tile.hpp"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int QH = 416;                      // trunk width
 constexpr int QKG = QH / 16;                 // 26 channel groups of 16
@@ -45,44 +43,14 @@ struct Trunk4Args {
   int res_post;                              // rowlin with mask: res is added AFTER the mask (skip gradient of a residual block)
 };
 
-__device__ __forceinline__ unsigned lds_addr_q(const float* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
-}
-// one fragment (1 KB), global (L2) -> LDS by DMA: scalar fragment address + this lane's 16 bytes (no VALU)
-__device__ __forceinline__ void dma_frag_q(const float* __restrict__ src_frag, unsigned lds_dst, unsigned lane16) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(lane16), "s"(lds_dst), "s"(src_frag) : "memory");
-}
 // the i-th of this wave's fragments of a 26-fragment stage: fragment wave + 4 i (i = 6 exists for waves 0, 1 only)
 __device__ __forceinline__ void dma_part_q(const float* __restrict__ src, const float* dst, int wave, unsigned lane16, int i) {
   const int c = wave + 4 * i;
-  if (c < QKG) dma_frag_q(src + c * QFRAG, lds_addr_q(dst) + (unsigned)c * (QFRAG * 4), lane16);
+  if (c < QKG) dma_frag(src + c * QFRAG, lds_addr(dst) + (unsigned)c * (QFRAG * 4), lane16);
 }
 __device__ __forceinline__ void dma_stage_q(const float* __restrict__ src, const float* dst, int wave, unsigned lane16) {
 #pragma unroll
   for (int i = 0; i < 7; ++i) dma_part_q(src, dst, wave, lane16, i);
-}
-__device__ __forceinline__ void dma_wait_q() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// 8 MFMAs: two weight fragments against two activation registers into two accumulators, alternating
-__device__ __forceinline__ void mm_kk(const f32x4 wa, const f32x4 wb, const f32x4 va, const f32x4 vb, f32x4& c0, f32x4& c1) {
-  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.x, va.x, c0, 0, 0, 0);
-  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.x, vb.x, c1, 0, 0, 0);
-  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.y, va.y, c0, 0, 0, 0);
-  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.y, vb.y, c1, 0, 0, 0);
-  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.z, va.z, c0, 0, 0, 0);
-  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.z, vb.z, c1, 0, 0, 0);
-  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa.w, va.w, c0, 0, 0, 0);
-  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb.w, vb.w, c1, 0, 0, 0);
-}
-// 8 MFMAs: two weight fragments against ONE activation register into two accumulators, alternating
-__device__ __forceinline__ void mm_nn(const f32x4 wa, const f32x4 wb, const f32x4 v, f32x4& c0, f32x4& c1) {
-  mm_kk(wa, wb, v, v, c0, c1);
-}
-__device__ __forceinline__ f32x4 relu4q(f32x4 v) {
-  v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-  return v;
 }
 
 // out[t] += zconst + sum_j zw[row, j] * ztab[zidx[row, j], 16 t + 4 g ..]: one neighbour at a time, its 26 gathers in
@@ -133,11 +101,11 @@ __global__ __launch_bounds__(256, 2) void resblock4_kernel(const Trunk4Args a) {
     for (int t = 0; t < QKG; ++t) {
       const f32x4 v = *reinterpret_cast<const f32x4*>(xp + 16 * t);
       const f32x4 b = *reinterpret_cast<const f32x4*>(a.b1 + 16 * t + 4 * g);
-      xr[t] = relu4q(v);
+      xr[t] = relu4(v);
       yacc[t].x = v.x + b.x; yacc[t].y = v.y + b.y; yacc[t].z = v.z + b.z; yacc[t].w = v.w + b.w;
     }
   }
-  dma_wait_q();
+  dma_wait();
   __syncthreads();
   const float* const fa = bufA + lane * 4;
   const float* const fb = bufB + lane * 4;
@@ -175,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void resblock4_kernel(const Trunk4Args a) {
           wb = *reinterpret_cast<const f32x4*>(fa + (2 * q + 3) * QFRAG);
         }
         __builtin_amdgcn_sched_barrier(0);
-        mm_kk(ca, cb, xr[2 * q], xr[2 * q + 1], h0, h1);
+        mfma16x2(ca, cb, xr[2 * q], xr[2 * q + 1], h0, h1);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -184,7 +152,7 @@ __global__ __launch_bounds__(256, 2) void resblock4_kernel(const Trunk4Args a) {
     h.z = fmaxf(h0.z + h1.z, 0.f); h.w = fmaxf(h0.w + h1.w, 0.f);
     STAMP4(0)
 #ifndef OCC4D_TR4_NOBAR
-    dma_wait_q();
+    dma_wait();
     __syncthreads();
 #endif
     STAMP4(1)
@@ -205,13 +173,13 @@ __global__ __launch_bounds__(256, 2) void resblock4_kernel(const Trunk4Args a) {
           wb = *reinterpret_cast<const f32x4*>(fb + (2 * p + 3) * QFRAG);
         }
         __builtin_amdgcn_sched_barrier(0);
-        mm_nn(ca, cb, h, yacc[2 * p], yacc[2 * p + 1]);
+        mfma16x2_b(ca, cb, h, yacc[2 * p], yacc[2 * p + 1]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
     STAMP4(2)
 #ifndef OCC4D_TR4_NOBAR
-    dma_wait_q();
+    dma_wait();
     __syncthreads();
 #endif
     STAMP4(3)
@@ -258,7 +226,7 @@ __device__ __forceinline__ void rowlin4_stage(const Trunk4Args& a, int s, const 
         wb = *reinterpret_cast<const f32x4*>(frag + (2 * q + 3) * QFRAG);
       }
       __builtin_amdgcn_sched_barrier(0);
-      mm_kk(ca, cb, xr[2 * q], xr[2 * q + 1], o0, o1);
+      mfma16x2(ca, cb, xr[2 * q], xr[2 * q + 1], o0, o1);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -306,20 +274,20 @@ __global__ __launch_bounds__(256, 2) void rowlin4_kernel(const Trunk4Args a) {
 #pragma unroll
     for (int t = 0; t < QKG; ++t) {
       const f32x4 v = *reinterpret_cast<const f32x4*>(xp + 16 * t);
-      xr[t] = a.relu_in ? relu4q(v) : v;
+      xr[t] = a.relu_in ? relu4(v) : v;
     }
   }
-  dma_wait_q();
+  dma_wait();
   __syncthreads();
   // the packed stream carries n_stages + 1 stages (the last repeats stage 0): prefetching is branch-free
 #pragma clang loop unroll(disable)
   for (int s = s0; s < s1; s += 2) {
     rowlin4_stage(a, s, bufA + lane * 4, xr, row, rowc, g, a.w0p + (int64_t)(s + 1) * QSTAGE, bufB, wave, lane16);
-    dma_wait_q();
+    dma_wait();
     __syncthreads();
     if (s + 1 < s1)
       rowlin4_stage(a, s + 1, bufB + lane * 4, xr, row, rowc, g, a.w0p + (int64_t)(s + 2) * QSTAGE, bufA, wave, lane16);
-    dma_wait_q();
+    dma_wait();
     __syncthreads();
   }
 }

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(512, 2) void rowlin_split_kernel(const RowlinX6Args
   // this wave's i-th fragment of a stage (PARTS per wave and stage; the tail repeats the last fragment)
   auto dma_part = [&](int stage_no, const unsigned* dst, int i) {
     const int f = min(wave + YWAVES * i, YSF - 1);
-    dma_frag_x(wst + (int64_t)stage_no * YSTAGE + f * YFW, lds_addr_x(dst) + (unsigned)f * (YFW * 4), lane16);
+    dma_frag(wst + (int64_t)stage_no * YSTAGE + f * YFW, lds_addr(dst) + (unsigned)f * (YFW * 4), lane16);
   };
 #pragma unroll
   for (int i = 0; i < PARTS; ++i) dma_part(0, buf0, i);
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(512, 2) void rowlin_split_kernel(const RowlinX6Args
   for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
     for (int t = 0; t < YT; ++t) acc[rt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  dma_wait_x();
+  dma_wait();
   __builtin_amdgcn_s_barrier();                       // barrier 0: stage 0 is complete
   if (grp_b) {
 #pragma unroll
@@ -128,12 +128,12 @@ __global__ __launch_bounds__(512, 2) void rowlin_split_kernel(const RowlinX6Args
       }
       S::mm_x2_b(bc, xs[0], xs[1], acc[0][t], acc[1][t]);           // (weights on the A side: TRANSPOSED tiles)
       if (t == 6 && grp_b) {
-        dma_wait_x();
+        dma_wait();
         __builtin_amdgcn_s_barrier();
       }
     }
     if (!grp_b) {
-      dma_wait_x();
+      dma_wait();
       __builtin_amdgcn_s_barrier();
     }
   };

@@ -24,11 +24,9 @@
 
 #include <type_traits>
 
-#include "common.hpp"
+#include "tile.hpp"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WN = 416;                  // rows of an N chunk
 constexpr int WTA = 13;                  // tile rows (16 n) per wave: 2 wave rows x 13 x 16 = 416
@@ -46,17 +44,6 @@ struct W16Args {
   float* part; float* part_b;
   int relu_x;
 };
-
-__device__ __forceinline__ unsigned lds_addr_w(const float* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
-}
-// 1 KB, global -> LDS: scalar base + per-lane byte offset (precomputed once: no VALU in the stage loop)
-__device__ __forceinline__ void dma_w(const float* __restrict__ base, unsigned voff, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(lds_dst), "s"(base) : "memory");
-}
-__device__ __forceinline__ void dma_wait_w() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // NTB k tiles of 16 per workgroup column: 4 (64 columns) or 2 (the 32-wide remainder column)
 template <int NTB, bool RELU, bool BIAS>
@@ -117,9 +104,9 @@ __global__ __launch_bounds__(256, 2) void wgrad16_kernel(const W16Args a) {
   const unsigned w1k = (unsigned)wave * 1024u;
   // slot `slot` of the stage whose first rows are at (gsrc, xsrc), into the buffers (gdst, xdst)
   auto dma_slot = [&](int slot, const float* gsrc, const float* xsrc, float* gdst, float* xdst) __attribute__((always_inline)) {
-    if (slot < GSL) dma_w(gsrc, voff[slot], lds_addr_w(gdst) + w1k + (unsigned)slot * 4096u);
-    else if (slot == GSL) dma_w(xsrc, voff[GSL], lds_addr_w(xdst) + w1k);
-    else if (extra) dma_w(gsrc, voff[GSL + 1], lds_addr_w(gdst) + 24u * 1024u + w1k);
+    if (slot < GSL) dma_frag(gsrc, lds_addr(gdst) + w1k + (unsigned)slot * 4096u, voff[slot]);
+    else if (slot == GSL) dma_frag(xsrc, lds_addr(xdst) + w1k, voff[GSL]);
+    else if (extra) dma_frag(gsrc, lds_addr(gdst) + 24u * 1024u + w1k, voff[GSL + 1]);
   };
 
   f32x4 acc[WTA][WTB];
@@ -133,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void wgrad16_kernel(const W16Args a) {
 
 #pragma unroll
   for (int sl = 0; sl < GSL + 2; ++sl) dma_slot(sl, gbase, xbase, gs0, xs0);
-  dma_wait_w();
+  dma_wait();
   __syncthreads();
 
   // one stage = 4 MFMA steps of 4 rows of M: per step 13 A dwords (g, this wave's tile rows) + 2 B dwords (x) from
@@ -189,12 +176,12 @@ __global__ __launch_bounds__(256, 2) void wgrad16_kernel(const W16Args a) {
     for (int st = 0; st < n_stage; st += 2) {
       if (st + 1 < n_stage) { gnext += gstep; xnext += xstep; }
       stage(with_bias, gs0, xs0, gnext, xnext, gs1, xs1);
-      dma_wait_w();
+      dma_wait();
       __syncthreads();
       if (st + 1 >= n_stage) break;
       if (st + 2 < n_stage) { gnext += gstep; xnext += xstep; }
       stage(with_bias, gs1, xs1, gnext, xnext, gs0, xs0);
-      dma_wait_w();
+      dma_wait();
       __syncthreads();
     }
   };

@@ -493,8 +493,11 @@ def resblock_f16x3(x, w0, b0, w1, b1, out=None, packed=None):
     return out
 
 
-def pt_cross_attn(aq, qpos, apos, idx, kt, vt, P1, c1, wp, w2, b2, p2, c2, out=None):
-    """Fused vector attention (occ4d_pt_cross_attn_f32): agg (n,d)."""
+def _attn_operands(aq, qpos, apos, idx, kt, vt, out):
+    """What the fused attention wrappers do alike: aq / kt as aligned rows, idx (n, k) int32 contiguous, the shape checks, the
+    output rows, the fp32 sqrt(d) divisor and the launch's FLOPs (useful, unpadded): per pair Wp (32 x 2d) + W2 (2d x d) +
+    P2 (32 x d).  -> (the entry points' eleven leading arguments aq .. ld_vt, the tensors behind them -- the caller keeps them
+    alive until the launch --, out, its row stride, n, m, k, d, divisor, flops)."""
     aq, ld_aq = _aligned_rows(_dev(aq, name='aq'), 'aq')
     kt, ld_kt = _aligned_rows(_dev(kt, name='kt'), 'kt')
     vt, ld_vt = _rows(_dev(vt, name='vt'), 'vt')
@@ -504,21 +507,25 @@ def pt_cross_attn(aq, qpos, apos, idx, kt, vt, P1, c1, wp, w2, b2, p2, c2, out=N
     n, k = idx.shape
     d = vt.shape[1]
     assert idx.is_contiguous() and aq.shape == (n, 2 * d) and kt.shape[1] == 2 * d and qp.shape[0] == n
-    ws = [_dev(t).contiguous() for t in (P1, c1, wp, w2, b2, p2, c2)]
-    assert ws[2].shape == (2 * d, 32) and ws[3].shape == (d, 2 * d) and ws[5].shape == (d, 32)
     if out is None:
         out = torch.empty((n, d), dtype=torch.float32, device=aq.device)
     o, ldo = _rows(out, 'out')
     assert o is out and o.shape == (n, d)
     divisor = float(torch.tensor(math.sqrt(d), dtype=torch.float32))
-    # FLOPs this launch executes (useful, unpadded): per pair Wp (32 x 2d) + W2 (2d x d) + P2 (32 x d)
     flops = 2.0 * n * k * (32 * 2 * d + 2 * d * d + 32 * d)
+    head = (_ptr(aq), ld_aq, _ptr(qp), qs, _ptr(ap), as_, _ptr(idx), _ptr(kt), ld_kt, _ptr(vt), ld_vt)
+    return head, (aq, qp, ap, idx, kt, vt), out, ldo, n, kt.shape[0], k, d, divisor, flops
+
+
+def pt_cross_attn(aq, qpos, apos, idx, kt, vt, P1, c1, wp, w2, b2, p2, c2, out=None):
+    """Fused vector attention (occ4d_pt_cross_attn_f32): agg (n,d)."""
+    head, _alive, out, ldo, n, m, k, d, divisor, flops = _attn_operands(aq, qpos, apos, idx, kt, vt, out)
+    P1, c1, wp, w2, b2, p2, c2 = (_dev(t).contiguous() for t in (P1, c1, wp, w2, b2, p2, c2))
+    assert wp.shape == (2 * d, 32) and w2.shape == (d, 2 * d) and p2.shape == (d, 32)
     fn = _lib.lib().occ4d_pt_cross_attn_f32
-    w2_arg, wp_arg = ws[3], ws[2]
     _lib.check(_launch('cross_attn', dict(n=n, k=k, d=d), flops, lambda: fn(
-        _ptr(aq), ld_aq, _ptr(qp), qs, _ptr(ap), as_, _ptr(idx), _ptr(kt), ld_kt, _ptr(vt), ld_vt,
-        _ptr(ws[0]), _ptr(ws[1]), _ptr(wp_arg), _ptr(w2_arg), _ptr(ws[4]), _ptr(ws[5]), _ptr(ws[6]),
-        _ptr(o), ldo, n, kt.shape[0], k, d, divisor, _stream())))
+        *head, _ptr(P1), _ptr(c1), _ptr(wp), _ptr(w2), _ptr(b2), _ptr(p2), _ptr(c2), _ptr(out), ldo, n, m, k, d, divisor,
+        _stream())))
     return out
 
 
@@ -541,36 +548,19 @@ def pack_attn16p_stream(w2, b2, wp, p2, c2):
 def pt_cross_attn16p(aq, qpos, apos, idx, kt, vt, P1, c1, wstream, out=None, skew=None):
     """Fused vector attention, d = 416, paired workgroups (occ4d_pt_cross_attn16p_f32): agg (n, 416).
     `vt` is the value table WITH pos_mlp[2].bias folded in (Wv f + c2), one row per abstract point."""
-    aq, ld_aq = _aligned_rows(_dev(aq, name='aq'), 'aq')
-    kt, ld_kt = _aligned_rows(_dev(kt, name='kt'), 'kt')
-    vt, ld_vt = _rows(_dev(vt, name='vt'), 'vt')
-    qp, qs = _rows(_dev(qpos, name='qpos'), 'qpos')
-    ap, as_ = _rows(_dev(apos, name='apos'), 'apos')
-    idx = _dev(idx, torch.int32, 'idx')
-    n, k = idx.shape
-    d = vt.shape[1]
-    assert idx.is_contiguous() and aq.shape == (n, 2 * d) and kt.shape[1] == 2 * d and qp.shape[0] == n
-    ws = [_dev(t).contiguous() for t in (P1, c1)]
-    assert ws[0].shape == (32, 3) and wstream.is_contiguous()
-    if out is None:
-        out = torch.empty((n, d), dtype=torch.float32, device=aq.device)
-    o, ldo = _rows(out, 'out')
-    assert o is out and o.shape == (n, d)
-    divisor = float(torch.tensor(math.sqrt(d), dtype=torch.float32))
-    flops = 2.0 * n * k * (32 * 2 * d + 2 * d * d + 32 * d)      # executed, useful (same count as pt_cross_attn)
+    head, _alive, out, ldo, n, m, k, d, divisor, flops = _attn_operands(aq, qpos, apos, idx, kt, vt, out)
+    P1, c1 = (_dev(t).contiguous() for t in (P1, c1))
+    assert P1.shape == (32, 3) and wstream.is_contiguous()
     sk = ATTN16P_SKEW if skew is None else int(skew)
     _lib.check(_launch('cross_attn', dict(n=n, k=k, d=d), flops, lambda: _lib.lib().occ4d_pt_cross_attn16p_f32(
-        _ptr(aq), ld_aq, _ptr(qp), qs, _ptr(ap), as_, _ptr(idx), _ptr(kt), ld_kt, _ptr(vt), ld_vt,
-        _ptr(ws[0]), _ptr(ws[1]), _ptr(wstream), _ptr(o), ldo, n, kt.shape[0], k, d, divisor, sk, _stream())))
+        *head, _ptr(P1), _ptr(c1), _ptr(wstream), _ptr(out), ldo, n, m, k, d, divisor, sk, _stream())))
     return out
 
 
-def pt_pair_mlp(aq, kt, r, idx, c2, wstream, skew=None, logits=None):
-    """Training: the pair tensors of the merged-form layer in one kernel (occ4d_pt_pair_mlp_f32):
-    a (n k, 832) = aq_i - kt_j + Wp r before the ReLU, logits (n k, 416) = W2 relu(a) (attn_mlp[2].bias left out: it
-    cancels in the softmax), pe (n k, 416) = P2 r + c2.  wstream = pack_attn16p_stream(W2, ., Wp, P2, .).
-    `logits`: the (n k, 416) rows the training forward stored (pt_layer_fwd(..., logits_out=)): returned as they are,
-    the launch skips GEMM2 and only writes a and pe."""
+def _pair_operands(aq, kt, r, idx, c2, wstream):
+    """What the pair-tensor wrappers do alike (d = 416): aq / kt as aligned rows, idx (n, k) int32 and r (n k, 32) contiguous,
+    the shape checks, the outputs a (n k, 2d) and pe (n k, d).  -> (the entry points' eight leading arguments aq .. wstream, the
+    tensors behind them -- kept alive by the caller until the launch --, a, pe, n, m, k, d)."""
     aq, ld_aq = _aligned_rows(_dev(aq, name='aq'), 'aq')
     kt, ld_kt = _aligned_rows(_dev(kt, name='kt'), 'kt')
     idx = _dev(idx, torch.int32, 'idx')
@@ -581,19 +571,29 @@ def pt_pair_mlp(aq, kt, r, idx, c2, wstream, skew=None, logits=None):
     assert idx.is_contiguous() and r.is_contiguous() and r.shape == (n * k, 32) and aq.shape == (n, 2 * d)
     assert kt.shape[1] == 2 * d and c2.shape == (d,) and wstream.is_contiguous()
     a = torch.empty((n * k, 2 * d), dtype=torch.float32, device=aq.device)
+    pe = torch.empty((n * k, d), dtype=torch.float32, device=aq.device)
+    head = (_ptr(aq), ld_aq, _ptr(kt), ld_kt, _ptr(r), _ptr(idx), _ptr(c2), _ptr(wstream))
+    return head, (aq, kt, r, idx, c2), a, pe, n, kt.shape[0], k, d
+
+
+def pt_pair_mlp(aq, kt, r, idx, c2, wstream, skew=None, logits=None):
+    """Training: the pair tensors of the merged-form layer in one kernel (occ4d_pt_pair_mlp_f32):
+    a (n k, 832) = aq_i - kt_j + Wp r before the ReLU, logits (n k, 416) = W2 relu(a) (attn_mlp[2].bias left out: it
+    cancels in the softmax), pe (n k, 416) = P2 r + c2.  wstream = pack_attn16p_stream(W2, ., Wp, P2, .).
+    `logits`: the (n k, 416) rows the training forward stored (pt_layer_fwd(..., logits_out=)): returned as they are,
+    the launch skips GEMM2 and only writes a and pe."""
+    head, _alive, a, pe, n, m, k, d = _pair_operands(aq, kt, r, idx, c2, wstream)
     stored = logits is not None
     if stored:
         logits = _dev(logits, name='logits')
         assert logits.is_contiguous() and tuple(logits.shape) == (n * k, d)
     else:
-        logits = torch.empty((n * k, d), dtype=torch.float32, device=aq.device)
-    pe = torch.empty((n * k, d), dtype=torch.float32, device=aq.device)
+        logits = torch.empty((n * k, d), dtype=torch.float32, device=a.device)
     flops = 2.0 * n * k * (32 * 2 * d + (0 if stored else 2 * d * d) + 32 * d)
     sk = ATTN16P_SKEW if skew is None else int(skew)
     _lib.check(_launch('pair_hidden' if stored else 'pair_mlp', dict(n=n, k=k, d=d), flops,
                        lambda: _lib.lib().occ4d_pt_pair_mlp_f32(
-        _ptr(aq), ld_aq, _ptr(kt), ld_kt, _ptr(r), _ptr(idx), _ptr(c2), _ptr(wstream), _ptr(a),
-        None if stored else _ptr(logits), _ptr(pe), n, kt.shape[0], k, d, sk, _stream())))
+        *head, _ptr(a), None if stored else _ptr(logits), _ptr(pe), n, m, k, d, sk, _stream())))
     return a, logits, pe
 
 
@@ -611,22 +611,11 @@ def pack_attn_bf16x6_stream(w2, wp, p2):
 def pt_pair_mlp_bf16x6(aq, kt, r, idx, c2, wstream6):
     """pt_pair_mlp on the three-way split bf16 MFMAs (occ4d_pt_pair_mlp_bf16x6_f32; opt-in, fp32-class).
     wstream6 = pack_attn_bf16x6_stream(W2, Wp, P2)."""
-    aq, ld_aq = _aligned_rows(_dev(aq, name='aq'), 'aq')
-    kt, ld_kt = _aligned_rows(_dev(kt, name='kt'), 'kt')
-    idx = _dev(idx, torch.int32, 'idx')
-    n, k = idx.shape
-    d = TRUNK_WIDTH
-    r = _dev(r, name='r')
-    c2 = _dev(c2).contiguous()
-    assert idx.is_contiguous() and r.is_contiguous() and r.shape == (n * k, 32) and aq.shape == (n, 2 * d)
-    assert kt.shape[1] == 2 * d and c2.shape == (d,) and wstream6.is_contiguous()
-    a = torch.empty((n * k, 2 * d), dtype=torch.float32, device=aq.device)
-    logits = torch.empty((n * k, d), dtype=torch.float32, device=aq.device)
-    pe = torch.empty((n * k, d), dtype=torch.float32, device=aq.device)
+    head, _alive, a, pe, n, m, k, d = _pair_operands(aq, kt, r, idx, c2, wstream6)
+    logits = torch.empty((n * k, d), dtype=torch.float32, device=a.device)
     flops = 2.0 * n * k * (32 * 2 * d + 2 * d * d + 32 * d)
     _lib.check(_launch('pair_mlp', dict(n=n, k=k, d=d), flops, lambda: _lib.lib().occ4d_pt_pair_mlp_bf16x6_f32(
-        _ptr(aq), ld_aq, _ptr(kt), ld_kt, _ptr(r), _ptr(idx), _ptr(c2), _ptr(wstream6), _ptr(a), _ptr(logits), _ptr(pe),
-        n, kt.shape[0], k, d, _stream())))
+        *head, _ptr(a), _ptr(logits), _ptr(pe), n, m, k, d, _stream())))
     return a, logits, pe
 
 

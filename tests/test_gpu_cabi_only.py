@@ -40,41 +40,45 @@ class DecoderW(C.Structure):                   # occ4d_decoder_weights
                [('cross_after', C.c_int32 * 4), ('cross', LayerW * 4)]
 
 
+# the stub's own table, at module level so that tests/test_abi.py can read it beside the binding derived from the header
+# (importing this file touches no device and loads no library)
+LW, DW = C.POINTER(LayerW), C.POINTER(DecoderW)
+SIG = {
+    'occ4d_last_error': (C.c_char_p, []),
+    'occ4d_knn_f32': (C.c_int, [F, C.c_int64, C.c_int, F, C.c_int64, C.c_int, C.c_int, C.c_int, I, C.c_int, F, S]),
+    'occ4d_fps_f32': (C.c_int, [F, C.c_int64, C.c_int, C.c_int, I, I, S]),
+    'occ4d_gather_rows_f32': (C.c_int, [F, C.c_int64, I, C.c_int, C.c_int, F, C.c_int64, S]),
+    'occ4d_pt_layer_prepared_floats': (C.c_int64, [LW, C.c_int]),
+    'occ4d_pt_layer_prepare_f32': (C.c_int, [LW, F, C.c_int, S]),
+    'occ4d_pt_layer_workspace_floats': (C.c_int64, [LW, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'occ4d_pt_layer_fwd_f32': (C.c_int, [LW, F, F, C.c_int64, F, C.c_int64, C.c_int, F, C.c_int64, F, C.c_int64, C.c_int,
+                                         C.c_int, I, F, F, C.c_int64, F, C.c_int, C.c_void_p, S]),
+    'occ4d_down_pool_fwd_f32': (C.c_int, [F, C.c_int64, C.c_int, C.c_int, F, F, C.c_int, C.c_int, F, F, F, F, C.c_float, I,
+                                          C.c_int, C.c_int, F, C.c_int64, F, S]),
+    'occ4d_decoder_prepared_floats': (C.c_int64, [DW, C.c_int]),
+    'occ4d_decoder_prepare_f32': (C.c_int, [DW, F, C.c_int, S]),
+    'occ4d_decoder_scene_floats': (C.c_int64, [DW, C.c_int]),
+    'occ4d_decoder_prepare_scene_f32': (C.c_int, [DW, F, F, C.c_int64, F, C.c_int64, F, C.c_int, F, C.c_int, S]),
+    'occ4d_decoder_query_workspace_floats': (C.c_int64, [DW, C.c_int, C.c_int, C.c_int]),
+    'occ4d_decoder_query_fwd_f32': (C.c_int, [DW, F, F, C.c_int, F, C.c_int64, C.c_int, I, I, F, C.c_int64, F, C.c_int64,
+                                              F, C.c_int, C.c_void_p, S]),
+    'occ4d_knn_dists_f32': (C.c_int, [F, C.c_int64, C.c_int, F, C.c_int64, C.c_int, I, C.c_int, C.c_int, F, S]),
+    'occ4d_pack_trunk_rows_f32': (C.c_int, [F, C.c_int64, C.c_int, F, S]),
+    'occ4d_pack_trunk_cols_f32': (C.c_int, [F, C.c_int64, F, S]),
+    'occ4d_pack_trunk4_rows_f32': (C.c_int, [F, C.c_int64, C.c_int, F, S]),
+    'occ4d_pack_trunk4_cols_f32': (C.c_int, [F, C.c_int64, F, S]),
+    'occ4d_pack_attn16p_stream_f32': (C.c_int, [F, F, F, F, S]),
+    'occ4d_trunk_packed_floats': (C.c_int64, [C.c_int]),
+    'occ4d_trunk4_packed_floats': (C.c_int64, [C.c_int]),
+    'occ4d_pt_cross_attn16p_stream_floats': (C.c_int64, []),
+}
+
+
 @pytest.fixture(scope='module')
 def lib():
     assert torch.cuda.is_available(), 'GPU tests need a GPU'
     h = C.CDLL(os.path.join(ROOT, 'occlusions-4d_amd', 'libocc4d.so'))
-    LW, DW = C.POINTER(LayerW), C.POINTER(DecoderW)
-    sig = {
-        'occ4d_last_error': (C.c_char_p, []),
-        'occ4d_knn_f32': (C.c_int, [F, C.c_int64, C.c_int, F, C.c_int64, C.c_int, C.c_int, C.c_int, I, C.c_int, F, S]),
-        'occ4d_fps_f32': (C.c_int, [F, C.c_int64, C.c_int, C.c_int, I, I, S]),
-        'occ4d_gather_rows_f32': (C.c_int, [F, C.c_int64, I, C.c_int, C.c_int, F, C.c_int64, S]),
-        'occ4d_pt_layer_prepared_floats': (C.c_int64, [LW, C.c_int]),
-        'occ4d_pt_layer_prepare_f32': (C.c_int, [LW, F, C.c_int, S]),
-        'occ4d_pt_layer_workspace_floats': (C.c_int64, [LW, C.c_int, C.c_int, C.c_int, C.c_int]),
-        'occ4d_pt_layer_fwd_f32': (C.c_int, [LW, F, F, C.c_int64, F, C.c_int64, C.c_int, F, C.c_int64, F, C.c_int64, C.c_int,
-                                             C.c_int, I, F, F, C.c_int64, F, C.c_int, C.c_void_p, S]),
-        'occ4d_down_pool_fwd_f32': (C.c_int, [F, C.c_int64, C.c_int, C.c_int, F, F, C.c_int, C.c_int, F, F, F, F, C.c_float, I,
-                                              C.c_int, C.c_int, F, C.c_int64, F, S]),
-        'occ4d_decoder_prepared_floats': (C.c_int64, [DW, C.c_int]),
-        'occ4d_decoder_prepare_f32': (C.c_int, [DW, F, C.c_int, S]),
-        'occ4d_decoder_scene_floats': (C.c_int64, [DW, C.c_int]),
-        'occ4d_decoder_prepare_scene_f32': (C.c_int, [DW, F, F, C.c_int64, F, C.c_int64, F, C.c_int, F, C.c_int, S]),
-        'occ4d_decoder_query_workspace_floats': (C.c_int64, [DW, C.c_int, C.c_int, C.c_int]),
-        'occ4d_decoder_query_fwd_f32': (C.c_int, [DW, F, F, C.c_int, F, C.c_int64, C.c_int, I, I, F, C.c_int64, F, C.c_int64,
-                                                  F, C.c_int, C.c_void_p, S]),
-        'occ4d_knn_dists_f32': (C.c_int, [F, C.c_int64, C.c_int, F, C.c_int64, C.c_int, I, C.c_int, C.c_int, F, S]),
-        'occ4d_pack_trunk_rows_f32': (C.c_int, [F, C.c_int64, C.c_int, F, S]),
-        'occ4d_pack_trunk_cols_f32': (C.c_int, [F, C.c_int64, F, S]),
-        'occ4d_pack_trunk4_rows_f32': (C.c_int, [F, C.c_int64, C.c_int, F, S]),
-        'occ4d_pack_trunk4_cols_f32': (C.c_int, [F, C.c_int64, F, S]),
-        'occ4d_pack_attn16p_stream_f32': (C.c_int, [F, F, F, F, S]),
-        'occ4d_trunk_packed_floats': (C.c_int64, [C.c_int]),
-        'occ4d_trunk4_packed_floats': (C.c_int64, [C.c_int]),
-        'occ4d_pt_cross_attn16p_stream_floats': (C.c_int64, []),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in SIG.items():
         fn = getattr(h, name)
         fn.restype, fn.argtypes = res, args
     return h
