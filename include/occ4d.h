@@ -260,7 +260,9 @@ int occ4d_matmul_f64(const double* a, int64_t sam, int64_t sak, const double* b,
  * attn_mlp[2].bias is constant over the neighbour axis the softmax normalises over and cancels exactly; pos_mlp[2].bias
  * c2 must come folded into the value table: vt[j] = Wv f_j + c2 (the kernel adds P2 r_ij to it).
  * skew: phase offset given once to the later-placed workgroup of every CU in the first dispatch round, in units of
- * s_sleep(127) (about 8 K shader cycles); 0 = none.  Performance only -- results do not depend on it. */
+ * s_sleep(127) (about 8 K shader cycles); 0 = none.  Performance only -- results do not depend on it.
+ * 32-bit row offsets: n ld_aq 4 B and m ld_kt 4 B must stay below 4 GiB and m ld_vt below 2^31 floats, else OCC4D_EINVAL
+ * (chunk the queries; the path entry points chunk at 32768 rows). */
 int64_t occ4d_pt_cross_attn16p_stream_floats(void);
 int occ4d_pt_cross_attn16p_f32(const float* aq, int64_t ld_aq, const float* qpos, int64_t q_stride, const float* apos,
                                int64_t a_stride, const int32_t* idx, const float* kt, int64_t ld_kt, const float* vt,
@@ -273,7 +275,8 @@ int occ4d_pt_cross_attn16p_f32(const float* aq, int64_t ld_aq, const float* qpos
  * then needs no second GEMM2 (occ4d_pt_pair_mlp_f32 with logits = NULL).  With a_out (n k, 832), pe_out (n k, 416) and
  * c2 = pos_mlp[2].bias (all three or none) the hidden pre-activations a and pe = P2 r + c2 are left as well -- the three
  * pair tensors of occ4d_pt_pair_mlp_f32 on the same operands -- and backward recomputes nothing.
- * Same results in agg, bit for bit. */
+ * Same results in agg, bit for bit.  The same 32-bit row-offset limits: n ld_aq 4 B and m ld_kt 4 B below 4 GiB, m ld_vt
+ * below 2^31 floats, else OCC4D_EINVAL (chunk the queries). */
 int occ4d_pt_cross_attn16p_logits_f32(const float* aq, int64_t ld_aq, const float* qpos, int64_t q_stride, const float* apos,
                                       int64_t a_stride, const int32_t* idx, const float* kt, int64_t ld_kt, const float* vt,
                                       int64_t ld_vt, const float* P1, const float* c1, const float* wstream, float* agg,

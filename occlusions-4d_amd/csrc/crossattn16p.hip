@@ -704,6 +704,10 @@ static int attn16p_launch(const char* who, const float* aq, int64_t ld_aq, const
                     ((uintptr_t)wstream % 16) == 0,
                 "%s: aq / kt / wstream must be 16-byte aligned with ld %% 4 == 0", who);
   OCC4D_REQUIRE((int64_t)m * ld_vt < (int64_t)1 << 31, "%s: vt too large for 32-bit row offsets", who);
+  // the kernel addresses aq / kt rows by 32-bit BYTE offsets (aq_off, kt_off): the same limits as occ4d_pt_pair_mlp_f32
+  OCC4D_REQUIRE((int64_t)n * ld_aq * 4 < ((int64_t)1 << 32) && (int64_t)m * ld_kt * 4 < ((int64_t)1 << 32),
+                "%s: 32-bit row offsets: n * ld_aq * 4 B and m * ld_kt * 4 B must stay below 4 GiB (split the queries "
+                "into chunks)", who);
   OCC4D_REQUIRE(divisor > 0.f, "%s: divisor must be > 0", who);
   OCC4D_REQUIRE(skew >= 0 && skew <= 64, "%s: skew=%d outside [0,64]", who, skew);
   Attn16pArgs a{aq, ld_aq, qpos, qs, apos, as, idx, kt, ld_kt, vt, ld_vt, P1, c1, wstream, agg, ld_agg, n, m, k, divisor,
