@@ -9,6 +9,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libocc4d.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d.h')
+FRONTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_frontend.h')
 
 
 class NativeLibraryError(RuntimeError):
@@ -133,6 +134,15 @@ class DecoderWeights(C.Structure):
 SIGNATURES = parse_prototypes(_HEADER, {'occ4d_linear_args': LinearArgs, 'occ4d_pt_layer_weights': PtLayerWeights,
                                         'occ4d_launch_events': LaunchEvents, 'occ4d_decoder_weights': DecoderWeights})
 
+# the clip front end (frontend.py) has a header of its own, include/occ4d_frontend.h: occ4d.h's symbol set and ABI_VERSION
+# stay as they are.  Same conventions, same parser, same two libraries.
+try:
+    with open(FRONTEND_HEADER_PATH) as _f:
+        FRONTEND_SIGNATURES = parse_prototypes(_f.read(), {})
+except OSError as e:
+    raise NativeLibraryError('include/occ4d_frontend.h not found at %s (%s): the ctypes binding is derived from it'
+                             % (FRONTEND_HEADER_PATH, e))
+
 _lib = None
 _twin = False            # True only after an explicit load_cpu_twin(): host pointers, no streams (cpu_twin.py)
 
@@ -142,9 +152,9 @@ def is_twin():
 
 
 def bind(handle, missing=None):
-    """Sets restype / argtypes of every symbol of SIGNATURES on a loaded library and returns it.  A symbol the library does
+    """Sets restype / argtypes of every symbol of SIGNATURES and FRONTEND_SIGNATURES on a loaded library and returns it.  A symbol the library does
     not export is a stale library (NativeLibraryError) unless `missing` is given: then missing(name) stands in for it."""
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError:

@@ -23,6 +23,8 @@
 #include <vector>
 
 #include "occ4d.h"
+#include "occ4d_frontend.h"
+#include "frontend_math.hpp"      // csrc/: the front end's per-element arithmetic, the HIP kernels' own source
 
 namespace {
 
@@ -230,6 +232,14 @@ int occ4d_fps_start_f32(const float* xyz, int64_t stride, int n, int m, int star
 int occ4d_fps_f32(const float* xyz, int64_t stride, int n, int m, int32_t* out_sorted, int32_t* out_order, void* st) {
   return occ4d_fps_start_f32(xyz, stride, n, m, 0, out_sorted, out_order, st);
 }
+// the dataloader's clip reduction (the front end's last step): the same selection, status word 0
+int64_t occ4d_fps_coop_workspace_bytes(void) { return 64; }
+int occ4d_fps_coop_f32(const float* xyz, int64_t stride, int n, int m, int start, int, int32_t* out_sorted, int32_t* out_order,
+                       void* workspace, void* st) {
+  REQ(workspace, "occ4d_fps_coop_f32: null workspace");
+  std::memset(workspace, 0, 64);
+  return occ4d_fps_start_f32(xyz, stride, n, m, start, out_sorted, out_order, st);
+}
 
 int occ4d_nested_fps_level_i32(const int32_t* order, const int32_t* orig, int n, int m, int32_t* out_pos, int32_t* out_orig,
                                void*) {
@@ -412,6 +422,20 @@ int occ4d_compact_count_f32(const float* key, int64_t ld, int n, float threshold
   *total_kept = total;
   return OCC4D_OK;
 }
+int occ4d_compact_rows_f32(const float* src, int64_t ld, int n, int d, const float* key, int64_t ld_key, float threshold,
+                           int strict, const int* block_offsets, float* out_rows, float* out_key, void*) {
+  REQ(src && key && block_offsets && out_rows && n >= 0 && d >= 1 && ld >= d && ld_key >= 1, "occ4d_compact_rows_f32: bad arguments");
+  int64_t kept = 0;
+  for (int i = 0; i < n; ++i) {
+    const float kv = key[(int64_t)i * ld_key];
+    if (strict ? kv > threshold : kv >= threshold) {
+      std::memcpy(out_rows + kept * d, src + (int64_t)i * ld, sizeof(float) * d);
+      if (out_key) out_key[kept] = kv;
+      ++kept;
+    }
+  }
+  return OCC4D_OK;
+}
 int occ4d_split_count_f32(const float* implicit_output, int64_t ld, int n, float threshold, int* block_counts, int* total_solid,
                           void* st) {
   return occ4d_compact_count_f32(implicit_output, ld, n, threshold, 0, block_counts, total_solid, st);
@@ -443,6 +467,60 @@ int occ4d_split_write_f32(const float* pts, const float* outp, int64_t ld, int n
       std::memcpy(d, p, 16);
       std::memcpy(d + 4, o, sizeof(float) * g);
     }
+  }
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- front end
+// include/occ4d_frontend.h: the loops of csrc/frontend.hip over csrc/frontend_math.hpp
+int occ4d_rgbd_rows_f32(const float* depth, const float* rgb, const float* flat, const float* k_inv, const float* rt_inv,
+                        const float* hue_clusters, int n_clusters, int T, int H, int W, float x_min, float x_max, float y_min,
+                        float y_max, float z_min, float z_max, int floor_fix, int view_idx, float* out_rows, float* out_target,
+                        float* out_key, void*) {
+  namespace fe = occ4d_frontend;
+  REQ(depth && rgb && k_inv && rt_inv && out_rows && out_key, "occ4d_rgbd_rows_f32: null pointer");
+  REQ(T >= 0 && H >= 1 && W >= 1 && (int64_t)T * H * W < ((int64_t)1 << 31), "occ4d_rgbd_rows_f32: T = %d, H = %d, W = %d", T, H, W);
+  REQ(!flat || (hue_clusters && n_clusters >= 1 && n_clusters <= 64), "occ4d_rgbd_rows_f32: n_clusters = %d must be in 1 .. 64",
+      n_clusters);
+  const int64_t hw = (int64_t)H * W, total = hw * T;
+#pragma omp parallel for schedule(static)
+  for (int64_t p = 0; p < total; ++p) {
+    const int t = (int)(p / hw), pix = (int)(p % hw);
+    const float z = depth[p];
+    float xyz[3];
+    fe::unproject(k_inv + 16 * t, rt_inv + 16 * t, (float)(pix % W), (float)(pix / W), z, xyz);
+    const bool keep = z > 0.f && fe::in_cuboid(xyz, x_min, x_max, y_min, y_max, z_min, z_max, floor_fix != 0);
+    const float inst = flat ? fe::instance_id(flat[3 * p], flat[3 * p + 1], flat[3 * p + 2], hue_clusters, n_clusters) : -1.f;
+    const float row[8] = {xyz[0], xyz[1], xyz[2], inst, rgb[3 * p], rgb[3 * p + 1], rgb[3 * p + 2], (float)t};
+    std::memcpy(out_rows + 8 * p, row, sizeof row);
+    if (out_target) {
+      const float tgt[8] = {xyz[0], xyz[1], xyz[2], inst, (float)view_idx, row[4], row[5], row[6]};
+      std::memcpy(out_target + 8 * p, tgt, sizeof tgt);
+    }
+    out_key[p] = keep ? 1.f : 0.f;
+  }
+  return OCC4D_OK;
+}
+
+int occ4d_lidar_rows_f32(const float* rows, int64_t ld, int n, int d, const float* source, const float* inv_target, float z_offset,
+                         int cube_mode, double min_z, double other_bounds, float* out_rows, int64_t ldo, float* out_key, void*) {
+  namespace fe = occ4d_frontend;
+  REQ(rows && out_rows && out_key, "occ4d_lidar_rows_f32: null pointer");
+  REQ(n >= 0 && d >= 3 && ld >= d && ldo >= d, "occ4d_lidar_rows_f32: n = %d, d = %d, ld = %lld, ldo = %lld", n, d, (long long)ld,
+      (long long)ldo);
+  REQ((source != nullptr) == (inv_target != nullptr), "occ4d_lidar_rows_f32: source and inv_target go together");
+  REQ(cube_mode >= 0 && cube_mode <= 4, "occ4d_lidar_rows_f32: cube_mode %d (0 = no filter, 1 .. 4)", cube_mode);
+  const fe::Cuboid c = fe::carla_input_cuboid(cube_mode, min_z, other_bounds);
+#pragma omp parallel for schedule(static)
+  for (int i = 0; i < n; ++i) {
+    const float* src = rows + (int64_t)i * ld;
+    float* dst = out_rows + (int64_t)i * ldo;
+    float xyz[3] = {src[0], src[1], src[2]};
+    if (source) fe::lidar_transform(source, inv_target, xyz);
+    if (z_offset != 0.f) xyz[2] += z_offset;
+    dst[0] = xyz[0]; dst[1] = xyz[1]; dst[2] = xyz[2];
+    for (int k = 3; k < d; ++k) dst[k] = src[k];
+    out_key[i] = (cube_mode == 0 || fe::in_cuboid(xyz, c.x_min, c.x_max, c.y_min, c.y_max, c.z_min, c.z_max, false)) ? 1.f : 0.f;
   }
   return OCC4D_OK;
 }

@@ -1,10 +1,10 @@
 """Hot-path geometry helpers on the HIP library.
 
 Interface mirror of the hot functions of the reference's utils/geometry.py:
-``my_knn_torch`` (:458-503), ``sample_implicit_points_blind_numpy`` (:1199-1283) and the
-dataloader's ``subsample_pad_pcl_torch`` (:294-376).
-Everything else in that file (camera / lidar transforms, guided samplers, cuboid
-filters) is data preparation or training-only and out of scope.
+``my_knn_torch`` (:458-503), ``sample_implicit_points_blind_numpy`` (:1199-1283), the
+dataloader's ``subsample_pad_pcl_torch`` (:294-376) and its per-frame
+steps ``point_cloud_from_rgbd``, ``transform_lidar_frame`` and the input cuboid filters (rank 5;
+whole clips: frontend.py).
 """
 import os
 import numpy as np
@@ -162,11 +162,16 @@ def sample_random_uniform_3ball(num_points, max_radius, min_radius=0.0):
     return uvw * radius[:, None]
 
 
-def filter_pcl_bounds_torch(pcl, x_min=-10.0, x_max=10.0, y_min=-10.0, y_max=10.0, z_min=-10.0, z_max=10.0):
+def filter_pcl_bounds_torch(pcl, x_min=-10.0, x_max=10.0, y_min=-10.0, y_max=10.0, z_min=-10.0, z_max=10.0,
+                            greater_floor_fix=False):
     mask_x = torch.logical_and(x_min <= pcl[..., 0], pcl[..., 0] <= x_max)
     mask_y = torch.logical_and(y_min <= pcl[..., 1], pcl[..., 1] <= y_max)
     mask_z = torch.logical_and(z_min <= pcl[..., 2], pcl[..., 2] <= z_max)
-    return pcl[torch.logical_and(torch.logical_and(mask_x, mask_y), mask_z)]
+    mask = torch.logical_and(torch.logical_and(mask_x, mask_y), mask_z)
+    if greater_floor_fix:                   # filter_pcl_bounds_numpy's option (utils/geometry.py:164-167): GREATER's curving floor
+        inv_pyramid = torch.maximum(torch.abs(pcl[..., 0]), torch.abs(pcl[..., 1]))
+        mask = torch.logical_and(pcl[..., 2] > (inv_pyramid - 4.5) / 3.5, mask)
+    return pcl[mask]
 
 
 _CARLA_OUTPUT_SCALE = {1: (2.0, 1.0, 0.5), 2: (2.4, 0.8, 0.4), 3: (2.2, 1.0, 0.4), 4: (2.5, 1.0, 0.4)}
@@ -177,6 +182,42 @@ def filter_pcl_bounds_carla_output_torch(pcl, min_z=-0.5, other_bounds=16.0, pad
     return filter_pcl_bounds_torch(pcl, x_min=0.0 - padding, x_max=other_bounds * sx + padding,
                                    y_min=-other_bounds * sy - padding, y_max=other_bounds * sy + padding,
                                    z_min=min_z, z_max=other_bounds * sz)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# Interface mirrors of the reference's per-frame data preparation on the front-end kernels
+# (include/occ4d_frontend.h); whole clips go through frontend.greater_clip / frontend.carla_clip.
+# --------------------------------------------------------------------------------------------------------------
+def point_cloud_from_rgbd(rgb, depth, cam_RT, cam_K):
+    """rgb (H, W, 3) and depth (H, W) on the device, cam_RT (3, 4) and cam_K (3, 3) on the host -> (N, 6) rows (x, y, z, R, G,
+    B) of the pixels with depth > 0 in row-major order (utils/geometry.py:118-146)."""
+    from . import frontend
+    assert depth.dim() == 2 and tuple(rgb.shape) == tuple(depth.shape) + (3,), 'rgb must be (H, W, 3), depth (H, W)'
+    k_inv = torch.from_numpy(frontend.inverse_4x4(np.asarray(cam_K)[None])).to(depth.device)
+    rt_inv = torch.from_numpy(frontend.inverse_4x4(np.asarray(cam_RT)[None])).to(depth.device)
+    inf = float('inf')
+    rows, _, key = frontend.rgbd_rows(depth[None], rgb[None], None, k_inv, rt_inv, None, (-inf, inf, -inf, inf, -inf, inf),
+                                      floor_fix=False)
+    kept = ops.compact_rows(rows, key, 0.5, strict=True)[0]
+    return torch.cat([kept[:, :3], kept[:, 4:7]], dim=1)
+
+
+def transform_lidar_frame(lidar_pcl, source_matrix, target_matrix):
+    """Rows (N, D) = (x, y, z, *) on the device from the source sensor's frame into the target sensor's: source_matrix, then
+    inv(target_matrix), both (4, 4) float32 on the host (utils/geometry.py:1286-1306)."""
+    from . import frontend
+    inv_target = np.linalg.inv(np.asarray(target_matrix))
+    return frontend.lidar_rows(lidar_pcl, np.asarray(source_matrix), inv_target)[0]
+
+
+def filter_pcl_bounds_carla_input_torch(pcl, min_z=-0.5, other_bounds=20.0, cube_mode=4):
+    """filter_pcl_bounds_carla_input_numpy (utils/geometry.py:191-221) for rows (N, D) on the device; any other cube_mode
+    keeps every row, as the reference does."""
+    from . import frontend
+    if cube_mode not in (1, 2, 3, 4):
+        return pcl
+    rows, key = frontend.lidar_rows(pcl, cube_mode=cube_mode, min_z=min_z, other_bounds=other_bounds)
+    return ops.compact_rows(rows, key, 0.5, strict=True)[0]
 
 
 def get_vehped_points(pcl, segm_idx):
