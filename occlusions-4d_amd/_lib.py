@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libocc4d.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d.h')
 FRONTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_frontend.h')
+EVAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_eval.h')
 
 
 class NativeLibraryError(RuntimeError):
@@ -143,6 +144,17 @@ except OSError as e:
     raise NativeLibraryError('include/occ4d_frontend.h not found at %s (%s): the ctypes binding is derived from it'
                              % (FRONTEND_HEADER_PATH, e))
 
+# the evaluation statistics (evaluation.EvalStats) likewise: include/occ4d_eval.h, whose `#define OCC4D_EVAL_*` give the layout
+# of the two statistics arrays (EVAL_CONSTANTS: the names without the OCC4D_EVAL_ prefix)
+try:
+    with open(EVAL_HEADER_PATH) as _f:
+        _EVAL_HEADER = _f.read()
+except OSError as e:
+    raise NativeLibraryError('include/occ4d_eval.h not found at %s (%s): the ctypes binding is derived from it'
+                             % (EVAL_HEADER_PATH, e))
+EVAL_SIGNATURES = parse_prototypes(_EVAL_HEADER, {})
+EVAL_CONSTANTS = {k[len('EVAL_'):]: v for k, v in parse_constants(_EVAL_HEADER).items()}
+
 _lib = None
 _twin = False            # True only after an explicit load_cpu_twin(): host pointers, no streams (cpu_twin.py)
 
@@ -152,9 +164,9 @@ def is_twin():
 
 
 def bind(handle, missing=None):
-    """Sets restype / argtypes of every symbol of SIGNATURES and FRONTEND_SIGNATURES on a loaded library and returns it.  A symbol the library does
+    """Sets restype / argtypes of every symbol of SIGNATURES, FRONTEND_SIGNATURES and EVAL_SIGNATURES on a loaded library and returns it.  A symbol the library does
     not export is a stale library (NativeLibraryError) unless `missing` is given: then missing(name) stands in for it."""
-    for name, (res, args) in list(SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError:

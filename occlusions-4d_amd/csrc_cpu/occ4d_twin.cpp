@@ -24,7 +24,9 @@
 
 #include "occ4d.h"
 #include "occ4d_frontend.h"
+#include "occ4d_eval.h"
 #include "frontend_math.hpp"      // csrc/: the front end's per-element arithmetic, the HIP kernels' own source
+#include "eval_math.hpp"          // csrc/: the evaluation statistics' per-row classification, likewise
 
 namespace {
 
@@ -522,6 +524,97 @@ int occ4d_lidar_rows_f32(const float* rows, int64_t ld, int n, int d, const floa
     for (int k = 3; k < d; ++k) dst[k] = src[k];
     out_key[i] = (cube_mode == 0 || fe::in_cuboid(xyz, c.x_min, c.x_max, c.y_min, c.y_max, c.z_min, c.z_max, false)) ? 1.f : 0.f;
   }
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- evaluation
+// include/occ4d_eval.h: the loops of csrc/evalstats.hip over csrc/eval_math.hpp, rows in order, sums sequential
+int64_t occ4d_eval_counts_len(int n_groups, int n_classes) {
+  if (n_groups < 1 || n_groups > OCC4D_EVAL_MAX_GROUPS || n_classes < 0 || n_classes > OCC4D_EVAL_MAX_CLASSES) return -1;
+  return OCC4D_EVAL_HEAD + n_groups * occ4d_eval::group_stride(n_classes);
+}
+int64_t occ4d_eval_sums_len(int n_groups) {
+  return (n_groups < 1 || n_groups > OCC4D_EVAL_MAX_GROUPS) ? -1 : (int64_t)n_groups * OCC4D_EVAL_GROUP_SUMS;
+}
+int64_t occ4d_eval_workspace_bytes(int n) { return n < 0 ? -1 : 8; }
+
+int occ4d_eval_query_stats_f32(const float* out, int64_t ldo, int n, int g_out, const int32_t* nn_idx, const float* nn_dist,
+                               const float* target, int64_t ldt, int m, int dt, int col_rgb, int col_track, int col_sem, int out_track,
+                               const int32_t* target_group, int n_groups, int n_classes, float density_threshold, float radius,
+                               int flags, int64_t* counts, double* sums, void* workspace, void*) {
+  namespace ev = occ4d_eval;
+  const char* who = "occ4d_eval_query_stats_f32";
+  REQ(occ4d_eval_counts_len(n_groups, n_classes) > 0, "%s: n_groups = %d must be in 1 .. 8, n_classes = %d in 0 .. 32", who, n_groups, n_classes);
+  REQ(n >= 0 && m >= 0 && g_out >= 1 && dt >= 1 && ldo >= g_out && ldt >= dt, "%s: n = %d, m = %d, g_out = %d, ldo = %lld, dt = %d, ldt = %lld", who,
+      n, m, g_out, (long long)ldo, dt, (long long)ldt);
+  REQ(counts && sums && workspace && ((uintptr_t)workspace % 8) == 0, "%s: null counts / sums / workspace, or workspace not 8-byte aligned", who);
+  if (n == 0) return OCC4D_OK;
+  REQ(out && nn_idx && nn_dist && (target || m == 0), "%s: null pointer", who);
+  const bool color = (flags & OCC4D_EVAL_FLAG_COLOR) && col_rgb >= 0;
+  const bool track = (flags & OCC4D_EVAL_FLAG_TRACK) && col_track >= 0;
+  const bool seg = (flags & OCC4D_EVAL_FLAG_SEG) && col_sem >= 0 && n_classes >= 1;
+  REQ(!color || (g_out >= 4 && col_rgb + 3 <= dt), "%s: colour needs g_out = %d >= 4 and col_rgb = %d + 3 <= dt = %d", who, g_out, col_rgb, dt);
+  REQ(!track || (out_track >= 0 && out_track < g_out && col_track < dt), "%s: tracking needs out_track = %d < g_out = %d and col_track = %d < dt = %d", who,
+      out_track, g_out, col_track, dt);
+  REQ(!seg || (g_out >= n_classes && col_sem < dt), "%s: segmentation needs g_out = %d >= n_classes = %d and col_sem = %d < dt = %d", who, g_out,
+      n_classes, col_sem, dt);
+  const ev::QueryArgs a{out, ldo, n, g_out, nn_idx, nn_dist, target, ldt, m, color ? col_rgb : -1, track ? col_track : -1,
+                        seg ? col_sem : -1, out_track, target_group, n_groups, n_classes, density_threshold, radius};
+  const int64_t stride = ev::group_stride(n_classes);
+  double call[OCC4D_EVAL_MAX_GROUPS * OCC4D_EVAL_GROUP_SUMS] = {};      // the call's own totals, added onto the running values at the end
+  for (int i = 0; i < n; ++i) {
+    const ev::QueryRow r = ev::classify_query(a, i);
+    if (r.group < 0) {
+      ++counts[OCC4D_EVAL_BAD_ROWS];
+      continue;
+    }
+    int64_t* c = counts + OCC4D_EVAL_HEAD + r.group * stride;
+    double* s = call + r.group * OCC4D_EVAL_GROUP_SUMS;
+    ++c[r.occ];
+    if (r.solid) {
+      ++c[OCC4D_EVAL_N_ACCURACY];
+      s[OCC4D_EVAL_SUM_ACCURACY_D] += r.d;
+      s[OCC4D_EVAL_SUM_ACCURACY_D2] += r.d2;
+    }
+    if (r.color) {
+      ++c[OCC4D_EVAL_N_COLOR];
+      s[OCC4D_EVAL_SUM_COLOR_L1] += r.l1;
+    }
+    if (r.track >= 0) ++c[r.track];
+    if (r.seg >= 0) {
+      ++c[OCC4D_EVAL_GROUP_COUNTS + r.seg];
+      ++c[OCC4D_EVAL_N_SEG];
+    } else if (r.seg == -2) {
+      ++c[OCC4D_EVAL_SEG_IGNORED];
+    }
+  }
+  for (int k = 0; k < n_groups * OCC4D_EVAL_GROUP_SUMS; ++k) sums[k] += call[k];
+  return OCC4D_OK;
+}
+
+int occ4d_eval_target_stats_f32(const float* dist, int m, const int32_t* target_group, int n_groups, int n_classes, int64_t* counts,
+                                double* sums, void* workspace, void*) {
+  namespace ev = occ4d_eval;
+  const char* who = "occ4d_eval_target_stats_f32";
+  REQ(occ4d_eval_counts_len(n_groups, n_classes) > 0, "%s: n_groups = %d must be in 1 .. 8, n_classes = %d in 0 .. 32", who, n_groups, n_classes);
+  REQ(m >= 0 && counts && sums && workspace && ((uintptr_t)workspace % 8) == 0, "%s: m = %d, null counts / sums / workspace, or workspace not 8-byte aligned",
+      who, m);
+  if (m == 0) return OCC4D_OK;
+  REQ(dist, "%s: null pointer", who);
+  const int64_t stride = ev::group_stride(n_classes);
+  double call[OCC4D_EVAL_MAX_GROUPS * OCC4D_EVAL_GROUP_SUMS] = {};
+  for (int j = 0; j < m; ++j) {
+    const int g = ev::group_of(target_group, j, m, n_groups);
+    if (g < 0) {
+      ++counts[OCC4D_EVAL_BAD_ROWS];
+      continue;
+    }
+    ++counts[OCC4D_EVAL_HEAD + g * stride + OCC4D_EVAL_N_COMPLETENESS];
+    const double d = (double)dist[j];
+    call[g * OCC4D_EVAL_GROUP_SUMS + OCC4D_EVAL_SUM_COMPLETENESS_D] += d;
+    call[g * OCC4D_EVAL_GROUP_SUMS + OCC4D_EVAL_SUM_COMPLETENESS_D2] += d * d;
+  }
+  for (int k = 0; k < n_groups * OCC4D_EVAL_GROUP_SUMS; ++k) sums[k] += call[k];
   return OCC4D_OK;
 }
 

@@ -21,14 +21,163 @@ import pickle
 import numpy as np
 import torch
 
+from . import _lib
 from . import inference
+from . import ops
+
+_EC = _lib.EVAL_CONSTANTS
+# target columns (R; G, B follow / mark_track / semantic tag, -1 = absent) of the two data kinds (eval/inference.py:96):
+# GREATER rows are (x, y, z, instance, view, R, G, B, mark_track), CARLA rows (x, y, z, cosine, instance, semantic, view,
+# R, G, B, mark_track)
+TARGET_COLUMNS = {'greater': dict(col_rgb=5, col_track=8, col_sem=-1), 'carla': dict(col_rgb=7, col_track=10, col_sem=5)}
+_COUNT_NAMES = ('OCC_TP', 'OCC_FP', 'OCC_FN', 'OCC_TN', 'TRACK_TP', 'TRACK_FP', 'TRACK_FN', 'TRACK_TN', 'SEG_IGNORED',
+                'N_ACCURACY', 'N_COMPLETENESS', 'N_COLOR', 'N_SEG')
 
 
-def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt=False, reuse_encode=True):
+def _ratio(num, den):
+    """num / den element-wise in float64, nan where den == 0."""
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    return np.divide(num, den, out=np.full(np.broadcast(num, den).shape, np.nan), where=den != 0)
+
+
+class EvalStats:
+    """Additive evaluation statistics of decoded frames against their ground-truth frames (include/occ4d_eval.h): two device
+    arrays, `counts` (int64) and `sums` (float64), that `add_frame` accumulates onto with no host read of their contents,
+    that sum across frames, clips and ranks (`merge`, `+=`, `all_reduce`) and that `summary()` turns into the usual figures
+    with ONE host read.  Every statistic is kept per group (n_groups <= 8: the caller's partition of the target points,
+    e.g. visible / occluded); semantic_classes (<= 32) sizes the segmentation confusion matrix, 0 = none."""
+
+    def __init__(self, n_groups=1, semantic_classes=0, device=None):
+        self.n_groups, self.semantic_classes = int(n_groups), int(semantic_classes)
+        n_counts, n_sums = ops.eval_layout(self.n_groups, self.semantic_classes)
+        self.device = torch.device('cpu' if _lib.is_twin() else 'cuda') if device is None else torch.device(device)
+        self.counts = torch.zeros((n_counts,), dtype=torch.int64, device=self.device)
+        self.sums = torch.zeros((n_sums,), dtype=torch.float64, device=self.device)
+
+    def _tensor(self, a, dtype=torch.float32):
+        if isinstance(a, np.ndarray):
+            a = torch.from_numpy(np.ascontiguousarray(a))
+        return a.to(device=self.device, dtype=dtype)
+
+    def add_frame(self, points_query, implicit_output, target_rows, *, density_threshold, point_occupancy_radius, color_mode,
+                  predict_segmentation, track_mode, data_kind, target_group=None, nn=None, solid=None, col_rgb=None,
+                  col_track=None, col_sem=None):
+        """Adds one output frame: points_query (N, 3 or 4), implicit_output (N, G) (squashed, as perform_inference returns it),
+        target_rows (M, Dt) (device tensors or numpy, uploaded once).  target_group: (M,) integer group id per target point.
+        nn = (idx (N,), dist (N,)): the query -> target 1-NN if the caller has it; solid: the predicted-solid rows
+        (xyz first) if the caller has split them.  The target columns default from data_kind (TARGET_COLUMNS).  Colour is
+        scored for color_mode 'rgb' / 'rgb_nosigmoid', tracking for track_mode != 'none', segmentation for
+        predict_segmentation with semantic_classes > 0 and a semantic column."""
+        q, out, tgt = self._tensor(points_query), self._tensor(implicit_output), self._tensor(target_rows)
+        assert q.dim() == 2 and q.shape[1] in (3, 4) and out.dim() == 2 and out.shape[0] == q.shape[0], 'points_query (N, 3 or 4), implicit_output (N, G)'
+        assert tgt.dim() == 2 and tgt.shape[0] >= 1 and tgt.shape[1] >= 3, 'target_rows must be (M >= 1, Dt >= 3)'
+        cols = dict(TARGET_COLUMNS.get(data_kind, dict(col_rgb=-1, col_track=-1, col_sem=-1)))
+        cols.update({k: int(v) for k, v in dict(col_rgb=col_rgb, col_track=col_track, col_sem=col_sem).items() if v is not None})
+        flags = 0
+        if color_mode in ('rgb', 'rgb_nosigmoid'):
+            flags |= _EC['FLAG_COLOR']
+        if track_mode != 'none':
+            flags |= _EC['FLAG_TRACK']
+        if predict_segmentation and self.semantic_classes > 0:
+            flags |= _EC['FLAG_SEG']
+        grp = None if target_group is None else self._tensor(np.asarray(target_group) if not torch.is_tensor(target_group)
+                                                            else target_group, torch.int32).contiguous()
+        kw = dict(n_groups=self.n_groups, n_classes=self.semantic_classes, target_group=grp)
+        if q.shape[0] == 0:
+            return self
+        if nn is None:
+            idx, dist = ops.knn(q[:, :3], tgt[:, :3], 1, metric=1, return_dist=True)
+            nn = (idx[:, 0], dist[:, 0])
+        idx, dist = self._tensor(nn[0], torch.int32), self._tensor(nn[1])
+        if solid is None:
+            q4 = q if q.shape[1] == 4 else torch.nn.functional.pad(q, (0, 1))
+            solid = ops.split_solid_air(q4.contiguous(), out, density_threshold)[0]
+        solid = self._tensor(solid)
+        if solid.shape[0] > 0:               # completeness: every target point to its nearest predicted-solid query
+            _, back = ops.knn(tgt[:, :3], solid[:, :3], 1, metric=1, return_dist=True)
+            ops.eval_target_stats(back[:, 0], self.counts, self.sums, **kw)
+        ops.eval_query_stats(out, idx, dist, tgt, self.counts, self.sums, density_threshold=density_threshold,
+                             radius=point_occupancy_radius, flags=flags, out_track=inference.get_track_idx(color_mode), **cols, **kw)
+        return self
+
+    def _same_layout(self, other):
+        assert isinstance(other, EvalStats) and (other.n_groups, other.semantic_classes) == (self.n_groups, self.semantic_classes), \
+            'EvalStats of different (n_groups, semantic_classes) do not add'
+
+    def merge(self, other):
+        self._same_layout(other)
+        self.counts += other.counts.to(self.device)
+        self.sums += other.sums.to(self.device)
+        return self
+
+    __iadd__ = merge
+
+    def all_reduce(self, group=None):
+        """torch.distributed SUM over both arrays (the same layout on every rank)."""
+        import torch.distributed as dist
+        dist.all_reduce(self.counts, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(self.sums, op=dist.ReduceOp.SUM, group=group)
+        return self
+
+    def state(self):
+        """The object as numpy (copies: a later add does not change them); from_state() is the way back."""
+        return dict(n_groups=self.n_groups, semantic_classes=self.semantic_classes, counts=self.counts.cpu().numpy().copy(),
+                    sums=self.sums.cpu().numpy().copy())
+
+    @classmethod
+    def from_state(cls, state, device=None):
+        self = cls(int(state['n_groups']), int(state['semantic_classes']), device)
+        counts, sums = np.asarray(state['counts'], np.int64), np.asarray(state['sums'], np.float64)
+        assert counts.shape == tuple(self.counts.shape) and sums.shape == tuple(self.sums.shape)
+        self.counts.copy_(torch.from_numpy(counts))
+        self.sums.copy_(torch.from_numpy(sums))
+        return self
+
+    def summary(self):
+        """The figures per group, as float64 arrays of shape (n_groups,) (nan where the denominator is 0), from one host read:
+        precision, recall, f1, iou (occupancy, prediction against the 1-NN label); chamfer_accuracy (mean nn distance of
+        the predicted-solid queries), chamfer_completeness (mean distance of the target points to the nearest predicted-
+        solid query), chamfer (their sum) and chamfer_*_sq / chamfer_sq on squared distances; seg_accuracy, seg_miou (over
+        the classes that occur as a row or a column of the confusion matrix); track_iou; color_l1 (mean |dR| + |dG| + |dB|).
+        'counts': the raw counts by name ((n_groups,) int64 each), 'confusion' (n_groups, C, C), 'bad_rows'.  Raises
+        ValueError when rows were skipped (bad_rows > 0)."""
+        G, C, K = self.n_groups, self.semantic_classes, _EC['GROUP_COUNTS']
+        both = torch.cat([self.counts.view(torch.float64), self.sums]).cpu()           # (bit reinterpretation: ONE transfer)
+        counts, sums = both[:self.counts.numel()].view(torch.int64).numpy(), both[self.counts.numel():].numpy()
+        bad = int(counts[_EC['BAD_ROWS']])
+        if bad > 0:
+            raise ValueError('EvalStats: %d rows were skipped (nn_idx outside the target, or a group id outside [0, %d))' % (bad, G))
+        per = counts[_EC['HEAD']:].reshape(G, K + C * C)
+        c = {name.lower(): per[:, _EC[name]].copy() for name in _COUNT_NAMES}
+        conf = per[:, K:].reshape(G, C, C).copy()
+        s = sums.reshape(G, _EC['GROUP_SUMS'])
+        tp, fp, fn = c['occ_tp'], c['occ_fp'], c['occ_fn']
+        res = dict(precision=_ratio(tp, tp + fp), recall=_ratio(tp, tp + fn), f1=_ratio(2 * tp, 2 * tp + fp + fn),
+                   iou=_ratio(tp, tp + fp + fn))
+        res['chamfer_accuracy'] = _ratio(s[:, _EC['SUM_ACCURACY_D']], c['n_accuracy'])
+        res['chamfer_completeness'] = _ratio(s[:, _EC['SUM_COMPLETENESS_D']], c['n_completeness'])
+        res['chamfer'] = res['chamfer_accuracy'] + res['chamfer_completeness']
+        res['chamfer_accuracy_sq'] = _ratio(s[:, _EC['SUM_ACCURACY_D2']], c['n_accuracy'])
+        res['chamfer_completeness_sq'] = _ratio(s[:, _EC['SUM_COMPLETENESS_D2']], c['n_completeness'])
+        res['chamfer_sq'] = res['chamfer_accuracy_sq'] + res['chamfer_completeness_sq']
+        diag = np.einsum('gcc->gc', conf)
+        union = conf.sum(axis=2) + conf.sum(axis=1) - diag
+        res['seg_accuracy'] = _ratio(diag.sum(axis=1), conf.sum(axis=(1, 2)))
+        res['seg_miou'] = _ratio(np.where(union > 0, _ratio(diag, union), 0.0).sum(axis=1), (union > 0).sum(axis=1))
+        res['track_iou'] = _ratio(c['track_tp'], c['track_tp'] + c['track_fp'] + c['track_fn'])
+        res['color_l1'] = _ratio(s[:, _EC['SUM_COLOR_L1']], c['n_color'])
+        res.update(counts=c, confusion=conf, bad_rows=bad)
+        return res
+
+
+def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt=False, reuse_encode=True, stats=None,
+                  stats_group_fn=None):
     """batch: dict with 'pcl_input' (1,N,8), 'pcl_input_sem' (1,N,1-3), 'pcl_target' list of (1,T,9-11) tensors and
     batch['meta_data']['pcl_target_size'] (list of (1,) tensors), as the reference's test data loader yields them
     (data/data_greater.py:593-606, data/data_carla.py:651-661).  args: namespace with the test_args fields used
-    below (args.py:311-410).  Returns pcl_all (list over output frames of tuples of numpy arrays)."""
+    below (args.py:311-410).  Returns pcl_all (list over output frames of tuples of numpy arrays).
+    stats: an EvalStats that every output frame is added to, scored against its target frame (on the device, beside the
+    decode); stats_group_fn(frame_rows) -> (T,) integer array: the group of every target point.  None: nothing is scored."""
     # One encode per clip is only equivalent to the reference's encode per output frame when the encode is
     # deterministic: a network built with fps_random_start=True (the constructor default; the reference's test path
     # builds its networks with False, eval/inference.py:59) draws a new FPS start per call, so it is re-encoded per frame.
@@ -45,6 +194,9 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
     for time_idx in range(len(pcl_target)):
         frame = pcl_target[time_idx][0].detach().cpu().numpy()
         frame = frame[:int(sizes[time_idx].item() if torch.is_tensor(sizes[time_idx]) else sizes[time_idx])]
+        stats_kw = {}
+        if stats is not None:
+            stats_kw = dict(stats=stats, stats_target=frame, stats_group=None if stats_group_fn is None else stats_group_fn(frame))
         res = inference.perform_inference(
             pcl_input.clone(), sem_inference, frame if save_gt else None, networks, device, 'if', args.min_z,
             args.cr_cube_bounds, args.color_mode, time_idx, logger, sample_implicit=args.sample_implicit,
@@ -52,7 +204,7 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
             predict_segmentation=args.segmentation_lw > 0.0, track_mode=args.track_mode,
             point_occupancy_radius=args.point_occupancy_radius, semantic_classes=args.semantic_classes,
             density_threshold=args.density_threshold, data_kind=data_kind, cube_mode=args.cube_mode, compress_air=True,
-            encoded=encoded if reuse_encode else None, return_encoded=reuse_encode)
+            encoded=encoded if reuse_encode else None, return_encoded=reuse_encode, **stats_kw)
         if reuse_encode and args.track_mode in ('none', 'one'):
             encoded = res.pop('_encoded')
         else:

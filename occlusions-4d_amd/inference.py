@@ -150,7 +150,8 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                       batch_size=1024, predict_segmentation=False, track_mode='none',
                       point_occupancy_radius=0.2, semantic_classes=13,
                       density_threshold=0.5, data_kind='', cube_mode=4, compress_air=False,
-                      encoded=None, return_encoded=False, neighbour_lists=None):
+                      encoded=None, return_encoded=False, neighbour_lists=None, stats=None, stats_target=None,
+                      stats_group=None):
     """One encode of the input point-cloud video + decode of all query points of one output
     frame.  Returns dict(output_solid, output_air, pcl_abstract, features_global,
     implicit_output, points_query) of float32 numpy arrays.
@@ -158,7 +159,10 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     device tensors of an earlier call on the same input cloud (the reference's eval loop re-encodes the clip for every
     output frame, eval/test.py:67-86); `return_encoded` adds them to the result as '_encoded'; `neighbour_lists` =
     (knn_local (N_q, 8), knn_cross (N_q, 14)) integer arrays: the decoder's neighbour lists of a particular run of the
-    reference for these queries (LocalPclResnetFC.forward's extension; either entry may be None)."""
+    reference for these queries (LocalPclResnetFC.forward's extension; either entry may be None); `stats` = an
+    evaluation.EvalStats this frame is added to, scored on the device against `pcl_target_frame` (or `stats_target` when that
+    is not passed: no gt_solid / gt_air then) with `stats_group` = the group id per target point; the query -> target search
+    and the solid split are shared with the gt branch and the result dict is what it is without `stats`."""
     assert task == 'if'
     assert sample_implicit
     output_track_idx = get_track_idx(color_mode)
@@ -207,15 +211,32 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                 [copies.result(h) for h in all_output], output_track_idx)
 
         gt_available = pcl_target_frame is not None
+        nn_dev = target_dev = None
+        if stats is not None:                 # one upload of the target rows, one search for both consumers
+            stats_rows = pcl_target_frame if gt_available else stats_target
+            assert stats_rows is not None, 'stats needs a target frame: pcl_target_frame or stats_target'
+            target_dev = torch.as_tensor(np.ascontiguousarray(stats_rows, dtype=np.float32) if isinstance(stats_rows, np.ndarray)
+                                         else stats_rows).to(device=device, dtype=torch.float32)
+            nn_dev = nn_target(queries_dev[:, :3], target_dev[:, :3])
         if gt_available:                      # nearest ground-truth point of every query (:270-276)
-            target_labels, nn_indices = get_1nn_label(queries_dev[:, :3], pcl_target_frame, point_occupancy_radius,
-                                                      device)
+            if nn_dev is not None:
+                target_labels, nn_indices = nn_labels(nn_dev[0], nn_dev[1], point_occupancy_radius)
+            else:
+                target_labels, nn_indices = get_1nn_label(queries_dev[:, :3], pcl_target_frame, point_occupancy_radius,
+                                                          device)
             points_nngt = np.concatenate([target_labels[:, None], pcl_target_frame[nn_indices]], axis=-1)
 
         # density-threshold split + compress_air on the device (:279-305): order-preserving compaction
         if not single_run:                    # merged on the host; one upload
             output_dev = torch.from_numpy(implicit_output).to(device)
         solid, air = ops.split_solid_air(queries_dev, output_dev, density_threshold, compress_air, semantic_classes)
+        if stats is not None:
+            assert not predict_segmentation or stats.semantic_classes in (0, semantic_classes), \
+                'stats.semantic_classes = %d, semantic_classes = %d' % (stats.semantic_classes, semantic_classes)
+            stats.add_frame(queries_dev, output_dev, target_dev, density_threshold=density_threshold,
+                            point_occupancy_radius=point_occupancy_radius, color_mode=color_mode,
+                            predict_segmentation=predict_segmentation, track_mode=track_mode, data_kind=data_kind,
+                            target_group=stats_group, nn=nn_dev, solid=solid)
         # (the reference's concatenate with the int64 argmax promotes the compressed air rows to float64: converted on
         # the device, not by a host pass over the array)
         solid_h = copies.fetch(solid)
@@ -240,13 +261,22 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     return result
 
 
+def nn_target(points_query_xyz, target_xyz):
+    """(idx (N,) int32, dist (N,)) on the device: the nearest target point of every query.  Streaming k = 1 kernel."""
+    idx, dist = ops.knn(points_query_xyz, target_xyz, 1, metric=1, return_dist=True)
+    return idx[:, 0], dist[:, 0]
+
+
+def nn_labels(idx, dist, thresh):
+    """The host arrays of get_1nn_label from a search's device results."""
+    return (dist < thresh).cpu().numpy() * 1, idx.cpu().numpy().astype(np.int64)
+
+
 def get_1nn_label(points_query_xyz, pcl_target_frame, thresh, device):
     """Pseudo label of every query from its nearest target point (utils/geometry.py:444-455, an sklearn
     KDTree there): label = (distance < thresh), plus the neighbour's index.  Streaming k = 1 kernel."""
     target_xyz = torch.from_numpy(np.ascontiguousarray(pcl_target_frame[..., :3], dtype=np.float32)).to(device)
-    idx, dist = ops.knn(points_query_xyz, target_xyz, 1, metric=1, return_dist=True)
-    labels = (dist[:, 0] < thresh).cpu().numpy() * 1
-    return labels, idx[:, 0].cpu().numpy().astype(np.int64)
+    return nn_labels(*nn_target(points_query_xyz, target_xyz), thresh)
 
 
 def multi_track_merge(track_instance_ids, pcl_abstract, features_global, implicit_output, output_track_idx):

@@ -1184,6 +1184,53 @@ def compact_rows_nosync(rows, key, threshold, strict=True):
     return out_rows, scratch[nb:nb + 1]
 
 
+def eval_layout(n_groups, n_classes):
+    """(len(counts), len(sums)) of the evaluation statistics arrays (include/occ4d_eval.h) for this many groups / classes."""
+    lens = (int(_lib.lib().occ4d_eval_counts_len(int(n_groups), int(n_classes))), int(_lib.lib().occ4d_eval_sums_len(int(n_groups))))
+    assert min(lens) > 0, 'n_groups = %s must be in 1 .. 8 and n_classes = %s in 0 .. 32' % (n_groups, n_classes)
+    return lens
+
+
+def _eval_arrays(counts, sums, target_group, m, n_groups, n_classes, n):
+    c, s = _dev(counts, torch.int64, 'counts'), _dev(sums, torch.float64, 'sums')
+    assert c.is_contiguous() and s.is_contiguous() and (c.numel(), s.numel()) == eval_layout(n_groups, n_classes)
+    grp = None
+    if target_group is not None:
+        grp = _dev(target_group, torch.int32, 'target_group')
+        assert grp.shape == (m,) and grp.is_contiguous()
+    ws = torch.empty((int(_lib.lib().occ4d_eval_workspace_bytes(n)) // 8,), dtype=torch.float64, device=c.device)
+    return c, s, grp, ws
+
+
+def eval_query_stats(implicit_output, nn_idx, nn_dist, target, counts, sums, *, n_groups=1, n_classes=0, density_threshold=0.5,
+                     radius=0.2, flags=0, col_rgb=-1, col_track=-1, col_sem=-1, out_track=4, target_group=None):
+    """Adds the statistics of the N decoded queries of a frame (implicit_output (N, G), the nearest target row nn_idx (N) int32
+    and its distance nn_dist (N), target (M, Dt)) onto `counts` (int64) / `sums` (float64), in place: occ4d_eval_query_stats_f32.
+    No host read."""
+    o, ldo = _rows(_dev(implicit_output, name='implicit_output'), 'implicit_output')
+    t, ldt = _rows(_dev(target, name='target'), 'target')
+    n, m = o.shape[0], t.shape[0]
+    idx, dist = _dev(nn_idx, torch.int32, 'nn_idx'), _dev(nn_dist, name='nn_dist')
+    assert idx.shape == (n,) and dist.shape == (n,), 'nn_idx / nn_dist must be (N,)'
+    idx, dist = idx.contiguous(), dist.contiguous()
+    c, s, grp, ws = _eval_arrays(counts, sums, target_group, m, n_groups, n_classes, n)
+    _lib.check(_lib.lib().occ4d_eval_query_stats_f32(_ptr(o), ldo, n, o.shape[1], _ptr(idx), _ptr(dist), _ptr(t), ldt, m, t.shape[1],
+                                                     int(col_rgb), int(col_track), int(col_sem), int(out_track), _ptr(grp),
+                                                     int(n_groups), int(n_classes), float(density_threshold), float(radius),
+                                                     int(flags), _ptr(c), _ptr(s), _ptr(ws), _stream()))
+
+
+def eval_target_stats(dist, counts, sums, *, n_groups=1, n_classes=0, target_group=None):
+    """Adds the completeness statistics of the M target points (dist (M): distance to the nearest predicted-solid query) onto
+    `counts` / `sums`, in place: occ4d_eval_target_stats_f32.  No host read."""
+    d = _dev(dist, name='dist')
+    assert d.dim() == 1
+    d = d.contiguous()
+    c, s, grp, ws = _eval_arrays(counts, sums, target_group, d.shape[0], n_groups, n_classes, d.shape[0])
+    _lib.check(_lib.lib().occ4d_eval_target_stats_f32(_ptr(d), d.shape[0], _ptr(grp), int(n_groups), int(n_classes), _ptr(c), _ptr(s),
+                                                      _ptr(ws), _stream()))
+
+
 def add_rows(a, b):
     """a + b for two (n, d) tensors (exact fp32 add; the sampler's query = target point + offset)."""
     a, lda = _rows(_dev(a, name='a'), 'a')
