@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, 'libocc4d.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d.h')
 FRONTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_frontend.h')
 EVAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_eval.h')
+OCCL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_occl.h')
 
 
 class NativeLibraryError(RuntimeError):
@@ -155,6 +156,17 @@ except OSError as e:
 EVAL_SIGNATURES = parse_prototypes(_EVAL_HEADER, {})
 EVAL_CONSTANTS = {k[len('EVAL_'):]: v for k, v in parse_constants(_EVAL_HEADER).items()}
 
+# the id histogram behind the live occlusion fractions (occlusion.py): include/occ4d_occl.h, whose `#define OCC4D_OCCL_*` give
+# the bin limit and the two extra bins (OCCL_CONSTANTS: the names without the OCC4D_OCCL_ prefix)
+try:
+    with open(OCCL_HEADER_PATH) as _f:
+        _OCCL_HEADER = _f.read()
+except OSError as e:
+    raise NativeLibraryError('include/occ4d_occl.h not found at %s (%s): the ctypes binding is derived from it'
+                             % (OCCL_HEADER_PATH, e))
+OCCL_SIGNATURES = parse_prototypes(_OCCL_HEADER, {})
+OCCL_CONSTANTS = {k[len('OCCL_'):]: v for k, v in parse_constants(_OCCL_HEADER).items()}
+
 _lib = None
 _twin = False            # True only after an explicit load_cpu_twin(): host pointers, no streams (cpu_twin.py)
 
@@ -164,9 +176,10 @@ def is_twin():
 
 
 def bind(handle, missing=None):
-    """Sets restype / argtypes of every symbol of SIGNATURES, FRONTEND_SIGNATURES and EVAL_SIGNATURES on a loaded library and returns it.  A symbol the library does
+    """Sets restype / argtypes of every symbol of SIGNATURES, FRONTEND_SIGNATURES, EVAL_SIGNATURES and OCCL_SIGNATURES on a loaded library and returns it.  A symbol the library does
     not export is a stale library (NativeLibraryError) unless `missing` is given: then missing(name) stands in for it."""
-    for name, (res, args) in list(SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
+            list(OCCL_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError:

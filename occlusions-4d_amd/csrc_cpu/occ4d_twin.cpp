@@ -25,8 +25,10 @@
 #include "occ4d.h"
 #include "occ4d_frontend.h"
 #include "occ4d_eval.h"
+#include "occ4d_occl.h"
 #include "frontend_math.hpp"      // csrc/: the front end's per-element arithmetic, the HIP kernels' own source
 #include "eval_math.hpp"          // csrc/: the evaluation statistics' per-row classification, likewise
+#include "occl_math.hpp"          // csrc/: the id histogram's per-row decision, likewise
 
 namespace {
 
@@ -615,6 +617,35 @@ int occ4d_eval_target_stats_f32(const float* dist, int m, const int32_t* target_
     call[g * OCC4D_EVAL_GROUP_SUMS + OCC4D_EVAL_SUM_COMPLETENESS_D2] += d * d;
   }
   for (int k = 0; k < n_groups * OCC4D_EVAL_GROUP_SUMS; ++k) sums[k] += call[k];
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- id histogram
+// include/occ4d_occl.h: the walk of csrc/idhist.hip over csrc/occl_math.hpp, rows in order.  The offsets are host memory
+// here, so the contract on them is checked.
+int occ4d_id_histogram_f32(const float* rows, int64_t ld, int n, int col, const int64_t* seg_offsets, int n_segments, int n_ids,
+                           const float* key, int pred_col, float pred_a, float pred_b, int32_t* counts, void*) {
+  namespace oc = occ4d_occl;
+  const char* who = "occ4d_id_histogram_f32";
+  REQ(n_ids >= 1 && n_ids <= OCC4D_OCCL_MAX_IDS, "%s: n_ids = %d must be in 1 .. %d", who, n_ids, OCC4D_OCCL_MAX_IDS);
+  REQ(n >= 0 && n_segments >= 0 && ld >= 1, "%s: n = %d, n_segments = %d, ld = %lld", who, n, n_segments, (long long)ld);
+  REQ(col >= 0 && col < ld, "%s: col = %d must be in 0 .. ld - 1 = %lld", who, col, (long long)ld - 1);
+  REQ(pred_col >= -1 && pred_col < ld, "%s: pred_col = %d must be -1 or in 0 .. ld - 1 = %lld", who, pred_col, (long long)ld - 1);
+  if (n == 0 || n_segments == 0) return OCC4D_OK;
+  REQ(rows && seg_offsets && counts, "%s: null rows / seg_offsets / counts", who);
+  REQ(seg_offsets[0] == 0 && seg_offsets[n_segments] == n, "%s: seg_offsets must run from 0 to n = %d, got %lld .. %lld", who, n,
+      (long long)seg_offsets[0], (long long)seg_offsets[n_segments]);
+  for (int s = 0; s < n_segments; ++s)
+    REQ(seg_offsets[s] <= seg_offsets[s + 1], "%s: seg_offsets must ascend (segment %d: %lld > %lld)", who, s,
+        (long long)seg_offsets[s], (long long)seg_offsets[s + 1]);
+  const oc::HistArgs a{rows, ld, n, col, key, pred_col, pred_a, pred_b, n_ids};
+  const int bins = n_ids + OCC4D_OCCL_EXTRA_BINS;
+  for (int64_t i = 0; i < n; ++i) {
+    const int bin = oc::bin_of(a, i);
+    if (bin < 0) continue;
+    const int seg = oc::segment_end_index(seg_offsets, n_segments, i) - 1;
+    ++counts[(int64_t)seg * bins + bin];
+  }
   return OCC4D_OK;
 }
 

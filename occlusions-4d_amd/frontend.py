@@ -14,15 +14,20 @@ np.random.choice draws, the shuffles -- drawn as np.random.shuffle of arange(n),
 shuffling the (n, D) array does --, the torch.randint start of the farthest-point sampling), so equal seeds give the
 reference's clouds bit for bit (tests/golden/frontend_*.npz).
 
-Out of scope: file I/O and image decoding, the dataset classes, the occlusion-biased clip choice, get_valo_ids and the
-choice of track_id (the caller passes it).
+With ``live_occl_mode`` ('unfilt' / 'normal') the clip functions also give the loader's ``valo_ids``, ``num_valo_ids`` and
+``live_occl`` (get_valo_ids, data/data_utils.py:12-100), with ``track_mode`` greater_clip chooses ``track_id`` as data/
+data_greater.py:534-552 does (occlusion.py): the id histograms run on buffers the clip holds anyway ('unfilt': the raw rows and
+their keep key, no compacted copy) and all tables are fetched in ONE further device -> host read.
+
+Out of scope: file I/O and image decoding, the dataset classes, the occlusion-biased clip choice (sample_bias='occl' reads
+occl.txt from the dataset).
 """
 import ctypes as C
 
 import numpy as np
 import torch
 
-from . import _lib, geometry, ops
+from . import _lib, geometry, occlusion, ops
 
 
 def _device_f32(a, device, name, shape_tail=None):
@@ -162,10 +167,12 @@ def _cat(parts, d, device):
 
 
 def _finish(all_input, all_target, n_fps_input, n_fps_target, pcl_input_frames, pcl_target_frames, n_sem, track_id,
-            target_inst_col, target_filter=None, retain_vehped=False, segm_idx=None):
+            target_inst_col, target_filter=None, retain_vehped=False, segm_idx=None, occl=None):
     """The common tail of both loaders.  all_input: list-T of the source view's rows (x, y, z, sem..., R, G, B, t);
     all_target: list-T of list-V of rows (x, y, z, sem..., view, R, G, B); target_filter(frame) -> keep key (m) on the device:
-    an order-preserving selection of every shuffled target frame, the kept counts of all frames read in ONE transfer."""
+    an order-preserving selection of every shuffled target frame, the kept counts of all frames read in ONE transfer.
+    occl: the clip's occlusion.ClipCounts or None; its one read comes after every random draw of the clip, and a track id it
+    chooses replaces `track_id`."""
     device = all_input[0].device
     meta = dict(sample_input_ratios=[], sample_target_ratios=[])
     pcl_input = _shuffled(_cat(all_input[:pcl_input_frames], all_input[0].shape[1], device))
@@ -199,6 +206,10 @@ def _finish(all_input, all_target, n_fps_input, n_fps_target, pcl_input_frames, 
             sizes[i] = min(pre, post)
     meta['pcl_target_size'] = sizes
 
+    if occl is not None:
+        extra = occl.finish(pcl_input)
+        track_id = extra.get('track_id', track_id)
+        meta.update(extra)
     pcl_input_sem = pcl_input[:, 3:3 + n_sem]
     track_in = torch.zeros_like(pcl_input[:, 0:1])
     track_tg = [torch.zeros_like(f[:, 0:1]) for f in pcl_target]
@@ -212,18 +223,26 @@ def _finish(all_input, all_target, n_fps_input, n_fps_target, pcl_input_frames, 
 
 def greater_clip(rgb, flat, depth, cam_RT, cam_K, hue_clusters, other_bounds=5.0, min_z=-1.0, n_points_rnd=0,
                  n_fps_input=14336, n_fps_target=14336, pcl_input_frames=12, pcl_target_frames=12, src_view=0, track_id=-1,
-                 device=None):
+                 device=None, live_occl_mode=None, track_mode=None, max_valo_ids=32, occl_n_ids=None):
     """RGB-D frames of V views and T times -> (pcl_input (n, 8) = (x, y, z, R, G, B, t, mark_track), pcl_input_sem (n, 1) =
     (instance_id), pcl_target list of (m, 9) = (x, y, z, instance_id, view_idx, R, G, B, mark_track), meta_data) on the device.
     rgb, flat (V, T, H, W, 3), depth (V, T, H, W), cam_RT (V, T, 3, 4), cam_K (V, T, 3, 3): numpy arrays or tensors (tensors on
     the device are used in place).  meta_data: pcl_sizes (V, T), cuboid_filter_ratios, sample_input_ratios,
-    sample_target_ratios, pcl_input_size, pcl_target_size."""
+    sample_target_ratios, pcl_input_size, pcl_target_size.
+    live_occl_mode 'unfilt' (counts over the un-subsampled clouds; needs pcl_input_frames == T) or 'normal' (over the subsampled
+    ones): meta_data gains valo_ids (max_valo_ids, int32, padded with -1), num_valo_ids, live_occl (pcl_input_frames,
+    max_valo_ids) and track_id (occlusion.valo_ids).  track_mode 'none' / 'snitch' / 'random': `track_id` is ignored, the id is
+    chosen as the reference's loader does (occlusion.choose_track_id; 'random' draws np.random.choice AFTER every other draw of
+    the clip) and stands in meta_data['track_id'].  occl_n_ids: bins of the id histogram (default: len(hue_clusters)).  Either
+    argument costs the clip ONE more device -> host read; with both None nothing changes."""
     return _greater_clip(rgb, flat, depth, cam_RT, cam_K, hue_clusters, other_bounds, min_z, n_points_rnd, n_fps_input,
-                         n_fps_target, pcl_input_frames, pcl_target_frames, src_view, track_id, device, None)
+                         n_fps_target, pcl_input_frames, pcl_target_frames, src_view, track_id, device, None,
+                         live_occl_mode, track_mode, max_valo_ids, occl_n_ids)
 
 
 def _greater_clip(rgb, flat, depth, cam_RT, cam_K, hue_clusters, other_bounds, min_z, n_points_rnd, n_fps_input, n_fps_target,
-                  pcl_input_frames, pcl_target_frames, src_view, track_id, device, stages):
+                  pcl_input_frames, pcl_target_frames, src_view, track_id, device, stages, live_occl_mode=None, track_mode=None,
+                  max_valo_ids=32, occl_n_ids=None):
     """greater_clip; `stages` (private, the stage-by-stage tests): a dict that receives references to the intermediate
     clouds the function builds anyway -- it never changes the work done."""
     if device is None:
@@ -244,6 +263,12 @@ def _greater_clip(rgb, flat, depth, cam_RT, cam_K, hue_clusters, other_bounds, m
     ob = float(other_bounds)
     bounds = (-ob, ob, -ob, ob, float(min_z), ob)
 
+    occl = None
+    if live_occl_mode is not None or track_mode is not None:
+        n_ids = occl_n_ids if occl_n_ids is not None else (1 if clusters is None else max(1, clusters.numel()))
+        occl = occlusion.ClipCounts(live_occl_mode, track_mode, V, T, pcl_input_frames, src_view, False, 0, None, 3, max_valo_ids,
+                                    n_ids, device)
+    keep_frames = occl is not None and live_occl_mode is not None and not occl.unfilt      # ('normal': every subsampled frame)
     meta = dict(cuboid_filter_ratios=[])
     pcl_sizes = np.zeros((V, T), dtype=np.int64)
     all_input, all_target = None, [[None] * V for _ in range(T)]
@@ -252,6 +277,9 @@ def _greater_clip(rgb, flat, depth, cam_RT, cam_K, hue_clusters, other_bounds, m
         rows, target, key = rgbd_rows(depth[v], rgb[v], None if flat is None else flat[v], k_inv[v], rt_inv[v], clusters, bounds,
                                       floor_fix=True, view_idx=v, want_target=True)
         seg = _Segments(key, [(t * H * W, (t + 1) * H * W) for t in range(T)])
+        if occl is not None and occl.unfilt:                      # the kept rows where they lie: frame segments known on the host
+            occl.add_view(v, rows, [t * H * W for t in range(T + 1)], key=key)
+        view_frames = []
         valid = (depth[v] > 0).reshape(T, -1).sum(dim=1).to(torch.int32)
         counts = torch.cat([seg.totals(), valid]).cpu().numpy()                        # the view's ONE device -> host read
         kept, pre_filter = counts[:T], counts[T:]
@@ -268,6 +296,11 @@ def _greater_clip(rgb, flat, depth, cam_RT, cam_K, hue_clusters, other_bounds, m
                 frame_tg = seg.rows(target, t, int(kept[t]))
                 all_target[t][v] = frame_tg if inds is None else _take(frame_tg, inds)
             pcl_sizes[v, t] = int(kept[t]) if inds is None else len(inds)
+            if keep_frames:
+                if frame_in is None:
+                    frame_in = seg.rows(rows, t, int(kept[t]))
+                    frame_in = frame_in if inds is None else _take(frame_in, inds)
+                view_frames.append(frame_in)
             if stages is not None:
                 stages[('kept', v, t)] = int(kept[t])
                 stages[('subsample', v, t)] = inds
@@ -275,25 +308,30 @@ def _greater_clip(rgb, flat, depth, cam_RT, cam_K, hue_clusters, other_bounds, m
                 stages[('frame_target', v, t)] = all_target[t][v]
         if stages is not None:
             stages[('rows', v)], stages[('key', v)] = rows, key
+        if keep_frames:
+            occl.add_view(v, *occlusion._frames(view_frames))
         if v == src_view:
             all_input = view_input
     meta['pcl_sizes'] = pcl_sizes
     pcl_input, sem, pcl_target, tail = _finish(all_input, all_target[first_target:], n_fps_input, n_fps_target, pcl_input_frames,
-                                               pcl_target_frames, 1, track_id, 3)
+                                               pcl_target_frames, 1, track_id, 3, occl=occl)
     meta.update(tail)
     return pcl_input, sem, pcl_target, meta
 
 
 def carla_clip(lidar, sensor_RT, reference_frame=None, correct_origin_ground=True, min_z=-1.0, other_bounds=20.0,
                target_bounds=16.0, cube_mode=4, n_points_rnd=0, n_fps_input=14336, n_fps_target=14336, pcl_input_frames=12,
-               pcl_target_frames=12, oversample_vehped_target=False, track_id=-1, device=None):
+               pcl_target_frames=12, oversample_vehped_target=False, track_id=-1, device=None, live_occl_mode=None,
+               max_valo_ids=256, occl_n_ids=None):
     """Lidar sweeps -> the CARLA clouds on the device.  lidar: list-V of list-T of (N, 9) rows (x, y, z, cosine_angle,
     instance_id, semantic_tag, R, G, B) (numpy or tensors); sensor_RT (T, V, 4, 4): sensor-to-world matrices of the clip's
     frames; reference_frame: index of the clip frame whose forward (view 0) sensor is the common frame, None = every frame's
     own.  Returns (pcl_input (n, 8) = (x, y, z, R, G, B, t, mark_track), pcl_input_sem (n, 3) = (cosine_angle, instance_id,
     semantic_tag), pcl_target list of (m, 11) = (x, y, z, cosine_angle, instance_id, semantic_tag, view_idx, R, G, B,
     mark_track), meta_data as greater_clip).  The input is view 0 (data/data_carla.py:523-529).  Host reads: the T frame
-    counts once per view, and the kept counts of all target frames after the output cuboid once."""
+    counts once per view, and the kept counts of all target frames after the output cuboid once.
+    live_occl_mode 'unfilt' / 'normal': meta_data gains valo_ids, num_valo_ids and live_occl over the vehicle / pedestrian
+    instances (occlusion.valo_ids; occl_n_ids: bins of the id histogram, default OCC4D_OCCL_MAX_IDS) for ONE more read."""
     V, T = len(lidar), len(lidar[0])
     sensor_RT = _host_f32(sensor_RT)
     assert sensor_RT.shape == (T, V, 4, 4), 'sensor_RT must be (T, V, 4, 4) = %s, got %s' % ((T, V, 4, 4), sensor_RT.shape)
@@ -306,6 +344,11 @@ def carla_clip(lidar, sensor_RT, reference_frame=None, correct_origin_ground=Tru
     z_offset = 1.0 if correct_origin_ground else 0.0            # (the hard-coded sensor height, data/data_carla.py:461-463)
     filter_mode = cube_mode if cube_mode in (1, 2, 3, 4) else 0
 
+    occl = None
+    if live_occl_mode is not None:
+        occl = occlusion.ClipCounts(live_occl_mode, None, V, T, pcl_input_frames, 0, True, 1, 2, 4, max_valo_ids,
+                                    occlusion.MAX_IDS if occl_n_ids is None else occl_n_ids, device)
+    keep_frames = occl is not None and not occl.unfilt
     meta = dict(cuboid_filter_ratios=[])
     pcl_sizes = np.zeros((V, T), dtype=np.int64)
     first_target = T - pcl_target_frames
@@ -329,6 +372,9 @@ def carla_clip(lidar, sensor_RT, reference_frame=None, correct_origin_ground=Tru
                 lidar_rows(sweeps[t], src, inv, z_offset, filter_mode, min_z, other_bounds, out=buf[lo:hi], out_key=key[lo:hi])
                 ops.fill_rows(buf[lo:hi, d:], float(t))
         seg = _Segments(key, [(int(offsets[t]), int(offsets[t + 1])) for t in range(T)])
+        if occl is not None and occl.unfilt:
+            occl.add_view(v, buf, offsets, key=key)
+        view_frames = []
         kept = seg.totals().cpu().numpy()                                              # the view's ONE device -> host read
         for t in range(T):
             n_t = int(offsets[t + 1] - offsets[t])
@@ -337,13 +383,17 @@ def carla_clip(lidar, sensor_RT, reference_frame=None, correct_origin_ground=Tru
             pcl_sizes[v, t] = int(kept[t]) if inds is None else len(inds)
             need_in, need_tg = v == 0 and t < pcl_input_frames, t >= first_target
             frame = None
-            if need_in or need_tg:
+            if need_in or need_tg or keep_frames:
                 frame = seg.rows(buf, t, int(kept[t]))
                 frame = frame if inds is None else _take(frame, inds)
+            if keep_frames:
+                view_frames.append(frame)
             if need_in:
                 all_input.append(frame)
             if need_tg:                                                                # merge_pcl_views_numpy(insert_view_idx)
                 all_target[t][v] = torch.cat([frame[:, :d - 3], torch.full_like(frame[:, :1], float(v)), frame[:, d - 3:d]], dim=1)
+        if keep_frames:
+            occl.add_view(v, *occlusion._frames(view_frames))
     meta['pcl_sizes'] = pcl_sizes
 
     def output_cuboid(frame):              # filter_pcl_bounds_carla_output_torch(padding = 2) as a keep key for the compaction
@@ -358,6 +408,6 @@ def carla_clip(lidar, sensor_RT, reference_frame=None, correct_origin_ground=Tru
     pcl_input, sem, pcl_target, tail = _finish(all_input, all_target[first_target:], n_fps_input, n_fps_target, pcl_input_frames,
                                                pcl_target_frames, n_sem, track_id, 4,
                                                target_filter=output_cuboid if cube_mode in geometry._CARLA_OUTPUT_SCALE else None,
-                                               retain_vehped=oversample_vehped_target, segm_idx=5)
+                                               retain_vehped=oversample_vehped_target, segm_idx=5, occl=occl)
     meta.update(tail)
     return pcl_input, sem, pcl_target, meta

@@ -8,6 +8,7 @@ import os
 
 import warnings
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1229,6 +1230,42 @@ def eval_target_stats(dist, counts, sums, *, n_groups=1, n_classes=0, target_gro
     c, s, grp, ws = _eval_arrays(counts, sums, target_group, d.shape[0], n_groups, n_classes, d.shape[0])
     _lib.check(_lib.lib().occ4d_eval_target_stats_f32(_ptr(d), d.shape[0], _ptr(grp), int(n_groups), int(n_classes), _ptr(c), _ptr(s),
                                                       _ptr(ws), _stream()))
+
+
+def id_histogram(rows, col, seg_offsets, n_ids, key=None, pred_col=-1, pred_values=(), out=None):
+    """Segmented histogram of the ids in column `col` of rows (n, d): -> (S, n_ids + 2) int32 on the device, ADDED onto `out`
+    when given (occ4d_id_histogram_f32, include/occ4d_occl.h).  seg_offsets: S + 1 ascending row offsets from 0 to n -- a host
+    sequence (checked here, then uploaded) or an int64 device tensor (used as it is).  Bin i: values == i; bin n_ids: values
+    < 0; bin n_ids + 1: everything else.  key (n): only rows with key > 0.5 count; pred_col / pred_values (one or two values):
+    only rows whose column pred_col equals one of them count.  No host read."""
+    r, ld = _rows(_dev(rows, name='rows'), 'rows')
+    n = r.shape[0]
+    if isinstance(seg_offsets, torch.Tensor):
+        off = _dev(seg_offsets, torch.int64, 'seg_offsets')
+        assert off.dim() == 1 and off.numel() >= 1 and off.is_contiguous(), 'seg_offsets must be a contiguous (S + 1) tensor'
+    else:
+        host = np.asarray(seg_offsets, dtype=np.int64).reshape(-1)
+        assert host.size >= 1 and host[0] == 0 and host[-1] == n and bool((np.diff(host) >= 0).all()), \
+            'seg_offsets must ascend from 0 to n = %d, got %s' % (n, host.tolist())
+        off = torch.from_numpy(host).to(r.device)
+    S = off.numel() - 1
+    bins = int(n_ids) + _lib.OCCL_CONSTANTS['EXTRA_BINS']
+    assert 1 <= int(n_ids) <= _lib.OCCL_CONSTANTS['MAX_IDS'], 'n_ids = %s must be in 1 .. %d' % (n_ids, _lib.OCCL_CONSTANTS['MAX_IDS'])
+    if out is None:
+        out = torch.zeros((S, bins), dtype=torch.int32, device=r.device)
+    o = _dev(out, torch.int32, 'out')
+    assert tuple(o.shape) == (S, bins) and o.is_contiguous(), 'out must be a contiguous (%d, %d) int32 tensor' % (S, bins)
+    k = None
+    if key is not None:
+        k = _dev(key, name='key')
+        assert tuple(k.shape) == (n,), 'key must be (n,)'
+        k = k.contiguous()
+    vals = tuple(float(v) for v in pred_values)
+    assert len(vals) <= 2 and (int(pred_col) < 0) == (len(vals) == 0), 'a predicate needs pred_col >= 0 and one or two pred_values'
+    pa, pb = (vals[0], vals[-1]) if vals else (0.0, 0.0)
+    _lib.check(_lib.lib().occ4d_id_histogram_f32(_ptr(r), ld, n, int(col), _ptr(off), S, int(n_ids), _ptr(k),
+                                                 int(pred_col) if vals else -1, pa, pb, _ptr(o), _stream()))
+    return out
 
 
 def add_rows(a, b):
