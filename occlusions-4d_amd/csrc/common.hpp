@@ -29,6 +29,41 @@ inline int check_launch(const char* what) {
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// Argument contract of the row-resident trunk launchers (csrc/trunk.hip: TrunkArgs; csrc/trunk4.hip: Trunk4Args): `who` is
+// the entry point the error text names, `width` the row width the kernels are built for.
+template <class Args>
+int check_trunk_args(const Args& a, const char* who, int width) {
+  OCC4D_REQUIRE(a.x && a.y && a.w0p && a.b0, "%s: null pointer", who);
+  OCC4D_REQUIRE(a.n >= 0, "%s: n = %d", who, a.n);
+  OCC4D_REQUIRE(a.ldx >= width && a.ldx % 4 == 0 && a.ldy % 4 == 0 && ((uintptr_t)a.x % 16) == 0 &&
+                    ((uintptr_t)a.y % 16) == 0 && ((uintptr_t)a.w0p % 16) == 0 && ((uintptr_t)a.b0 % 16) == 0,
+                "%s: x / y / weights / bias must be 16-byte aligned with row strides %% 4 == 0 (ldx >= %d)", who, width);
+  if (a.ztab) {
+    OCC4D_REQUIRE(a.zconst && a.zidx && a.zw && a.kz >= 1 && a.ldz % 4 == 0 && ((uintptr_t)a.ztab % 16) == 0 &&
+                      ((uintptr_t)a.zconst % 16) == 0,
+                  "%s: interpolation term needs zconst / zidx / zw, kz >= 1 and a 16-byte aligned table", who);
+  }
+  return OCC4D_OK;
+}
+
+// ... and what the rowlin entry points add to it: n_out a multiple of the kernel's `stage` outputs, the residual rows
+// (`skip`: the rows added after the mask, which that entry point requires) and, when `masked`, the mask rows.
+template <class Args>
+int check_rowlin_args(const Args& a, const char* who, int width, int stage, int n_out, bool masked, bool skip = false) {
+  if (int rc = check_trunk_args(a, who, width)) return rc;
+  OCC4D_REQUIRE(n_out >= stage && n_out % stage == 0 && a.ldy >= n_out, "%s: n_out = %d must be a multiple of %d <= ldy", who,
+                n_out, stage);
+  const bool res_ok = a.ldr % 4 == 0 && ((uintptr_t)a.res % 16) == 0 && a.ldr >= n_out;
+  if (skip) {
+    OCC4D_REQUIRE(a.res && res_ok, "%s: skip rows must be 16-byte aligned with lds %% 4 == 0 and lds >= n_out", who);
+  } else {
+    OCC4D_REQUIRE(!a.res || res_ok, "%s: residual rows must be 16-byte aligned with ldr %% 4 == 0", who);
+  }
+  OCC4D_REQUIRE(!masked || (a.mask && a.ldm % 4 == 0 && ((uintptr_t)a.mask % 16) == 0 && a.ldm >= n_out),
+                "%s: mask rows must be 16-byte aligned with ldm %% 4 == 0 and ldm >= n_out", who);
+  return OCC4D_OK;
+}
+
 // fps_bucket.hip: the pruned single-workgroup FPS (FPS_BUCKET_MIN_POINTS <= n <= 16384); -1 = n outside that range.
 // Since a round of the pruned kernel accepts several samples (round 3) it also wins on the small encoder levels, whose
 // step is bound by the serial argmax chain (profiles/time_fps.py, pruned vs exhaustive: 9558 points 1.84 vs 3.54 ms,

@@ -313,18 +313,17 @@ __global__ __launch_bounds__(512, 2) void rowlin_kernel(const TrunkArgs a) {
   }
 }
 
-int check_common(const TrunkArgs& a, const char* who) {
-  OCC4D_REQUIRE(a.x && a.y && a.w0p && a.b0, "%s: null pointer", who);
-  OCC4D_REQUIRE(a.n >= 0, "%s: n = %d", who, a.n);
-  OCC4D_REQUIRE(a.ldx >= TH && a.ldx % 4 == 0 && a.ldy % 4 == 0 && ((uintptr_t)a.x % 16) == 0 &&
-                    ((uintptr_t)a.y % 16) == 0 && ((uintptr_t)a.w0p % 16) == 0 && ((uintptr_t)a.b0 % 16) == 0,
-                "%s: x / y / weights / bias must be 16-byte aligned with row strides %% 4 == 0 (ldx >= %d)", who, TH);
-  if (a.ztab) {
-    OCC4D_REQUIRE(a.zconst && a.zidx && a.zw && a.kz >= 1 && a.ldz % 4 == 0 && ((uintptr_t)a.ztab % 16) == 0 &&
-                      ((uintptr_t)a.zconst % 16) == 0,
-                  "%s: interpolation term needs zconst / zidx / zw, kz >= 1 and a 16-byte aligned table", who);
-  }
-  return OCC4D_OK;
+// Host side of the two rowlin entry points: the struct, the argument checks (`masked`: a mask is required) and the launch.
+int rowlin_launch(const char* who, const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed, const float* b,
+                  int n_out, int relu_in, const float* res, int64_t ldr, const float* zconst, const float* ztab, int64_t ldz,
+                  const int32_t* zidx, const float* zw, int kz, bool masked, const float* mask, int64_t ldm, int n,
+                  void* stream) {
+  if (n == 0) return OCC4D_OK;               // (an empty batch has no storage: nothing to check)
+  TrunkArgs a{x, ldx, y, ldy, w_packed, b, nullptr, nullptr, res, ldr, zconst, ztab, ldz, zidx, zw, kz, n,
+              n_out / 32, relu_in, mask, ldm};
+  if (int rc = occ4d::check_rowlin_args(a, who, TH, 32, n_out, masked)) return rc;
+  rowlin_kernel<<<occ4d::cdiv(n, TROWS), 512, 0, (hipStream_t)stream>>>(a);
+  return occ4d::check_launch(who);
 }
 
 }  // namespace
@@ -338,33 +337,19 @@ extern "C" int occ4d_resblock_f32(const float* x, int64_t ldx, float* y, int64_t
                                   void* stream) {
   TrunkArgs a{x, ldx, y, ldy, w0_packed, b0, w1_packed, b1, nullptr, 0, zconst, ztab, ldz, zidx, zw, kz, n, TNS, 1, nullptr, 0};
   if (n == 0) return OCC4D_OK;               // (an empty batch has no storage: nothing to check)
-  if (int rc = check_common(a, "occ4d_resblock_f32")) return rc;
+  if (int rc = occ4d::check_trunk_args(a, "occ4d_resblock_f32", TH)) return rc;
   OCC4D_REQUIRE(w1_packed && b1 && ((uintptr_t)w1_packed % 16) == 0 && ((uintptr_t)b1 % 16) == 0 && ldy >= TH,
                 "occ4d_resblock_f32: second layer weights / bias missing or misaligned");
-  if (n == 0) return OCC4D_OK;
   resblock_kernel<<<occ4d::cdiv(n, TROWS), 512, 0, (hipStream_t)stream>>>(a);
   return occ4d::check_launch("occ4d_resblock_f32");
 }
-
-extern "C" int occ4d_rowlin_masked_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed,
-                                       const float* b, int n_out, int relu_in, const float* res, int64_t ldr,
-                                       const float* mask, int64_t ldm, int n, void* stream);
 
 extern "C" int occ4d_rowlin_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed,
                                 const float* b, int n_out, int relu_in, const float* res, int64_t ldr,
                                 const float* zconst, const float* ztab, int64_t ldz, const int32_t* zidx,
                                 const float* zw, int kz, int n, void* stream) {
-  TrunkArgs a{x, ldx, y, ldy, w_packed, b, nullptr, nullptr, res, ldr, zconst, ztab, ldz, zidx, zw, kz, n,
-              n_out / 32, relu_in, nullptr, 0};
-  if (n == 0) return OCC4D_OK;
-  if (int rc = check_common(a, "occ4d_rowlin_f32")) return rc;
-  OCC4D_REQUIRE(n_out >= 32 && n_out % 32 == 0 && ldy >= n_out, "occ4d_rowlin_f32: n_out = %d must be a multiple of 32 <= ldy",
-                n_out);
-  OCC4D_REQUIRE(!res || (ldr % 4 == 0 && ((uintptr_t)res % 16) == 0 && ldr >= n_out),
-                "occ4d_rowlin_f32: residual rows must be 16-byte aligned with ldr %% 4 == 0");
-  if (n == 0) return OCC4D_OK;
-  rowlin_kernel<<<occ4d::cdiv(n, TROWS), 512, 0, (hipStream_t)stream>>>(a);
-  return occ4d::check_launch("occ4d_rowlin_f32");
+  return rowlin_launch("occ4d_rowlin_f32", x, ldx, y, ldy, w_packed, b, n_out, relu_in, res, ldr, zconst, ztab, ldz, zidx, zw,
+                       kz, false, nullptr, 0, n, stream);
 }
 
 // y = mask > 0 ? ([res +] W [relu](x) + b) : 0 -- occ4d_rowlin_f32 with the ReLU mask of a data gradient applied in
@@ -372,16 +357,6 @@ extern "C" int occ4d_rowlin_f32(const float* x, int64_t ldx, float* y, int64_t l
 extern "C" int occ4d_rowlin_masked_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed,
                                        const float* b, int n_out, int relu_in, const float* res, int64_t ldr,
                                        const float* mask, int64_t ldm, int n, void* stream) {
-  TrunkArgs a{x, ldx, y, ldy, w_packed, b, nullptr, nullptr, res, ldr, nullptr, nullptr, 0, nullptr, nullptr, 0, n,
-              n_out / 32, relu_in, mask, ldm};
-  if (n == 0) return OCC4D_OK;
-  if (int rc = check_common(a, "occ4d_rowlin_masked_f32")) return rc;
-  OCC4D_REQUIRE(n_out >= 32 && n_out % 32 == 0 && ldy >= n_out, "occ4d_rowlin_masked_f32: n_out = %d must be a multiple of 32 <= ldy",
-                n_out);
-  OCC4D_REQUIRE(!res || (ldr % 4 == 0 && ((uintptr_t)res % 16) == 0 && ldr >= n_out),
-                "occ4d_rowlin_masked_f32: residual rows must be 16-byte aligned with ldr %% 4 == 0");
-  OCC4D_REQUIRE(mask && ldm % 4 == 0 && ((uintptr_t)mask % 16) == 0 && ldm >= n_out,
-                "occ4d_rowlin_masked_f32: mask rows must be 16-byte aligned with ldm %% 4 == 0 and ldm >= n_out");
-  rowlin_kernel<<<occ4d::cdiv(n, TROWS), 512, 0, (hipStream_t)stream>>>(a);
-  return occ4d::check_launch("occ4d_rowlin_masked_f32");
+  return rowlin_launch("occ4d_rowlin_masked_f32", x, ldx, y, ldy, w_packed, b, n_out, relu_in, res, ldr, nullptr, nullptr, 0,
+                       nullptr, nullptr, 0, true, mask, ldm, n, stream);
 }

@@ -292,20 +292,6 @@ __global__ __launch_bounds__(256, 2) void rowlin4_kernel(const Trunk4Args a) {
   }
 }
 
-int check_common4(const Trunk4Args& a, const char* who) {
-  OCC4D_REQUIRE(a.x && a.y && a.w0p && a.b0, "%s: null pointer", who);
-  OCC4D_REQUIRE(a.n >= 0, "%s: n = %d", who, a.n);
-  OCC4D_REQUIRE(a.ldx >= QH && a.ldx % 4 == 0 && a.ldy % 4 == 0 && ((uintptr_t)a.x % 16) == 0 &&
-                    ((uintptr_t)a.y % 16) == 0 && ((uintptr_t)a.w0p % 16) == 0 && ((uintptr_t)a.b0 % 16) == 0,
-                "%s: x / y / weights / bias must be 16-byte aligned with row strides %% 4 == 0 (ldx >= %d)", who, QH);
-  if (a.ztab) {
-    OCC4D_REQUIRE(a.zconst && a.zidx && a.zw && a.kz >= 1 && a.ldz % 4 == 0 && ((uintptr_t)a.ztab % 16) == 0 &&
-                      ((uintptr_t)a.zconst % 16) == 0,
-                  "%s: interpolation term needs zconst / zidx / zw, kz >= 1 and a 16-byte aligned table", who);
-  }
-  return OCC4D_OK;
-}
-
 }  // namespace
 
 extern "C" int64_t occ4d_trunk4_packed_floats(int n_out) { return (int64_t)(n_out / 16 + 1) * QSTAGE; }
@@ -316,7 +302,7 @@ extern "C" int occ4d_resblock4_f32(const float* x, int64_t ldx, float* y, int64_
                                    void* stream) {
   Trunk4Args a{x, ldx, y, ldy, w0_packed, b0, w1_packed, b1, nullptr, 0, zconst, ztab, ldz, zidx, zw, kz, n, QNC, 1};
   if (n == 0) return OCC4D_OK;               // (an empty batch has no storage: nothing to check)
-  if (int rc = check_common4(a, "occ4d_resblock4_f32")) return rc;
+  if (int rc = occ4d::check_trunk_args(a, "occ4d_resblock4_f32", QH)) return rc;
   OCC4D_REQUIRE(w1_packed && b1 && ((uintptr_t)w1_packed % 16) == 0 && ((uintptr_t)b1 % 16) == 0 && ldy >= QH,
                 "occ4d_resblock4_f32: second layer weights / bias missing or misaligned");
   resblock4_kernel<<<occ4d::cdiv(n, QROWS), 256, 0, (hipStream_t)stream>>>(a);
@@ -338,40 +324,36 @@ static int rowlin4_grid(Trunk4Args& a) {
   return a.full_tiles + tail * a.tail_parts;
 }
 
+// Host side of the three rowlin4 entry points: the struct, the argument checks (`masked`: a mask is required; `res_post`:
+// `res` holds the skip rows, required, added after the mask) and the launch.
+static int rowlin4_launch(const char* who, const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed,
+                          const float* b, int n_out, int relu_in, const float* res, int64_t ldr, const float* zconst,
+                          const float* ztab, int64_t ldz, const int32_t* zidx, const float* zw, int kz, bool masked,
+                          const float* mask, int64_t ldm, int res_post, int n, void* stream) {
+  if (n == 0) return OCC4D_OK;
+  Trunk4Args a{x, ldx, y, ldy, w_packed, b, nullptr, nullptr, res, ldr, zconst, ztab, ldz, zidx, zw, kz, n,
+               n_out / 16, relu_in, mask, ldm};
+  a.res_post = res_post;
+  if (int rc = occ4d::check_rowlin_args(a, who, QH, 16, n_out, masked, res_post != 0)) return rc;
+  const int grid = rowlin4_grid(a);
+  rowlin4_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
+  return occ4d::check_launch(who);
+}
+
 extern "C" int occ4d_rowlin4_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed,
                                  const float* b, int n_out, int relu_in, const float* res, int64_t ldr,
                                  const float* zconst, const float* ztab, int64_t ldz, const int32_t* zidx,
                                  const float* zw, int kz, int n, void* stream) {
-  Trunk4Args a{x, ldx, y, ldy, w_packed, b, nullptr, nullptr, res, ldr, zconst, ztab, ldz, zidx, zw, kz, n,
-               n_out / 16, relu_in, nullptr, 0};
-  if (n == 0) return OCC4D_OK;
-  if (int rc = check_common4(a, "occ4d_rowlin4_f32")) return rc;
-  OCC4D_REQUIRE(n_out >= 16 && n_out % 16 == 0 && ldy >= n_out, "occ4d_rowlin4_f32: n_out = %d must be a multiple of 16 <= ldy",
-                n_out);
-  OCC4D_REQUIRE(!res || (ldr % 4 == 0 && ((uintptr_t)res % 16) == 0 && ldr >= n_out),
-                "occ4d_rowlin4_f32: residual rows must be 16-byte aligned with ldr %% 4 == 0");
-  const int grid = rowlin4_grid(a);
-  rowlin4_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
-  return occ4d::check_launch("occ4d_rowlin4_f32");
+  return rowlin4_launch("occ4d_rowlin4_f32", x, ldx, y, ldy, w_packed, b, n_out, relu_in, res, ldr, zconst, ztab, ldz, zidx,
+                        zw, kz, false, nullptr, 0, 0, n, stream);
 }
 
 // occ4d_rowlin4_f32 with an output mask (the contract of occ4d_rowlin_masked_f32)
 extern "C" int occ4d_rowlin4_masked_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed,
                                         const float* b, int n_out, int relu_in, const float* res, int64_t ldr,
                                         const float* mask, int64_t ldm, int n, void* stream) {
-  Trunk4Args a{x, ldx, y, ldy, w_packed, b, nullptr, nullptr, res, ldr, nullptr, nullptr, 0, nullptr, nullptr, 0, n,
-               n_out / 16, relu_in, mask, ldm};
-  if (n == 0) return OCC4D_OK;
-  if (int rc = check_common4(a, "occ4d_rowlin4_masked_f32")) return rc;
-  OCC4D_REQUIRE(n_out >= 16 && n_out % 16 == 0 && ldy >= n_out,
-                "occ4d_rowlin4_masked_f32: n_out = %d must be a multiple of 16 <= ldy", n_out);
-  OCC4D_REQUIRE(!res || (ldr % 4 == 0 && ((uintptr_t)res % 16) == 0 && ldr >= n_out),
-                "occ4d_rowlin4_masked_f32: residual rows must be 16-byte aligned with ldr %% 4 == 0");
-  OCC4D_REQUIRE(mask && ldm % 4 == 0 && ((uintptr_t)mask % 16) == 0 && ldm >= n_out,
-                "occ4d_rowlin4_masked_f32: mask rows must be 16-byte aligned with ldm %% 4 == 0 and ldm >= n_out");
-  const int grid = rowlin4_grid(a);
-  rowlin4_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
-  return occ4d::check_launch("occ4d_rowlin4_masked_f32");
+  return rowlin4_launch("occ4d_rowlin4_masked_f32", x, ldx, y, ldy, w_packed, b, n_out, relu_in, res, ldr, nullptr, nullptr,
+                        0, nullptr, nullptr, 0, true, mask, ldm, 0, n, stream);
 }
 
 // Data gradient of a residual block's first layer with the skip gradient folded in:
@@ -380,18 +362,6 @@ extern "C" int occ4d_rowlin4_masked_f32(const float* x, int64_t ldx, float* y, i
 extern "C" int occ4d_rowlin4_masked_skip_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed,
                                              const float* b, int n_out, int relu_in, const float* skip, int64_t lds,
                                              const float* mask, int64_t ldm, int n, void* stream) {
-  Trunk4Args a{x, ldx, y, ldy, w_packed, b, nullptr, nullptr, skip, lds, nullptr, nullptr, 0, nullptr, nullptr, 0, n,
-               n_out / 16, relu_in, mask, ldm};
-  a.res_post = 1;
-  if (n == 0) return OCC4D_OK;
-  if (int rc = check_common4(a, "occ4d_rowlin4_masked_skip_f32")) return rc;
-  OCC4D_REQUIRE(n_out >= 16 && n_out % 16 == 0 && ldy >= n_out,
-                "occ4d_rowlin4_masked_skip_f32: n_out = %d must be a multiple of 16 <= ldy", n_out);
-  OCC4D_REQUIRE(skip && lds % 4 == 0 && ((uintptr_t)skip % 16) == 0 && lds >= n_out,
-                "occ4d_rowlin4_masked_skip_f32: skip rows must be 16-byte aligned with lds %% 4 == 0 and lds >= n_out");
-  OCC4D_REQUIRE(mask && ldm % 4 == 0 && ((uintptr_t)mask % 16) == 0 && ldm >= n_out,
-                "occ4d_rowlin4_masked_skip_f32: mask rows must be 16-byte aligned with ldm %% 4 == 0 and ldm >= n_out");
-  const int grid = rowlin4_grid(a);
-  rowlin4_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
-  return occ4d::check_launch("occ4d_rowlin4_masked_skip_f32");
+  return rowlin4_launch("occ4d_rowlin4_masked_skip_f32", x, ldx, y, ldy, w_packed, b, n_out, relu_in, skip, lds, nullptr,
+                        nullptr, 0, nullptr, nullptr, 0, true, mask, ldm, 1, n, stream);
 }

@@ -428,7 +428,8 @@ int occ4d_compact_count_f32(const float* key, int64_t ld, int n, float threshold
 }
 int occ4d_compact_rows_f32(const float* src, int64_t ld, int n, int d, const float* key, int64_t ld_key, float threshold,
                            int strict, const int* block_offsets, float* out_rows, float* out_key, void*) {
-  REQ(src && key && block_offsets && out_rows && n >= 0 && d >= 1 && ld >= d && ld_key >= 1, "occ4d_compact_rows_f32: bad arguments");
+  // (out_rows may be null when no row is kept -- an empty torch tensor has no storage --, as in csrc/postops.hip)
+  REQ(src && key && block_offsets && n >= 0 && d >= 1 && ld >= d && ld_key >= 1, "occ4d_compact_rows_f32: bad arguments");
   int64_t kept = 0;
   for (int i = 0; i < n; ++i) {
     const float kv = key[(int64_t)i * ld_key];

@@ -3,6 +3,7 @@ int32 torch tensors, launches on torch's current stream and returns torch tensor
 torch is plumbing here (device memory + streams); all arithmetic happens in
 libocc4d.so.  CPU tensors are rejected -- there is no fallback path."""
 import ctypes as C
+import functools
 import math
 import os
 
@@ -119,6 +120,39 @@ def _aligned_rows(t, name, k_pad=None):
         if t.data_ptr() % 16:
             t = t.clone()
     return t, ld
+
+
+def _out(out, shape, device, dtype=torch.float32, name='out'):
+    """The 2-D output of a launch -> (tensor, row stride in elements): allocated when `out` is None; a caller's `out` is
+    adopted as it is -- it must be on the library's device kind, of `dtype`, exactly `shape`, with a contiguous last
+    dimension (a copy made behind the caller's back would swallow the result)."""
+    if out is None:
+        return _rows(torch.empty(shape, dtype=dtype, device=device), name)
+    o, ld = _rows(_dev(out, dtype, name), name)
+    assert o is out and tuple(o.shape) == tuple(shape), \
+        '%s must be a %s tensor with unit column stride, got %s with strides %s' % (name, tuple(shape), tuple(out.shape), out.stride())
+    return o, ld
+
+
+def _sized(query_fn, *args, dtype=torch.float32, device):
+    """1-D buffer of the element count a `*_floats` / `*_workspace_*` query of the library returns for `args`; a negative
+    count (the query rejected its arguments) raises the library's EINVAL error."""
+    n = int(query_fn(*args))
+    if n < 0:
+        _lib.check(_lib.EINVAL)
+    return torch.empty((n,), dtype=dtype, device=device)
+
+
+@functools.lru_cache(maxsize=None)
+def _divisor(d):
+    """sqrt(d) rounded to fp32, as a Python float: the softmax divisor of the attention kernels."""
+    return float(np.float32(math.sqrt(d)))
+
+
+def _attn_flops(c, k, d, gemm2=True):
+    """Useful (unpadded) FLOPs of a fused attention launch over c rows: per pair Wp (32 x 2d) + W2 (2d x d; gemm2=False: the
+    launch that skips it) + P2 (32 x d)."""
+    return 2.0 * c * k * (32 * 2 * d + (2 * d * d if gemm2 else 0) + 32 * d)
 
 
 # --------------------------------------------------------------------------------------
@@ -278,10 +312,7 @@ def linear(x, w, b=None, relu_in=False, relu_out=False, residual=None, out=None,
     w, ldw = _aligned_rows(_dev(w, name='w'), 'w', k4)
     M, K = x.shape
     N = w.shape[0]
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    y, ldy = _rows(_dev(out, name='out'), 'out')
-    assert y is out and y.shape == (M, N)
+    out, ldy = _out(out, (M, N), x.device)
     a = _lib.LinearArgs()
     a.x, a.ldx, a.w, a.ldw = x.data_ptr(), ldx, w.data_ptr(), ldw
     a.bias = _dev(b, name='bias').data_ptr() if b is not None else None
@@ -291,7 +322,7 @@ def linear(x, w, b=None, relu_in=False, relu_out=False, residual=None, out=None,
         r, ldr = _rows(_dev(residual, name='residual'), 'residual')
         assert r.shape == (M, N)
         a.residual, a.ldr = r.data_ptr(), ldr
-    a.y, a.ldy = y.data_ptr(), ldy
+    a.y, a.ldy = out.data_ptr(), ldy
     a.M, a.K, a.N = M, K, N
     a.relu_in, a.relu_out = int(relu_in), int(relu_out)
     if add_rows is not None:
@@ -346,13 +377,9 @@ def pt_softmax_agg(logits, v, pe, idx, out=None):
     v, ldv = _rows(_dev(v, name='v'), 'v')
     if pe is not None:
         assert pe.is_contiguous() and pe.shape == (n * k, d)
-    if out is None:
-        out = torch.empty((n, d), dtype=torch.float32, device=logits.device)
-    o, ldo = _rows(out, 'out')
-    assert o is out
-    divisor = float(torch.tensor(math.sqrt(d), dtype=torch.float32))
+    out, ldo = _out(out, (n, d), logits.device)
     _lib.check(_lib.lib().occ4d_pt_softmax_agg_f32(_ptr(logits), _ptr(v), ldv, _ptr(pe),
-                                                   _ptr(_dev(idx, torch.int32)), n, k, d, divisor, _ptr(o), ldo,
+                                                   _ptr(_dev(idx, torch.int32)), n, k, d, _divisor(d), _ptr(out), ldo,
                                                    _stream()))
     return out
 
@@ -389,7 +416,7 @@ def pack_rowlin_bf16x6(w, scheme='bf16x6'):
     L = _lib.lib()
     size, pack = ((L.occ4d_rowlin_f16x3_packed_floats, L.occ4d_pack_rowlin_f16x3_f32) if scheme == 'f16x3' else
                   (L.occ4d_rowlin_bf16x6_packed_floats, L.occ4d_pack_rowlin_bf16x6_f32))
-    packed = torch.empty((int(size(n_out)),), dtype=torch.float32, device=w.device)
+    packed = _sized(size, n_out, device=w.device)
     _lib.check(pack(_ptr(w), ldw, n_out, _ptr(packed), _stream()))
     return packed
 
@@ -408,23 +435,18 @@ def rowlin_bf16x6(x, w, b=None, relu_in=False, res=None, out=None, packed=None, 
         packed, n_out = pack_rowlin_bf16x6(w, scheme), w.shape[0]
     assert x.shape[1] == 416 and n_out in X6_ROWLIN_WIDTHS
     L = _lib.lib()
-    if out is None:
-        out = torch.empty((n, n_out), dtype=torch.float32, device=x.device)
+    out, ldo = _out(out, (n, n_out), x.device)
     ldr = 0
     if res is not None:
         res, ldr = _rows(_dev(res, name='res'), 'res')
     bb = _cont(b, 'bias') if b is not None else None
-    flops = 2.0 * n * 416 * n_out
+    args = (_ptr(x), ldx, _ptr(out), ldo, _ptr(packed), _ptr(bb), n_out, int(relu_in), _ptr(res), ldr)
+    fn = L.occ4d_rowlin_f16x3_f32 if scheme == 'f16x3' else L.occ4d_rowlin_bf16x6_f32
     if mask is not None:
         mm, ldm = _rows(_dev(mask, name='mask'), 'mask')
         assert mm.shape == (n, n_out)
-        _lib.check(_launch('rowlin', dict(n=n, n_out=n_out), flops, lambda: L.occ4d_rowlin_bf16x6_masked_f32(
-            _ptr(x), ldx, _ptr(out), out.stride(0), _ptr(packed), _ptr(bb), n_out, int(relu_in), _ptr(res), ldr,
-            int(res_after_mask), _ptr(mm), ldm, n, _stream())))
-        return out
-    fn = L.occ4d_rowlin_f16x3_f32 if scheme == 'f16x3' else L.occ4d_rowlin_bf16x6_f32
-    _lib.check(_launch('rowlin', dict(n=n, n_out=n_out), flops, lambda: fn(
-        _ptr(x), ldx, _ptr(out), out.stride(0), _ptr(packed), _ptr(bb), n_out, int(relu_in), _ptr(res), ldr, n, _stream())))
+        fn, args = L.occ4d_rowlin_bf16x6_masked_f32, args + (int(res_after_mask), _ptr(mm), ldm)
+    _lib.check(_launch('rowlin', dict(n=n, n_out=n_out), 2.0 * n * 416 * n_out, lambda: fn(*args, n, _stream())))
     return out
 
 
@@ -437,7 +459,7 @@ def implicit_loss_fused(out, target, semantic_classes, density_lw, segmentation_
     cells, n, g = out.shape
     assert tuple(target.shape[:2]) == (cells, n) and target.shape[2] >= 2
     L = _lib.lib()
-    ws = torch.empty((int(L.occ4d_implicit_loss_workspace_floats(cells)),), dtype=torch.float32, device=out.device)
+    ws = _sized(L.occ4d_implicit_loss_workspace_floats, cells, device=out.device)
     loss = torch.empty((1,), dtype=torch.float32, device=out.device)
     grad = torch.empty_like(out) if want_grad else None
     _lib.check(L.occ4d_implicit_loss_f32(_ptr(out), g, _ptr(target), target.shape[2], cells, n, g, target.shape[2] - 1,
@@ -460,7 +482,7 @@ def implicit_loss_terms_fused(out, target, color_mode, semantic_classes, density
     cells, n, g = out.shape
     assert tuple(target.shape) == (cells, n, 6), 'target (cells, n, 6) = (density, R, G, B, mark_track, segm)'
     L = _lib.lib()
-    ws = torch.empty((int(L.occ4d_implicit_loss_terms_workspace_floats(cells)),), dtype=torch.float32, device=out.device)
+    ws = _sized(L.occ4d_implicit_loss_terms_workspace_floats, cells, device=out.device)
     scalars = torch.empty((5,), dtype=torch.float32, device=out.device)
     loss, terms = scalars[:1], scalars[1:]
     grad = torch.empty_like(out) if want_grad else None
@@ -481,24 +503,21 @@ def resblock_f16x3(x, w0, b0, w1, b1, out=None, packed=None):
     if packed is None:
         w0, w1 = (_cont(t.detach(), 'w') for t in (w0, w1))
         assert tuple(w0.shape) == (d, d) and tuple(w1.shape) == (d, d)
-        packed = torch.empty((int(L.occ4d_resblock_f16x3_packed_floats()),), dtype=torch.float32, device=x.device)
+        packed = _sized(L.occ4d_resblock_f16x3_packed_floats, device=x.device)
         _lib.check(L.occ4d_pack_resblock_f16x3_f32(_ptr(w0), d, _ptr(w1), d, _ptr(packed), _stream()))
     b0, b1 = (_cont(t.detach(), 'b') for t in (b0, b1))
-    if out is None:
-        out = torch.empty((n, d), dtype=torch.float32, device=x.device)
-    o, ldo = _aligned_rows(_dev(out, name='out'), 'out')
-    assert o is out and tuple(o.shape) == (n, d)
-    flops = 2.0 * 2.0 * n * d * d
-    _lib.check(_launch('resblock', dict(n=n), flops, lambda: L.occ4d_resblock_f16x3_f32(
-        _ptr(x), ldx, _ptr(o), ldo, _ptr(packed), _ptr(b0), _ptr(b1), n, _stream())))
+    out, ldo = _out(out, (n, d), x.device)
+    assert out.data_ptr() % 16 == 0 and ldo % 4 == 0, 'out must be 16-byte aligned with a row stride % 4 == 0'
+    _lib.check(_launch('resblock', dict(n=n), 4.0 * n * d * d, lambda: L.occ4d_resblock_f16x3_f32(
+        _ptr(x), ldx, _ptr(out), ldo, _ptr(packed), _ptr(b0), _ptr(b1), n, _stream())))
     return out
 
 
 def _attn_operands(aq, qpos, apos, idx, kt, vt, out):
     """What the fused attention wrappers do alike: aq / kt as aligned rows, idx (n, k) int32 contiguous, the shape checks, the
-    output rows, the fp32 sqrt(d) divisor and the launch's FLOPs (useful, unpadded): per pair Wp (32 x 2d) + W2 (2d x d) +
-    P2 (32 x d).  -> (the entry points' eleven leading arguments aq .. ld_vt, the tensors behind them -- the caller keeps them
-    alive until the launch --, out, its row stride, n, m, k, d, divisor, flops)."""
+    output rows, the fp32 sqrt(d) divisor and the launch's FLOPs (_attn_flops).  -> (the entry points' eleven leading
+    arguments aq .. ld_vt, the tensors behind them -- the caller keeps them alive until the launch --, out, its
+    row stride, n, m, k, d, divisor, flops)."""
     aq, ld_aq = _aligned_rows(_dev(aq, name='aq'), 'aq')
     kt, ld_kt = _aligned_rows(_dev(kt, name='kt'), 'kt')
     vt, ld_vt = _rows(_dev(vt, name='vt'), 'vt')
@@ -508,14 +527,9 @@ def _attn_operands(aq, qpos, apos, idx, kt, vt, out):
     n, k = idx.shape
     d = vt.shape[1]
     assert idx.is_contiguous() and aq.shape == (n, 2 * d) and kt.shape[1] == 2 * d and qp.shape[0] == n
-    if out is None:
-        out = torch.empty((n, d), dtype=torch.float32, device=aq.device)
-    o, ldo = _rows(out, 'out')
-    assert o is out and o.shape == (n, d)
-    divisor = float(torch.tensor(math.sqrt(d), dtype=torch.float32))
-    flops = 2.0 * n * k * (32 * 2 * d + 2 * d * d + 32 * d)
+    out, ldo = _out(out, (n, d), aq.device)
     head = (_ptr(aq), ld_aq, _ptr(qp), qs, _ptr(ap), as_, _ptr(idx), _ptr(kt), ld_kt, _ptr(vt), ld_vt)
-    return head, (aq, qp, ap, idx, kt, vt), out, ldo, n, kt.shape[0], k, d, divisor, flops
+    return head, (aq, qp, ap, idx, kt, vt), out, ldo, n, kt.shape[0], k, d, _divisor(d), _attn_flops(n, k, d)
 
 
 def pt_cross_attn(aq, qpos, apos, idx, kt, vt, P1, c1, wp, w2, b2, p2, c2, out=None):
@@ -590,9 +604,8 @@ def pt_pair_mlp(aq, kt, r, idx, c2, wstream, skew=None, logits=None):
         assert logits.is_contiguous() and tuple(logits.shape) == (n * k, d)
     else:
         logits = torch.empty((n * k, d), dtype=torch.float32, device=a.device)
-    flops = 2.0 * n * k * (32 * 2 * d + (0 if stored else 2 * d * d) + 32 * d)
     sk = ATTN16P_SKEW if skew is None else int(skew)
-    _lib.check(_launch('pair_hidden' if stored else 'pair_mlp', dict(n=n, k=k, d=d), flops,
+    _lib.check(_launch('pair_hidden' if stored else 'pair_mlp', dict(n=n, k=k, d=d), _attn_flops(n, k, d, gemm2=not stored),
                        lambda: _lib.lib().occ4d_pt_pair_mlp_f32(
         *head, _ptr(a), None if stored else _ptr(logits), _ptr(pe), n, m, k, d, sk, _stream())))
     return a, logits, pe
@@ -604,7 +617,7 @@ def pack_attn_bf16x6_stream(w2, wp, p2):
     w2, wp, p2 = (_cont(t.detach(), 'w') for t in (w2, wp, p2))
     assert w2.shape == (TRUNK_WIDTH, 2 * TRUNK_WIDTH) and wp.shape == (2 * TRUNK_WIDTH, 32) and p2.shape == (TRUNK_WIDTH, 32)
     L = _lib.lib()
-    out = torch.empty((int(L.occ4d_pt_cross_attn_bf16x6_stream_floats()),), dtype=torch.float32, device=w2.device)
+    out = _sized(L.occ4d_pt_cross_attn_bf16x6_stream_floats, device=w2.device)
     _lib.check(L.occ4d_pack_attn_bf16x6_stream_f32(_ptr(w2), _ptr(wp), _ptr(p2), _ptr(out), _stream()))
     return out
 
@@ -614,8 +627,7 @@ def pt_pair_mlp_bf16x6(aq, kt, r, idx, c2, wstream6):
     wstream6 = pack_attn_bf16x6_stream(W2, Wp, P2)."""
     head, _alive, a, pe, n, m, k, d = _pair_operands(aq, kt, r, idx, c2, wstream6)
     logits = torch.empty((n * k, d), dtype=torch.float32, device=a.device)
-    flops = 2.0 * n * k * (32 * 2 * d + 2 * d * d + 32 * d)
-    _lib.check(_launch('pair_mlp', dict(n=n, k=k, d=d), flops, lambda: _lib.lib().occ4d_pt_pair_mlp_bf16x6_f32(
+    _lib.check(_launch('pair_mlp', dict(n=n, k=k, d=d), _attn_flops(n, k, d), lambda: _lib.lib().occ4d_pt_pair_mlp_bf16x6_f32(
         *head, _ptr(a), _ptr(logits), _ptr(pe), n, m, k, d, _stream())))
     return a, logits, pe
 
@@ -623,13 +635,10 @@ def pt_pair_mlp_bf16x6(aq, kt, r, idx, c2, wstream6):
 def layernorm(x, gamma, beta, eps=1e-5, relu=False, out=None):
     x, ldx = _rows(_dev(x, name='x'), 'x')
     n, d = x.shape
-    if out is None:
-        out = torch.empty((n, d), dtype=torch.float32, device=x.device)
-    o, ldo = _rows(out, 'out')
-    assert o is out
+    out, ldo = _out(out, (n, d), x.device)
     g = _dev(gamma).contiguous() if gamma is not None else None
     b = _dev(beta).contiguous() if beta is not None else None
-    _lib.check(_lib.lib().occ4d_layernorm_f32(_ptr(x), ldx, _ptr(g), _ptr(b), eps, int(relu), _ptr(o), ldo, n, d,
+    _lib.check(_lib.lib().occ4d_layernorm_f32(_ptr(x), ldx, _ptr(g), _ptr(b), eps, int(relu), _ptr(out), ldo, n, d,
                                               _stream()))
     return out
 
@@ -650,11 +659,8 @@ def copy_rows(src, out=None):
     a library kernel (the stride-8 xyz view of a point cloud; the column blocks of the encoder's output)."""
     src, lds = _rows(_dev(src, name='src'), 'src')
     n, d = src.shape
-    if out is None:
-        out = torch.empty((n, d), dtype=torch.float32, device=src.device)
-    o, ldo = _rows(_dev(out, name='out'), 'out')
-    assert o is out and tuple(o.shape) == (n, d)
-    _lib.check(_lib.lib().occ4d_copy_rows_f32(_ptr(o), ldo, _ptr(src), lds, n, d, _stream()))
+    out, ldo = _out(out, (n, d), src.device)
+    _lib.check(_lib.lib().occ4d_copy_rows_f32(_ptr(out), ldo, _ptr(src), lds, n, d, _stream()))
     return out
 
 
@@ -798,10 +804,7 @@ def resblock(x, w0_packed, b0, w1_packed, b1, out=None, interp=None):
     xx, ldx = _rows(_dev(x, name='x'), 'x')
     n, d = xx.shape
     assert d == TRUNK_WIDTH
-    if out is None:
-        out = torch.empty((n, d), dtype=torch.float32, device=x.device)
-    o, ldo = _rows(_dev(out, name='out'), 'out')
-    assert o is out and o.shape == (n, d)
+    o, ldo = _out(out, (n, d), x.device)
     ia = _interp_args(interp, n)
     b0c, b1c = _dev(b0).contiguous(), _dev(b1).contiguous()
     # the packing tells the kernel generation: 27 stages of 6656 floats = csrc/trunk4.hip, 14 of 13312 = csrc/trunk.hip
@@ -811,8 +814,8 @@ def resblock(x, w0_packed, b0, w1_packed, b1, out=None, interp=None):
     fn = _lib.lib().occ4d_resblock4_f32 if half_cu else _lib.lib().occ4d_resblock_f32
     _lib.check(_launch('resblock', dict(n=n), 4.0 * n * d * d, lambda: fn(
         _ptr(xx), ldx, _ptr(o), ldo, _ptr(w0_packed), _ptr(b0c), _ptr(w1_packed), _ptr(b1c),
-        ia[0], ia[1], ia[2], ia[3], ia[4], ia[5], n, _stream())))
-    return out
+        *ia[:6], n, _stream())))
+    return o
 
 
 def rowlin(x, w_packed, b, n_out, relu_in=False, residual=None, out=None, interp=None, mask=None, skip=None):
@@ -823,10 +826,7 @@ def rowlin(x, w_packed, b, n_out, relu_in=False, residual=None, out=None, interp
     n, d = xx.shape
     half_cu = n_out % 16 == 0 and w_packed.numel() == (n_out // 16 + 1) * 6656      # csrc/trunk4.hip packing
     assert d == TRUNK_WIDTH and (half_cu or (n_out % 32 == 0 and w_packed.numel() == (n_out // 32 + 1) * 13312))
-    if out is None:
-        out = torch.empty((n, n_out), dtype=torch.float32, device=x.device)
-    o, ldo = _rows(_dev(out, name='out'), 'out')
-    assert o is out and o.shape == (n, n_out)
+    o, ldo = _out(out, (n, n_out), x.device)
     rr, ldr = (None, 0)
     if residual is not None:
         rr, ldr = _rows(_dev(residual, name='residual'), 'residual')
@@ -839,22 +839,19 @@ def rowlin(x, w_packed, b, n_out, relu_in=False, residual=None, out=None, interp
         assert mask is not None and half_cu and residual is None, 'rowlin: skip needs a mask and the half-CU packing'
         rr, ldr = _rows(_dev(skip, name='skip'), 'skip')
         assert rr.shape == (n, n_out)
+    L = _lib.lib()
+    args = (_ptr(xx), ldx, _ptr(o), ldo, _ptr(w_packed), _ptr(bc), n_out, int(relu_in), _ptr(rr), ldr)
     if mask is not None:
         mm, ldm = _rows(_dev(mask, name='mask'), 'mask')
         assert mm.shape == (n, n_out) and interp is None
-        mfn = _lib.lib().occ4d_rowlin4_masked_f32 if half_cu else _lib.lib().occ4d_rowlin_masked_f32
-        if skip is not None:
-            mfn = _lib.lib().occ4d_rowlin4_masked_skip_f32
-        _lib.check(_launch('rowlin', dict(n=n, n_out=n_out), 2.0 * n * d * n_out,
-                           lambda: mfn(_ptr(xx), ldx, _ptr(o), ldo, _ptr(w_packed), _ptr(bc),
-                                                                      n_out, int(relu_in), _ptr(rr), ldr, _ptr(mm), ldm, n,
-                                                                      _stream())))
-        return out
-    fn = _lib.lib().occ4d_rowlin4_f32 if half_cu else _lib.lib().occ4d_rowlin_f32
-    _lib.check(_launch('rowlin', dict(n=n, n_out=n_out), 2.0 * n * d * n_out, lambda: fn(
-        _ptr(xx), ldx, _ptr(o), ldo, _ptr(w_packed), _ptr(bc), n_out, int(relu_in), _ptr(rr), ldr,
-        ia[0], ia[1], ia[2], ia[3], ia[4], ia[5], n, _stream())))
-    return out
+        fn = L.occ4d_rowlin4_masked_skip_f32 if skip is not None else \
+            L.occ4d_rowlin4_masked_f32 if half_cu else L.occ4d_rowlin_masked_f32
+        args += (_ptr(mm), ldm)
+    else:
+        fn = L.occ4d_rowlin4_f32 if half_cu else L.occ4d_rowlin_f32
+        args += ia[:6]
+    _lib.check(_launch('rowlin', dict(n=n, n_out=n_out), 2.0 * n * d * n_out, lambda: fn(*args, n, _stream())))
+    return o
 
 
 # --------------------------------------------------------------------------------------
@@ -873,39 +870,46 @@ def path_row_chunks(n):
     return [min(step, n - lo) for lo in range(0, n, step)]
 
 
-def _attn_flops(c, k, d):
-    return 2.0 * c * k * (32 * 2 * d + 2 * d * d + 32 * d)
+_NO_EVENTS = (None, lambda: None)
 
 
-def _path_timing(name, flops_per_launch):
-    """(occ4d_launch_events struct or None, finish callback) for a path-level call that issues len(flops_per_launch)
-    launches of kernel family `name`: the library records the event pairs on its launch stream (include/occ4d.h);
-    finish(), called after the library call, books the pairs the call really used into the active timer's `events`
-    list ((name, start, end, flops) tuples, the format of KernelTimer / bench_train.StepCounter)."""
+def _path_events(n, families, first_pass=False):
+    """(occ4d_launch_events struct or None, finish callback) for a path-level call over n rows.  `families`: (kernel family
+    name, the rest of its want() shape, FLOPs of a launch over c rows, launches per pass) in the order they are offered to
+    the active timer, asked with n = the rows of a full pass (first_pass: of the call's first pass); the first one it wants
+    is timed.  The library records the event pairs on its launch stream (include/occ4d.h); finish(), called after the
+    library call, books the pairs the call really used into the timer's `events` list ((name, start, end, flops) tuples,
+    the format of KernelTimer / bench_train.StepCounter)."""
     t = _timer
-    if t is None or not flops_per_launch or not hasattr(t, 'events'):
-        return None, (lambda: None)
-    n = len(flops_per_launch)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(2 * n)]
+    if t is None or not n:
+        return _NO_EVENTS
+    chunks = path_row_chunks(n)
+    for name, shape, flops, per_pass in families:
+        if t.want(name, n=chunks[0] if first_pass else min(n, PATH_ROW_CHUNK), **shape):
+            break
+    else:
+        return _NO_EVENTS
+    flops_per_launch = [flops(c) for c in chunks for _ in range(per_pass)]
+    if not flops_per_launch or not hasattr(t, 'events'):
+        return _NO_EVENTS
+    m = len(flops_per_launch)
+    evs = [torch.cuda.Event(enable_timing=True) for _ in range(2 * m)]
     for e in evs:
         e.record()                       # (torch creates the hipEvent_t lazily, at the first record)
-    arr = (C.c_void_p * (2 * n))(*[e.cuda_event for e in evs])
-    st = _lib.LaunchEvents(events=C.cast(arr, C.POINTER(C.c_void_p)), capacity=n, used=0,
+    arr = (C.c_void_p * (2 * m))(*[e.cuda_event for e in evs])
+    st = _lib.LaunchEvents(events=C.cast(arr, C.POINTER(C.c_void_p)), capacity=m, used=0,
                            kernel=_lib.PROFILE_KINDS[name], reserved=0)
     st._keep = (arr, evs)
 
     def finish():
         for i in range(st.used):
             t.events.append((name, evs[2 * i], evs[2 * i + 1], float(flops_per_launch[i])))
-    return st, finish
+    return C.byref(st), finish
 
 
 def pt_layer_prepare(w, flags, device):
     """prepared buffer of occ4d_pt_layer_prepare_f32 for the weight struct `w` (merged matrices + packed streams)."""
-    n = int(_lib.lib().occ4d_pt_layer_prepared_floats(C.byref(w), flags))
-    if n < 0:
-        _lib.check(_lib.EINVAL)
-    prep = torch.empty((n,), dtype=torch.float32, device=device)
+    prep = _sized(_lib.lib().occ4d_pt_layer_prepared_floats, C.byref(w), flags, device=device)
     _lib.check(_lib.lib().occ4d_pt_layer_prepare_f32(C.byref(w), _ptr(prep), flags, _stream()))
     return prep
 
@@ -930,20 +934,11 @@ def pt_layer_fwd(w, prepared, x, pos, x2, pos2, k, flags=0, knn_idx=None, out=No
     if knn_idx is not None:
         knn_idx = _dev(knn_idx, torch.int32, 'knn_idx')
         assert knn_idx.is_contiguous() and tuple(knn_idx.shape) == (n, k)
-    if out is None:
-        out = torch.empty((n, d_out), dtype=torch.float32, device=x.device)
-    o, ldo = _rows(_dev(out, name='out'), 'out')
-    assert o is out and tuple(o.shape) == (n, d_out)
-    nws = int(_lib.lib().occ4d_pt_layer_workspace_floats(C.byref(w), n, m, k, flags))
-    if nws < 0:
-        _lib.check(_lib.EINVAL)
-    ws = torch.empty((nws,), dtype=torch.float32, device=x.device)
+    o, ldo = _out(out, (n, d_out), x.device)
+    ws = _sized(_lib.lib().occ4d_pt_layer_workspace_floats, C.byref(w), n, m, k, flags, device=x.device)
     fused = w.dim in FUSED_ATTN_DIMS and k <= FUSED_ATTN_MAX_K and w.pos_hidden == 32 and not (flags & _lib.PATH_UNFUSED)
-    chunks = path_row_chunks(n) if fused else []
-    t = _timer
-    ev, finish = (None, lambda: None)
-    if t is not None and chunks and t.want('cross_attn', n=chunks[0], k=k, d=w.dim):
-        ev, finish = _path_timing('cross_attn', [_attn_flops(c, k, w.dim) for c in chunks])
+    ev, finish = _path_events(n, [('cross_attn', dict(k=k, d=w.dim), lambda c: _attn_flops(c, k, w.dim), 1)],
+                              first_pass=True) if fused else _NO_EVENTS
     if logits_out is not None:
         lg = _dev(logits_out, name='logits_out')
         assert lg.is_contiguous() and tuple(lg.shape) == (n * k, w.dim) and logits_storable(w, k, flags)
@@ -953,15 +948,14 @@ def pt_layer_fwd(w, prepared, x, pos, x2, pos2, k, flags=0, knn_idx=None, out=No
             assert pa.is_contiguous() and pp.is_contiguous() and tuple(pa.shape) == (n * k, 2 * w.dim) and pp.shape == lg.shape
         _lib.check(_lib.lib().occ4d_pt_layer_fwd_logits_f32(
             C.byref(w), _ptr(prepared), _ptr(x), ldx, _ptr(p), ps, n, _ptr(x2p), ldx2, _ptr(p2), p2s, m, k, _ptr(knn_idx),
-            None, _ptr(o), ldo, _ptr(lg), _ptr(pa), _ptr(pp), _ptr(ws), flags, C.byref(ev) if ev is not None else None,
-            _stream()))
+            None, _ptr(o), ldo, _ptr(lg), _ptr(pa), _ptr(pp), _ptr(ws), flags, ev, _stream()))
         finish()
-        return out
+        return o
     _lib.check(_lib.lib().occ4d_pt_layer_fwd_f32(
         C.byref(w), _ptr(prepared), _ptr(x), ldx, _ptr(p), ps, n, _ptr(x2p), ldx2, _ptr(p2), p2s, m, k, _ptr(knn_idx), None,
-        _ptr(o), ldo, _ptr(ws), flags, C.byref(ev) if ev is not None else None, _stream()))
+        _ptr(o), ldo, _ptr(ws), flags, ev, _stream()))
     finish()
-    return out
+    return o
 
 
 def logits_storable(w, k, flags):
@@ -991,10 +985,7 @@ def down_pool_fwd(x, weight, bias, nn_idx, norm=0, gamma=None, beta=None, mean=N
 
 
 def decoder_prepare(w, flags, device):
-    n = int(_lib.lib().occ4d_decoder_prepared_floats(C.byref(w), flags))
-    if n < 0:
-        _lib.check(_lib.EINVAL)
-    prep = torch.empty((n,), dtype=torch.float32, device=device)
+    prep = _sized(_lib.lib().occ4d_decoder_prepared_floats, C.byref(w), flags, device=device)
     _lib.check(_lib.lib().occ4d_decoder_prepare_f32(C.byref(w), _ptr(prep), flags, _stream()))
     return prep
 
@@ -1005,10 +996,7 @@ def decoder_prepare_scene(w, prepared, xyz, feats, fglobal, flags):
     m = xyz.shape[0]
     assert feats.shape[0] == m
     fg = _cont(fglobal, 'features_global') if fglobal is not None and fglobal.numel() else None
-    n = int(_lib.lib().occ4d_decoder_scene_floats(C.byref(w), m))
-    if n < 0:
-        _lib.check(_lib.EINVAL)
-    scene = torch.empty((n,), dtype=torch.float32, device=xyz.device)
+    scene = _sized(_lib.lib().occ4d_decoder_scene_floats, C.byref(w), m, device=xyz.device)
     _lib.check(_lib.lib().occ4d_decoder_prepare_scene_f32(C.byref(w), _ptr(prepared), _ptr(xyz), xs, _ptr(feats), ldf,
                                                           _ptr(fg), m, _ptr(scene), flags, _stream()))
     return scene
@@ -1038,36 +1026,21 @@ def decoder_query_fwd(w, prepared, scene, m, queries, flags=0, out=None, penult=
     n = q.shape[0]
     kl = _neighbour_list(knn_local, n, w.k_local, 'knn_local')
     kc = _neighbour_list(knn_cross, n, w.k_cross, 'knn_cross') if w.n_cross > 0 else None
-    if out is None:
-        out = torch.empty((n, w.d_out), dtype=torch.float32, device=q.device)
-    o, ldo = _rows(_dev(out, name='out'), 'out')
-    assert o is out and tuple(o.shape) == (n, w.d_out)
-    if penult is None and want_penult:
-        penult = torch.empty((n, w.d_hidden), dtype=torch.float32, device=q.device)
+    o, ldo = _out(out, (n, w.d_out), q.device)
     ldp = 0
-    if penult is not None:
-        pp, ldp = _rows(_dev(penult, name='penult'), 'penult')
-        assert pp is penult and tuple(pp.shape) == (n, w.d_hidden)
-    nws = int(_lib.lib().occ4d_decoder_query_workspace_floats(C.byref(w), n, m, flags))
-    if nws < 0:
-        _lib.check(_lib.EINVAL)
-    ws = torch.empty((nws,), dtype=torch.float32, device=q.device)
+    if penult is not None or want_penult:
+        penult, ldp = _out(penult, (n, w.d_hidden), q.device, name='penult')
+    ws = _sized(_lib.lib().occ4d_decoder_query_workspace_floats, C.byref(w), n, m, flags, device=q.device)
     d, k = w.d_hidden, w.k_cross
     fused = (w.n_cross > 0 and d in FUSED_ATTN_DIMS and k <= FUSED_ATTN_MAX_K and w.cross[0].pos_hidden == 32
              and not (flags & _lib.PATH_UNFUSED))
-    t = _timer
-    ev, finish = (None, lambda: None)
-    if t is not None and fused and n and t.want('cross_attn', n=min(n, PATH_ROW_CHUNK), k=k, d=d):
-        chunks = path_row_chunks(n)
-        ev, finish = _path_timing('cross_attn', [_attn_flops(c, k, d) for c in chunks for _ in range(w.n_cross)])
-    elif t is not None and n and t.want('resblock', n=min(n, PATH_ROW_CHUNK)):
-        chunks = path_row_chunks(n)
-        ev, finish = _path_timing('resblock', [4.0 * c * d * d for c in chunks for _ in range(w.n_blocks)])
+    attn = [('cross_attn', dict(k=k, d=d), lambda c: _attn_flops(c, k, d), w.n_cross)] if fused else []
+    ev, finish = _path_events(n, attn + [('resblock', {}, lambda c: 4.0 * c * d * d, w.n_blocks)])
     _lib.check(_lib.lib().occ4d_decoder_query_fwd_f32(
         C.byref(w), _ptr(prepared), _ptr(scene), m, _ptr(q), qs, n, _ptr(kl), _ptr(kc), _ptr(o), ldo, _ptr(penult), ldp,
-        _ptr(ws), flags, C.byref(ev) if ev is not None else None, _stream()))
+        _ptr(ws), flags, ev, _stream()))
     finish()
-    return out, penult
+    return o, penult
 
 
 def squash(out, ops):
@@ -1139,50 +1112,41 @@ class RadiusGrid:
         return out
 
 
-def compact_rows(rows, key, threshold, strict=True):
-    """Order-preserving selection rows[key > threshold] (>= when not strict) -> (rows kept (n', d), keys kept (n'));
-    one 4-byte device->host read (the kept count) sizes the outputs."""
+def _compact(rows, key, threshold, strict, sync):
+    """compact_rows (sync: the kept count is read and sizes the outputs) / compact_rows_nosync (all n rows allocated) ->
+    (rows, keys, count (1,) int32 on the device -- None when sync and n == 0)."""
     r, ld = _rows(_dev(rows, name='rows'), 'rows')
     k = _dev(key, name='key')
     assert k.dim() == 1 and k.shape[0] == r.shape[0]
     n, d = r.shape
     if n == 0:
-        return r.new_empty((0, d)), k.new_empty((0,))
+        return r.new_empty((0, d)), k.new_empty((0,)), None if sync else torch.zeros((1,), dtype=torch.int32, device=r.device)
     lk = k.stride(0) if n > 1 else 1
     nb = (n + 255) // 256
     scratch = torch.empty(nb + 1, dtype=torch.int32, device=r.device)
     st = _stream()
     _lib.check(_lib.lib().occ4d_compact_count_f32(_ptr(k), lk, n, float(threshold), int(strict), _ptr(scratch),
                                                   _ptr(scratch[nb:]), st))
-    kept = int(scratch[nb].item())
+    kept = int(scratch[nb].item()) if sync else n
     out_rows = torch.empty((kept, d), dtype=torch.float32, device=r.device)
     out_key = torch.empty((kept,), dtype=torch.float32, device=r.device)
     _lib.check(_lib.lib().occ4d_compact_rows_f32(_ptr(r), ld, n, d, _ptr(k), lk, float(threshold), int(strict),
                                                  _ptr(scratch), _ptr(out_rows), _ptr(out_key), st))
-    return out_rows, out_key
+    return out_rows, out_key, scratch[nb:nb + 1]
+
+
+def compact_rows(rows, key, threshold, strict=True):
+    """Order-preserving selection rows[key > threshold] (>= when not strict) -> (rows kept (n', d), keys kept (n'));
+    one 4-byte device->host read (the kept count) sizes the outputs."""
+    return _compact(rows, key, threshold, strict, True)[:2]
 
 
 def compact_rows_nosync(rows, key, threshold, strict=True):
     """compact_rows without the device->host read: -> (buffer (n, d) whose first `count` rows are rows[key > threshold] in
     order -- the rest is uninitialised --, count (1,) int32 ON THE DEVICE).  For callers that collect several counts and
     read them in one transfer (the point sampler: one synchronisation per stage instead of one per selection)."""
-    r, ld = _rows(_dev(rows, name='rows'), 'rows')
-    k = _dev(key, name='key')
-    assert k.dim() == 1 and k.shape[0] == r.shape[0]
-    n, d = r.shape
-    if n == 0:
-        return r.new_empty((0, d)), torch.zeros((1,), dtype=torch.int32, device=r.device)
-    lk = k.stride(0) if n > 1 else 1
-    nb = (n + 255) // 256
-    scratch = torch.empty(nb + 1, dtype=torch.int32, device=r.device)
-    st = _stream()
-    _lib.check(_lib.lib().occ4d_compact_count_f32(_ptr(k), lk, n, float(threshold), int(strict), _ptr(scratch),
-                                                  _ptr(scratch[nb:]), st))
-    out_rows = torch.empty((n, d), dtype=torch.float32, device=r.device)
-    out_key = torch.empty((n,), dtype=torch.float32, device=r.device)
-    _lib.check(_lib.lib().occ4d_compact_rows_f32(_ptr(r), ld, n, d, _ptr(k), lk, float(threshold), int(strict),
-                                                 _ptr(scratch), _ptr(out_rows), _ptr(out_key), st))
-    return out_rows, scratch[nb:nb + 1]
+    out_rows, _, count = _compact(rows, key, threshold, strict, False)
+    return out_rows, count
 
 
 def eval_layout(n_groups, n_classes):
@@ -1344,7 +1308,7 @@ def bn_train_fwd(y, gamma, beta, eps):
     mean = torch.empty((d,), dtype=torch.float32, device=y.device)
     var = torch.empty((d,), dtype=torch.float32, device=y.device)
     out = torch.empty((n, d), dtype=torch.float32, device=y.device)
-    ws = torch.empty((int(_lib.lib().occ4d_bn_workspace_doubles(n, d)),), dtype=torch.float64, device=y.device)
+    ws = _sized(_lib.lib().occ4d_bn_workspace_doubles, n, d, dtype=torch.float64, device=y.device)
     _lib.check(_lib.lib().occ4d_bn_train_fwd_f32(_ptr(y), ldy, n, d, _ptr(_cont(gamma.detach(), 'gamma')),
                                                  _ptr(_cont(beta.detach(), 'beta')), float(eps), _ptr(mean), _ptr(var),
                                                  _ptr(out), d, _ptr(ws), _stream()))
@@ -1360,7 +1324,7 @@ def bn_train_bwd(y, g, out, mean, var, gamma, eps):
     dx = torch.empty((n, d), dtype=torch.float32, device=y.device)
     dgamma = torch.empty((d,), dtype=torch.float32, device=y.device)
     dbeta = torch.empty((d,), dtype=torch.float32, device=y.device)
-    ws = torch.empty((int(_lib.lib().occ4d_bn_workspace_doubles(n, d)),), dtype=torch.float64, device=y.device)
+    ws = _sized(_lib.lib().occ4d_bn_workspace_doubles, n, d, dtype=torch.float64, device=y.device)
     _lib.check(_lib.lib().occ4d_bn_train_bwd_f32(_ptr(y), ldy, _ptr(g), ldg, _ptr(out), ldo, n, d, _ptr(mean), _ptr(var),
                                                  _ptr(_cont(gamma.detach(), 'gamma')), float(eps), _ptr(dx), d, _ptr(dgamma),
                                                  _ptr(dbeta), _ptr(ws), _stream()))
@@ -1459,7 +1423,7 @@ def _segments(idx_flat, n_out, stable=True):
         idx_c = idx_flat if idx_flat.is_contiguous() else idx_flat.contiguous()
         order = torch.empty((idx_c.numel(),), dtype=torch.int32, device=idx_c.device)
         off = torch.empty((n_out + 1,), dtype=torch.int32, device=idx_c.device)
-        ws = torch.empty((int(_lib.lib().occ4d_segments_workspace_ints(n_out)),), dtype=torch.int32, device=idx_c.device)
+        ws = _sized(_lib.lib().occ4d_segments_workspace_ints, n_out, dtype=torch.int32, device=idx_c.device)
         _lib.check(_lib.lib().occ4d_segments_build_i32(_ptr(idx_c), idx_c.numel(), n_out, _ptr(order), _ptr(off), _ptr(ws),
                                                       _stream()))
     if not capturing:
@@ -1574,33 +1538,25 @@ def pt_softmax_agg_bwd(logits, v, pe, idx, dagg, reduce_dv=True):
     d = logits.shape[1]
     pe = _cont(pe, 'pe') if pe is not None else None
     dlogits = torch.empty_like(logits)
-    divisor = float(torch.tensor(math.sqrt(d), dtype=torch.float32))
     idx32 = _dev(idx, torch.int32)
+    # Per-pair value gradients (written through the kernel's dpe output, dv = None) in the deterministic mode -- summed per
+    # abstract point in pair order (measured in round 4: routing this sum through occ4d_segment_sum_sorted_f32 in the default
+    # mode instead of the kernel's own atomics changes nothing, 103.95 vs 103.91 ms per step) -- and on the 16-byte-lane
+    # kernel (5.4 TB/s over the four pair tensors; their sum per abstract point is a separate reduction: its own atomics
+    # from 16-byte lanes cost more than the kernel).  Otherwise the kernel adds dv itself, atomically.
+    per_pair = DETERMINISTIC or (SOFTMAX_BWD_SPLIT and k in (8, 12, 14, 16) and d % 4 == 0 and ldv % 4 == 0 and ldda % 4 == 0)
+    dpe = torch.empty_like(logits) if per_pair or pe is not None else None
+    dv = None if per_pair else torch.zeros((v.shape[0], d), dtype=torch.float32, device=logits.device)
+    _lib.check(_lib.lib().occ4d_pt_softmax_agg_bwd_f32(_ptr(logits), _ptr(v), ldv, _ptr(pe), _ptr(idx32), n, k, d,
+                                                       _divisor(d), _ptr(dagg), ldda, _ptr(dlogits), _ptr(dpe), _ptr(dv), d,
+                                                       _stream()))
+    if not per_pair:
+        return dlogits, dpe, dv
     if DETERMINISTIC:
-        # the per-pair value gradients (the kernel's dpe output) are kept and summed per abstract point in pair order
-        # (measured in round 4: routing this sum through occ4d_segment_sum_sorted_f32 in the default mode instead of the
-        # kernel's own atomics changes nothing, 103.95 vs 103.91 ms per step)
-        dval = torch.empty_like(logits)
-        _lib.check(_lib.lib().occ4d_pt_softmax_agg_bwd_f32(_ptr(logits), _ptr(v), ldv, _ptr(pe), _ptr(idx32), n, k, d,
-                                                           divisor, _ptr(dagg), ldda, _ptr(dlogits), _ptr(dval), None, d,
-                                                           _stream()))
-        dv = segment_gather_sum(dval, idx32.contiguous().view(-1), v.shape[0])
-        return dlogits, (dval if pe is not None else None), dv
-    if SOFTMAX_BWD_SPLIT and k in (8, 12, 14, 16) and d % 4 == 0 and ldv % 4 == 0 and ldda % 4 == 0:
-        # 16-byte-lane kernel (5.4 TB/s over the four pair tensors) writes the per-pair value gradients; their sum per
-        # abstract point is a separate reduction (its own atomics from 16-byte lanes cost more than the kernel)
-        dval = torch.empty_like(logits)
-        _lib.check(_lib.lib().occ4d_pt_softmax_agg_bwd_f32(_ptr(logits), _ptr(v), ldv, _ptr(pe), _ptr(idx32), n, k, d,
-                                                           divisor, _ptr(dagg), ldda, _ptr(dlogits), _ptr(dval), None, d,
-                                                           _stream()))
-        dv = scatter_add_rows(dval, idx32, v.shape[0]) if reduce_dv else (dval, idx32, v.shape[0])
-        return dlogits, (dval if pe is not None else None), dv
-    dpe = torch.empty_like(logits) if pe is not None else None
-    dv = torch.zeros((v.shape[0], d), dtype=torch.float32, device=logits.device)
-    _lib.check(_lib.lib().occ4d_pt_softmax_agg_bwd_f32(_ptr(logits), _ptr(v), ldv, _ptr(pe),
-                                                       _ptr(idx32), n, k, d, divisor, _ptr(dagg), ldda,
-                                                       _ptr(dlogits), _ptr(dpe), _ptr(dv), d, _stream()))
-    return dlogits, dpe, dv
+        dv = segment_gather_sum(dpe, idx32.contiguous().view(-1), v.shape[0])
+    else:
+        dv = scatter_add_rows(dpe, idx32, v.shape[0]) if reduce_dv else (dpe, idx32, v.shape[0])
+    return dlogits, (dpe if pe is not None else None), dv
 
 
 def pt_pos_hidden_bwd(pos, pos2, idx, r, gr):

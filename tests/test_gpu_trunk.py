@@ -195,3 +195,24 @@ def test_half_cu_rowlin_tail_split(n, n_out, masked):
         want = torch.where(mask[rows] > 0, want, torch.zeros_like(want))
     assert float((got[rows].double() - want).abs().max()) <= 2e-5 * float(want.abs().max())
 
+
+
+@pytest.mark.parametrize('n_out', [32, 416])
+@pytest.mark.parametrize('n', [1, 65, 130])
+def test_rowlin_masked_skip(n, n_out):
+    """occ4d_rowlin4_masked_skip_f32 (rowlin(..., mask=, skip=), half-CU packing): the data gradient of a residual block's
+    first layer with the skip gradient folded in, y = [mask > 0] (x W^T + b) + skip.  Both this launch and
+    occ4d_rowlin4_masked_f32 followed by an fp32 add put `skip` last onto the same masked value: equal bit for bit."""
+    rng = np.random.default_rng(7 * n + n_out)
+    g = torch.from_numpy(rng.normal(size=(n, H)).astype(np.float32)).cuda()
+    w, b = _weights(rng, n_out)
+    mask = torch.from_numpy(rng.normal(size=(n, n_out)).astype(np.float32)).cuda()
+    mask[0, :5] = 0.0                                           # (zero counts as "not positive")
+    skip = torch.from_numpy(rng.normal(size=(n, n_out)).astype(np.float32)).cuda()
+    p = pk.ops.pack_trunk4_rows(w)
+    masked = pk.ops.rowlin(g, p, b, n_out, mask=mask)
+    got = pk.ops.rowlin(g, p, b, n_out, mask=mask, skip=skip)
+    assert torch.equal(got, masked + skip)
+    assert torch.equal(got[0, :5], skip[0, :5]) and bool((masked != 0).any())
+    with pytest.raises(AssertionError, match='skip needs a mask'):
+        pk.ops.rowlin(g, p, b, n_out, skip=skip)
