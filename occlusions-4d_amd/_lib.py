@@ -12,6 +12,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d.h')
 FRONTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_frontend.h')
 EVAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_eval.h')
 OCCL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_occl.h')
+TRACK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_track.h')
 
 
 class NativeLibraryError(RuntimeError):
@@ -167,6 +168,14 @@ except OSError as e:
 OCCL_SIGNATURES = parse_prototypes(_OCCL_HEADER, {})
 OCCL_CONSTANTS = {k[len('OCCL_'):]: v for k, v in parse_constants(_OCCL_HEADER).items()}
 
+# the running merge of the per-instance reruns (inference.perform_inference, track_mode 'all'): include/occ4d_track.h
+try:
+    with open(TRACK_HEADER_PATH) as _f:
+        TRACK_SIGNATURES = parse_prototypes(_f.read(), {})
+except OSError as e:
+    raise NativeLibraryError('include/occ4d_track.h not found at %s (%s): the ctypes binding is derived from it'
+                             % (TRACK_HEADER_PATH, e))
+
 _lib = None
 _twin = False            # True only after an explicit load_cpu_twin(): host pointers, no streams (cpu_twin.py)
 
@@ -176,10 +185,10 @@ def is_twin():
 
 
 def bind(handle, missing=None):
-    """Sets restype / argtypes of every symbol of SIGNATURES, FRONTEND_SIGNATURES, EVAL_SIGNATURES and OCCL_SIGNATURES on a loaded library and returns it.  A symbol the library does
+    """Sets restype / argtypes of every symbol of SIGNATURES, FRONTEND_SIGNATURES, EVAL_SIGNATURES, OCCL_SIGNATURES and TRACK_SIGNATURES on a loaded library and returns it.  A symbol the library does
     not export is a stale library (NativeLibraryError) unless `missing` is given: then missing(name) stands in for it."""
     for name, (res, args) in list(SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
-            list(OCCL_SIGNATURES.items()):
+            list(OCCL_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError:

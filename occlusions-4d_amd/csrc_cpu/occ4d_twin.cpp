@@ -26,9 +26,11 @@
 #include "occ4d_frontend.h"
 #include "occ4d_eval.h"
 #include "occ4d_occl.h"
+#include "occ4d_track.h"
 #include "frontend_math.hpp"      // csrc/: the front end's per-element arithmetic, the HIP kernels' own source
 #include "eval_math.hpp"          // csrc/: the evaluation statistics' per-row classification, likewise
 #include "occl_math.hpp"          // csrc/: the id histogram's per-row decision, likewise
+#include "track_math.hpp"         // csrc/: the track merge's squash and winner / best update, likewise
 
 namespace {
 
@@ -389,8 +391,7 @@ int occ4d_squash_f32(float* out, int64_t ld, int n, int g, const int32_t* ops_ho
   for (int i = 0; i < n; ++i)
     for (int c = 0; c < g; ++c) {
       float& v = out[(int64_t)i * ld + c];
-      if (ops_host[c] == 1) v = 1.f / (1.f + std::exp(-v));
-      else if (ops_host[c] == 2) v = std::min(std::max(v, 0.f), 1.f);
+      v = occ4d_track::squash(v, ops_host[c]);      // (csrc/track_math.hpp: squash_kernel's expression, the merge's too)
     }
   return OCC4D_OK;
 }
@@ -647,6 +648,54 @@ int occ4d_id_histogram_f32(const float* rows, int64_t ld, int n, int col, const 
     const int seg = oc::segment_end_index(seg_offsets, n_segments, i) - 1;
     ++counts[(int64_t)seg * bins + bin];
   }
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- track merge
+// include/occ4d_track.h: the passes of csrc/trackmerge.hip over csrc/track_math.hpp, elements in order.
+int occ4d_track_merge_add_f32(const float* out, int64_t ld_out, int n, int g, const int32_t* ops_host, int track_col, float inst_id,
+                              int first, float* acc, int64_t ld_acc, float* best, float* winner, void*) {
+  namespace tk = occ4d_track;
+  const char* who = "occ4d_track_merge_add_f32";
+  REQ(n >= 0 && g >= 1 && g <= 32, "%s: n = %d, g = %d: need n >= 0, 1 <= g <= 32", who, n, g);
+  REQ(ld_out >= g && ld_acc >= g, "%s: ld_out = %lld, ld_acc = %lld must be >= g = %d", who, (long long)ld_out, (long long)ld_acc, g);
+  REQ(track_col >= -1 && track_col < g, "%s: track_col = %d must be -1 or in 0 .. g - 1 = %d", who, track_col, g - 1);
+  REQ(first == 0 || first == 1, "%s: first = %d must be 0 or 1", who, first);
+  if (ops_host)
+    for (int c = 0; c < g; ++c) REQ(ops_host[c] >= 0 && ops_host[c] <= 2, "%s: op code %d", who, ops_host[c]);
+  if (n == 0) return OCC4D_OK;
+  REQ(out && acc, "%s: null out / acc", who);
+  REQ(track_col < 0 || (best && winner), "%s: null best / winner with track_col = %d", who, track_col);
+  const uint64_t codes = tk::pack_codes(ops_host, g);
+  for (int64_t i = 0; i < n; ++i)
+    for (int c = 0; c < g; ++c) {
+      const float v = tk::squash(out[i * ld_out + c], tk::code_of(codes, c));
+      if (c == track_col) {
+        float b = first ? 0.f : best[i], w = first ? -1.f : winner[i];
+        tk::winner_update(v, inst_id, b, w);
+        best[i] = b;
+        winner[i] = w;
+      }
+      float& dst = acc[i * ld_acc + c];
+      dst = first ? v : dst + v;
+    }
+  return OCC4D_OK;
+}
+int occ4d_track_merge_finish_f32(float* acc, int64_t ld_acc, int n, int g, int n_runs, int track_col, const float* winner, void*) {
+  const char* who = "occ4d_track_merge_finish_f32";
+  REQ(n >= 0 && g >= 1 && g <= 32, "%s: n = %d, g = %d: need n >= 0, 1 <= g <= 32", who, n, g);
+  REQ(ld_acc >= g, "%s: ld_acc = %lld must be >= g = %d", who, (long long)ld_acc, g);
+  REQ(track_col >= -1 && track_col < g, "%s: track_col = %d must be -1 or in 0 .. g - 1 = %d", who, track_col, g - 1);
+  REQ(n_runs >= 1, "%s: n_runs = %d must be >= 1", who, n_runs);
+  if (n == 0) return OCC4D_OK;
+  REQ(acc, "%s: null acc", who);
+  REQ(track_col < 0 || winner, "%s: null winner with track_col = %d", who, track_col);
+  const float runs = (float)n_runs;
+  for (int64_t i = 0; i < n; ++i)
+    for (int c = 0; c < g; ++c) {
+      float& v = acc[i * ld_acc + c];
+      v = c == track_col ? winner[i] : v / runs;
+    }
   return OCC4D_OK;
 }
 

@@ -205,7 +205,7 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
             point_occupancy_radius=args.point_occupancy_radius, semantic_classes=args.semantic_classes,
             density_threshold=args.density_threshold, data_kind=data_kind, cube_mode=args.cube_mode, compress_air=True,
             encoded=encoded if reuse_encode else None, return_encoded=reuse_encode, **stats_kw)
-        if reuse_encode and args.track_mode in ('none', 'one'):
+        if reuse_encode:                  # (track_mode 'all': a dict with one encode per tracked instance)
             encoded = res.pop('_encoded')
         else:
             res.pop('_encoded', None)

@@ -151,7 +151,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                       point_occupancy_radius=0.2, semantic_classes=13,
                       density_threshold=0.5, data_kind='', cube_mode=4, compress_air=False,
                       encoded=None, return_encoded=False, neighbour_lists=None, stats=None, stats_target=None,
-                      stats_group=None):
+                      stats_group=None, track_merge='device'):
     """One encode of the input point-cloud video + decode of all query points of one output
     frame.  Returns dict(output_solid, output_air, pcl_abstract, features_global,
     implicit_output, points_query) of float32 numpy arrays.
@@ -162,9 +162,15 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     reference for these queries (LocalPclResnetFC.forward's extension; either entry may be None); `stats` = an
     evaluation.EvalStats this frame is added to, scored on the device against `pcl_target_frame` (or `stats_target` when that
     is not passed: no gt_solid / gt_air then) with `stats_group` = the group id per target point; the query -> target search
-    and the solid split are shared with the gt branch and the result dict is what it is without `stats`."""
+    and the solid split are shared with the gt branch and the result dict is what it is without `stats`.
+    In track_mode 'all', `encoded` / '_encoded' are dicts {instance id: (pcl_abstract, features_global)}, one entry per rerun.
+    `track_merge`: where the reruns of track_mode 'all' are merged.  'device': a running merge in the library
+    (ops.track_merge_add / track_merge_finish: the squash, the sums and the winner / best update in one pass per rerun), the
+    merged tensor stays on the device for the split and the scoring, and the host blocks once, at the end.  'host': every
+    rerun is copied to the host, multi_track_merge runs in numpy and the merged array is uploaded again.  Same bits."""
     assert task == 'if'
     assert sample_implicit
+    assert track_merge in ('device', 'host'), track_merge
     output_track_idx = get_track_idx(color_mode)
     input_inst_idx = 0 if data_kind == 'greater' else 1
     pcl_net, implicit_net = networks
@@ -191,20 +197,34 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         num_sample, min_z, cube_bounds, time_idx, data_kind, cube_mode, point_sample_mode, device)
     copies = _HostCopies(device)
     single_run = len(track_instance_ids) == 1 and track_instance_ids[0] == -1
+    device_merge = track_merge == 'device' and not single_run and len(track_instance_ids) > 0
     points_query = copies.fetch(queries_dev)              # (under the encode / decode that follows)
     all_abstract, all_global, all_output = [], [], []
+    encoded_out = {}
     with torch.no_grad():
-        for inst_id in track_instance_ids:
+        for run, inst_id in enumerate(track_instance_ids):
             if inst_id >= 0:                  # mark the instance to follow in the input cloud (:190-193)
                 pcl_input[..., -1] = (pcl_input_sem[..., input_inst_idx] == inst_id)
             res = infer_device(pcl_input, queries_dev, pcl_net, implicit_net, batch_size, color_mode,
                                predict_segmentation, track_mode, semantic_classes,
-                               encoded=encoded if inst_id < 0 else None, neighbour_lists=neighbour_lists)
+                               encoded=_encoded_for(encoded, inst_id), neighbour_lists=neighbour_lists,
+                               squash=not device_merge)
+            encoded_out[inst_id] = (res['pcl_abstract'], res['features_global'])
+            if device_merge:                  # this rerun onto the running merge: squash, sum, winner / best in one pass
+                raw = res['implicit_output']
+                if run == 0:
+                    merged = _RunningMerge(raw, res['pcl_abstract'], res['features_global'])
+                merged.add(raw, res['pcl_abstract'], res['features_global'], inst_id, output_track_idx,
+                           squash_codes(raw.shape[1], color_mode, predict_segmentation, track_mode, semantic_classes))
+                continue
             output_dev = res['implicit_output']
             all_output.append(copies.fetch(output_dev))
             all_abstract.append(copies.fetch(res['pcl_abstract']))
             all_global.append(copies.fetch(res['features_global']))
-        if not single_run:                    # the merge of the per-instance reruns is host arithmetic
+        if device_merge:
+            output_dev = merged.finish(output_track_idx)
+            merged_h = (copies.fetch(merged.abstract), copies.fetch(merged.features), copies.fetch(output_dev))
+        elif not single_run:                  # the merge of the per-instance reruns is host arithmetic
             copies.wait()
             (pcl_abstract, features_global, implicit_output) = multi_track_merge(
                 track_instance_ids, [copies.result(h) for h in all_abstract], [copies.result(h) for h in all_global],
@@ -227,7 +247,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
             points_nngt = np.concatenate([target_labels[:, None], pcl_target_frame[nn_indices]], axis=-1)
 
         # density-threshold split + compress_air on the device (:279-305): order-preserving compaction
-        if not single_run:                    # merged on the host; one upload
+        if not single_run and not device_merge:       # merged on the host; one upload
             output_dev = torch.from_numpy(implicit_output).to(device)
         solid, air = ops.split_solid_air(queries_dev, output_dev, density_threshold, compress_air, semantic_classes)
         if stats is not None:
@@ -247,11 +267,13 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         if single_run:
             (pcl_abstract, features_global, implicit_output) = (copies.result(all_abstract[0]),
                                                                  copies.result(all_global[0]), copies.result(all_output[0]))
+        elif device_merge:
+            (pcl_abstract, features_global, implicit_output) = (copies.result(h) for h in merged_h)
     ops.check_pending()                      # cooperative-FPS status words (everything above has completed)
     result = dict(output_solid=solid, output_air=air, pcl_abstract=pcl_abstract,
                   features_global=features_global, implicit_output=implicit_output, points_query=points_query)
     if return_encoded:
-        result['_encoded'] = (res['pcl_abstract'], res['features_global'])
+        result['_encoded'] = encoded_out[-1] if single_run else encoded_out
     if gt_available:
         solid_mask = implicit_output[..., 0] >= density_threshold
         gt_solid, gt_air = points_nngt[solid_mask], points_nngt[~solid_mask]
@@ -259,6 +281,44 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
             gt_air = np.concatenate([gt_air[..., :1], gt_air[..., 4:5]], axis=-1)
         result['gt_solid'], result['gt_air'] = gt_solid, gt_air
     return result
+
+
+def _encoded_for(encoded, inst_id):
+    """The caller's encode of the run that follows `inst_id` (-1: the unmarked run), or None: encode it now."""
+    if inst_id < 0:
+        return None if isinstance(encoded, dict) else encoded
+    return encoded.get(inst_id) if isinstance(encoded, dict) else None
+
+
+class _RunningMerge:
+    """multi_track_merge as a running merge on the device: one accumulator each for the implicit output (with the winner
+    / best columns of its track channel), the abstract cloud and the global feature.  The latter two go through the same
+    entry point as flat contiguous (n, 1) views without squash or track column; an abstract cloud of None stays None."""
+
+    def __init__(self, raw, pcl_abstract, features_global):
+        n = raw.shape[0]
+        self.output = torch.empty((n, raw.shape[1]), dtype=torch.float32, device=raw.device)
+        self.best = torch.empty((n,), dtype=torch.float32, device=raw.device)
+        self.winner = torch.empty((n,), dtype=torch.float32, device=raw.device)
+        self.abstract = None if pcl_abstract is None else torch.empty(pcl_abstract.shape, dtype=torch.float32,
+                                                                      device=pcl_abstract.device)
+        self.features = torch.empty(features_global.shape, dtype=torch.float32, device=features_global.device)
+        self.runs = 0
+
+    def add(self, raw, pcl_abstract, features_global, inst_id, track_col, codes):
+        first = self.runs == 0
+        ops.track_merge_add(raw, self.output, self.best, self.winner, inst_id, track_col, codes, first=first)
+        for part, acc in ((pcl_abstract, self.abstract), (features_global, self.features)):
+            if acc is not None:
+                ops.track_merge_add(part.contiguous().view(-1, 1), acc.view(-1, 1), None, None, inst_id, -1, None, first=first)
+        self.runs += 1
+
+    def finish(self, track_col):
+        ops.track_merge_finish(self.output, self.winner, self.runs, track_col)
+        for acc in (self.abstract, self.features):
+            if acc is not None:
+                ops.track_merge_finish(acc.view(-1, 1), None, self.runs, -1)
+        return self.output
 
 
 def nn_target(points_query_xyz, target_xyz):
@@ -300,10 +360,10 @@ def multi_track_merge(track_instance_ids, pcl_abstract, features_global, implici
 
 def infer_device(pcl_input, points_query, pcl_net, implicit_net, batch_size, color_mode,
                  predict_segmentation=False, track_mode='none', semantic_classes=13, encoded=None,
-                 neighbour_lists=None):
+                 neighbour_lists=None, squash=True):
     """Device-resident core of perform_inference: encode once, decode every mini-batch, squash.
     All tensors are CUDA; returns CUDA tensors (implicit_output (N,G), pcl_abstract (M,3+E),
-    features_global (D))."""
+    features_global (D)).  squash=False: implicit_output holds the network's RAW outputs (the caller squashes)."""
     if encoded is not None:
         (pcl_abstract, features_global) = encoded
     else:
@@ -318,8 +378,9 @@ def infer_device(pcl_input, points_query, pcl_net, implicit_net, batch_size, col
         lists = tuple(None if a is None else torch.as_tensor(a).to(points_query.device) for a in neighbour_lists)
         assert len(lists) == 2 and all(a is None or a.shape[0] == n for a in lists)
     decode_batches(implicit_net, points_query, 0, n, batch_size, pcl_abstract, features_global, out, lists=lists)
-    ops.squash(out, squash_codes(implicit_net.d_out, color_mode, predict_segmentation, track_mode,
-                                 semantic_classes))
+    if squash:
+        ops.squash(out, squash_codes(implicit_net.d_out, color_mode, predict_segmentation, track_mode,
+                                     semantic_classes))
     return dict(implicit_output=out, pcl_abstract=pcl_abstract, features_global=features_global)
 
 

@@ -1232,6 +1232,50 @@ def id_histogram(rows, col, seg_offsets, n_ids, key=None, pred_col=-1, pred_valu
     return out
 
 
+def _merge_rows(t, name):
+    """(tensor, row stride) of a track-merge operand: used IN PLACE (never a copy), so its last dim must be contiguous."""
+    t = _dev(t, name=name)
+    assert t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1), '%s must be (n, g) with a contiguous last dim' % name
+    return t, (t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0)))
+
+
+def _merge_column(t, n, name):
+    if t is None:
+        return None
+    t = _dev(t, name=name)
+    assert tuple(t.shape) == (n,) and t.is_contiguous(), '%s must be a contiguous (%d,) tensor' % (name, n)
+    return t
+
+
+def track_merge_add(out, acc, best, winner, inst_id, track_col, codes=None, first=False):
+    """One rerun of track_mode 'all' onto the running merge (occ4d_track_merge_add_f32, include/occ4d_track.h): acc (n, g)
+    = / += squash(out (n, g)) with `codes` (g codes of ops.squash; None = identity), and on column `track_col` (-1: none) the
+    winner / best (n,) update with `inst_id`.  first=True starts the merge: acc, best and winner need no initial value.
+    `out` is left unchanged.  Returns acc."""
+    o, ld_out = _merge_rows(out, 'out')
+    a, ld_acc = _merge_rows(acc, 'acc')
+    n, g = o.shape
+    assert tuple(a.shape) == (n, g), 'acc must be %s like out, got %s' % ((n, g), tuple(a.shape))
+    b, w = _merge_column(best, n, 'best'), _merge_column(winner, n, 'winner')
+    assert float(int(inst_id)) == float(inst_id) and float(np.float32(int(inst_id))) == float(int(inst_id)), \
+        'inst_id = %r is not an integer an fp32 holds' % (inst_id,)
+    assert codes is None or len(codes) == g, 'codes must hold g = %d entries' % g
+    arr = None if codes is None else (C.c_int32 * g)(*[int(v) for v in codes])
+    _lib.check(_lib.lib().occ4d_track_merge_add_f32(_ptr(o), ld_out, n, g, arr, int(track_col), float(int(inst_id)), int(bool(first)),
+                                                    _ptr(a), ld_acc, _ptr(b), _ptr(w), _stream()))
+    return acc
+
+
+def track_merge_finish(acc, winner, n_runs, track_col):
+    """The end of the running merge, in place (occ4d_track_merge_finish_f32): acc /= float32(n_runs) as an IEEE division, then
+    column `track_col` (-1: none) = winner.  Returns acc."""
+    a, ld_acc = _merge_rows(acc, 'acc')
+    n, g = a.shape
+    w = _merge_column(winner, n, 'winner')
+    _lib.check(_lib.lib().occ4d_track_merge_finish_f32(_ptr(a), ld_acc, n, g, int(n_runs), int(track_col), _ptr(w), _stream()))
+    return acc
+
+
 def add_rows(a, b):
     """a + b for two (n, d) tensors (exact fp32 add; the sampler's query = target point + offset)."""
     a, lda = _rows(_dev(a, name='a'), 'a')
