@@ -13,6 +13,7 @@ FRONTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_fr
 EVAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_eval.h')
 OCCL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_occl.h')
 TRACK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_track.h')
+PROJECT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_project.h')
 
 
 class NativeLibraryError(RuntimeError):
@@ -176,6 +177,14 @@ except OSError as e:
     raise NativeLibraryError('include/occ4d_track.h not found at %s (%s): the ctypes binding is derived from it'
                              % (TRACK_HEADER_PATH, e))
 
+# the camera projection, the z-buffer and the visibility test (projection.py): include/occ4d_project.h
+try:
+    with open(PROJECT_HEADER_PATH) as _f:
+        PROJECT_SIGNATURES = parse_prototypes(_f.read(), {})
+except OSError as e:
+    raise NativeLibraryError('include/occ4d_project.h not found at %s (%s): the ctypes binding is derived from it'
+                             % (PROJECT_HEADER_PATH, e))
+
 _lib = None
 _twin = False            # True only after an explicit load_cpu_twin(): host pointers, no streams (cpu_twin.py)
 
@@ -185,10 +194,11 @@ def is_twin():
 
 
 def bind(handle, missing=None):
-    """Sets restype / argtypes of every symbol of SIGNATURES, FRONTEND_SIGNATURES, EVAL_SIGNATURES, OCCL_SIGNATURES and TRACK_SIGNATURES on a loaded library and returns it.  A symbol the library does
+    """Sets restype / argtypes of every symbol of SIGNATURES, FRONTEND_SIGNATURES, EVAL_SIGNATURES, OCCL_SIGNATURES, TRACK_SIGNATURES
+    and PROJECT_SIGNATURES on a loaded library and returns it.  A symbol the library does
     not export is a stale library (NativeLibraryError) unless `missing` is given: then missing(name) stands in for it."""
     for name, (res, args) in list(SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
-            list(OCCL_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()):
+            list(OCCL_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(PROJECT_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError:

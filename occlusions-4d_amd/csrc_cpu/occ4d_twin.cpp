@@ -27,10 +27,12 @@
 #include "occ4d_eval.h"
 #include "occ4d_occl.h"
 #include "occ4d_track.h"
+#include "occ4d_project.h"
 #include "frontend_math.hpp"      // csrc/: the front end's per-element arithmetic, the HIP kernels' own source
 #include "eval_math.hpp"          // csrc/: the evaluation statistics' per-row classification, likewise
 #include "occl_math.hpp"          // csrc/: the id histogram's per-row decision, likewise
 #include "track_math.hpp"         // csrc/: the track merge's squash and winner / best update, likewise
+#include "project_math.hpp"       // csrc/: the projection chain, the pixel rule, the z-buffer key and the visibility code, likewise
 
 namespace {
 
@@ -695,6 +697,119 @@ int occ4d_track_merge_finish_f32(float* acc, int64_t ld_acc, int n, int g, int n
     for (int c = 0; c < g; ++c) {
       float& v = acc[i * ld_acc + c];
       v = c == track_col ? winner[i] : v / runs;
+    }
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- projection
+// include/occ4d_project.h: the passes of csrc/project.hip over csrc/project_math.hpp, items in order; the atomic minimum of the
+// splat is a plain minimum here.
+static int project_check_points(const char* who, const float* rows, int64_t ld, int n, const float* rt, const float* k, int V) {
+  REQ(n >= 0 && V >= 0, "%s: n = %d, V = %d must be >= 0", who, n, V);
+  REQ(ld >= 3, "%s: ld = %lld must be >= 3", who, (long long)ld);
+  if (n == 0 || V == 0) return OCC4D_OK;
+  REQ(rows && rt && k, "%s: null rows / rt / k", who);
+  return OCC4D_OK;
+}
+static int project_check_image(const char* who, int V, int H, int W) {
+  namespace pj = occ4d_project;
+  REQ(H >= 1 && W >= 1 && H <= pj::MAX_SIDE && W <= pj::MAX_SIDE, "%s: H = %d, W = %d must be in 1 .. %d", who, H, W, pj::MAX_SIDE);
+  REQ((int64_t)V * H * W < ((int64_t)1 << 31), "%s: V H W = %lld must be < 2^31", who, (long long)V * H * W);
+  return OCC4D_OK;
+}
+int occ4d_project_points_f32(const float* rows, int64_t ld, int n, const float* rt, const float* k, int V, int flip_xy, float* uvz,
+                             void*) {
+  namespace pj = occ4d_project;
+  const char* who = "occ4d_project_points_f32";
+  TRY(project_check_points(who, rows, ld, n, rt, k, V));
+  if (n == 0 || V == 0) return OCC4D_OK;
+  REQ(uvz, "%s: null uvz", who);
+  for (int v = 0; v < V; ++v)
+    for (int64_t i = 0; i < n; ++i) {
+      const float* p = rows + i * ld;
+      float r[3];
+      pj::project(rt + 16 * v, k + 16 * v, p[0], p[1], p[2], r);
+      float* o = uvz + 3 * ((int64_t)v * n + i);
+      o[0] = flip_xy ? r[1] : r[0];
+      o[1] = flip_xy ? r[0] : r[1];
+      o[2] = r[2];
+    }
+  return OCC4D_OK;
+}
+int occ4d_zbuffer_splat_f32(const float* rows, int64_t ld, int n, const float* rt, const float* k, int V, int H, int W, int radius,
+                            unsigned long long* keys, void*) {
+  namespace pj = occ4d_project;
+  const char* who = "occ4d_zbuffer_splat_f32";
+  TRY(project_check_points(who, rows, ld, n, rt, k, V));
+  TRY(project_check_image(who, V, H, W));
+  REQ(radius >= 0 && radius <= pj::MAX_RADIUS, "%s: radius = %d must be in 0 .. %d", who, radius, pj::MAX_RADIUS);
+  if (n == 0 || V == 0) return OCC4D_OK;
+  REQ(keys, "%s: null keys", who);
+  for (int v = 0; v < V; ++v)
+    for (int64_t i = 0; i < n; ++i) {
+      const float* p = rows + i * ld;
+      float uvz[3];
+      int px, py;
+      pj::project(rt + 16 * v, k + 16 * v, p[0], p[1], p[2], uvz);
+      if (!pj::centre_pixel(uvz, H, W, &px, &py)) continue;
+      const unsigned long long key = pj::pack_key(uvz[2], (uint32_t)i);
+      const int x0 = std::max(px - radius, 0), x1 = std::min(px + radius, W - 1);
+      const int y0 = std::max(py - radius, 0), y1 = std::min(py + radius, H - 1);
+      unsigned long long* image = keys + (int64_t)v * H * W;
+      for (int y = y0; y <= y1; ++y)
+        for (int x = x0; x <= x1; ++x) {
+          unsigned long long& dst = image[(int64_t)y * W + x];
+          dst = std::min(dst, key);
+        }
+    }
+  return OCC4D_OK;
+}
+int occ4d_zbuffer_resolve_f32(const unsigned long long* keys, int V, int H, int W, const float* rows, int64_t ld, int n, int d,
+                              float depth_background, float* depth, int32_t* index, const int32_t* cols_host, int C,
+                              float feat_background, float* feat, void*) {
+  namespace pj = occ4d_project;
+  const char* who = "occ4d_zbuffer_resolve_f32";
+  REQ(n >= 0 && V >= 0, "%s: n = %d, V = %d must be >= 0", who, n, V);
+  TRY(project_check_image(who, V, H, W));
+  REQ(C >= 0 && C <= pj::MAX_CHANNELS, "%s: C = %d must be in 0 .. %d", who, C, pj::MAX_CHANNELS);
+  if (C > 0) {
+    REQ(cols_host && feat, "%s: null cols_host / feat with C = %d", who, C);
+    REQ(d >= 1 && ld >= d, "%s: d = %d, ld = %lld: need 1 <= d <= ld", who, d, (long long)ld);
+    REQ(rows || n == 0, "%s: null rows with C = %d", who, C);
+    for (int c = 0; c < C; ++c)
+      REQ(cols_host[c] >= 0 && cols_host[c] < d, "%s: column %d must be in 0 .. d - 1 = %d", who, cols_host[c], d - 1);
+  }
+  if (V == 0) return OCC4D_OK;
+  REQ(keys, "%s: null keys", who);
+  const int64_t pixels = (int64_t)V * H * W;
+  for (int64_t p = 0; p < pixels; ++p) {
+    const unsigned long long key = keys[p];
+    const bool background = pj::key_is_background(key, n);
+    if (depth) depth[p] = background ? depth_background : pj::key_depth(key);
+    if (index) index[p] = background ? -1 : (int32_t)pj::key_row(key);
+    for (int c = 0; c < C; ++c)
+      feat[p * C + c] = background ? feat_background : rows[(int64_t)pj::key_row(key) * ld + cols_host[c]];
+  }
+  return OCC4D_OK;
+}
+int occ4d_visibility_f32(const float* rows, int64_t ld, int n, const float* rt, const float* k, int V, const float* depth,
+                         int64_t ld_depth, int H, int W, float margin, int32_t* code, void*) {
+  namespace pj = occ4d_project;
+  const char* who = "occ4d_visibility_f32";
+  TRY(project_check_points(who, rows, ld, n, rt, k, V));
+  TRY(project_check_image(who, V, H, W));
+  REQ(ld_depth >= W, "%s: ld_depth = %lld must be >= W = %d", who, (long long)ld_depth, W);
+  if (n == 0 || V == 0) return OCC4D_OK;
+  REQ(depth && code, "%s: null depth / code", who);
+  for (int v = 0; v < V; ++v)
+    for (int64_t i = 0; i < n; ++i) {
+      const float* p = rows + i * ld;
+      float uvz[3];
+      int px = 0, py = 0;
+      pj::project(rt + 16 * v, k + 16 * v, p[0], p[1], p[2], uvz);
+      const bool inside = pj::centre_pixel(uvz, H, W, &px, &py);
+      const float dimg = inside ? depth[((int64_t)v * H + py) * ld_depth + px] : 0.f;
+      code[(int64_t)v * n + i] = pj::visibility_code(inside, uvz[2], dimg, margin);
     }
   return OCC4D_OK;
 }

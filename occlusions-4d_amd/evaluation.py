@@ -24,6 +24,7 @@ import torch
 from . import _lib
 from . import inference
 from . import ops
+from . import projection
 
 _EC = _lib.EVAL_CONSTANTS
 # target columns (R; G, B follow / mark_track / semantic tag, -1 = absent) of the two data kinds (eval/inference.py:96):
@@ -171,13 +172,20 @@ class EvalStats:
 
 
 def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt=False, reuse_encode=True, stats=None,
-                  stats_group_fn=None):
+                  stats_group_fn=None, stats_occlusion=None):
     """batch: dict with 'pcl_input' (1,N,8), 'pcl_input_sem' (1,N,1-3), 'pcl_target' list of (1,T,9-11) tensors and
     batch['meta_data']['pcl_target_size'] (list of (1,) tensors), as the reference's test data loader yields them
     (data/data_greater.py:593-606, data/data_carla.py:651-661).  args: namespace with the test_args fields used
     below (args.py:311-410).  Returns pcl_all (list over output frames of tuples of numpy arrays).
     stats: an EvalStats that every output frame is added to, scored against its target frame (on the device, beside the
-    decode); stats_group_fn(frame_rows) -> (T,) integer array: the group of every target point.  None: nothing is scored."""
+    decode); stats_group_fn(frame_rows) -> (T,) integer array: the group of every target point.  None: nothing is scored.
+    stats_occlusion: instead of stats_group_fn, a dict 'depth' (T_out, H, W), 'cam_RT' (T_out, 3, 4), 'cam_K' ((3, 3) or
+    (T_out, 3, 3)), 'margin': the group of a target point of output frame t is its projection.visibility code against depth[t]
+    under camera t (VISIBLE 0 / OCCLUDED 1 / OUTSIDE 2; `stats` needs n_groups >= 3), computed on the device."""
+    assert stats_group_fn is None or stats_occlusion is None, 'stats_group_fn and stats_occlusion exclude each other'
+    if stats_occlusion is not None and stats is not None:
+        assert stats.n_groups >= 3, 'stats_occlusion needs an EvalStats with n_groups >= 3, got %d' % stats.n_groups
+        occ_rt, occ_k = stats_occlusion['cam_RT'], stats_occlusion['cam_K']
     # One encode per clip is only equivalent to the reference's encode per output frame when the encode is
     # deterministic: a network built with fps_random_start=True (the constructor default; the reference's test path
     # builds its networks with False, eval/inference.py:59) draws a new FPS start per call, so it is re-encoded per frame.
@@ -196,7 +204,12 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
         frame = frame[:int(sizes[time_idx].item() if torch.is_tensor(sizes[time_idx]) else sizes[time_idx])]
         stats_kw = {}
         if stats is not None:
-            stats_kw = dict(stats=stats, stats_target=frame, stats_group=None if stats_group_fn is None else stats_group_fn(frame))
+            group = None if stats_group_fn is None else stats_group_fn(frame)
+            if stats_occlusion is not None:
+                group = projection.visibility(torch.from_numpy(np.ascontiguousarray(frame[:, :3])).to(stats.device),
+                                              stats_occlusion['depth'][time_idx], occ_rt[time_idx],
+                                              occ_k if np.ndim(occ_k) == 2 else occ_k[time_idx], stats_occlusion['margin'])[0]
+            stats_kw = dict(stats=stats, stats_target=frame, stats_group=group)
         res = inference.perform_inference(
             pcl_input.clone(), sem_inference, frame if save_gt else None, networks, device, 'if', args.min_z,
             args.cr_cube_bounds, args.color_mode, time_idx, logger, sample_implicit=args.sample_implicit,

@@ -1276,6 +1276,78 @@ def track_merge_finish(acc, winner, n_runs, track_col):
     return acc
 
 
+def _project_operands(rows, rt, k):
+    """(rows, row stride, n, rt, k, V) of the projection entry points (include/occ4d_project.h): rows (n, >= 3) fp32 with a
+    contiguous last dim, rt / k (V, 16) or (V, 4, 4) contiguous: the expanded 4 x 4 matrices."""
+    r, ld = _rows(_dev(rows, name='rows'), 'rows')
+    assert r.shape[1] >= 3, 'rows must start with x, y, z, got %d columns' % r.shape[1]
+    rt, k = _dev(rt, name='rt'), _dev(k, name='k')
+    V = rt.shape[0] if rt.dim() else -1
+    assert rt.dim() in (2, 3) and rt.numel() == V * 16 and tuple(k.shape) == tuple(rt.shape), \
+        'rt / k must both be (V, 16) or (V, 4, 4), got %s and %s' % (tuple(rt.shape), tuple(k.shape))
+    return r, max(ld, 3), r.shape[0], rt.contiguous(), k.contiguous(), V
+
+
+def project_points(rows, rt, k, flip_xy=False):
+    """(u, v, depth) of every row under every camera: -> (V, n, 3) (occ4d_project_points_f32); flip_xy: (v, u, depth)."""
+    r, ld, n, rt, k, V = _project_operands(rows, rt, k)
+    uvz = torch.empty((V, n, 3), dtype=torch.float32, device=r.device)
+    _lib.check(_lib.lib().occ4d_project_points_f32(_ptr(r), ld, n, _ptr(rt), _ptr(k), V, int(bool(flip_xy)), _ptr(uvz), _stream()))
+    return uvz
+
+
+def zbuffer_splat(rows, rt, k, height, width, radius=0, keys=None):
+    """The z-buffer's first pass (occ4d_zbuffer_splat_f32): every row's key (depth bits << 32 | row index) as an atomic minimum
+    onto the (2 radius + 1)^2 pixels around its centre.  -> keys (V, H, W) int64, the bit pattern of the unsigned keys (-1 =
+    all-ones = empty); allocated full of -1 unless the caller hands one in to splat further onto."""
+    r, ld, n, rt, k, V = _project_operands(rows, rt, k)
+    H, W = int(height), int(width)
+    if keys is None:
+        keys = torch.full((V, H, W), -1, dtype=torch.int64, device=r.device)
+    kk = _dev(keys, torch.int64, 'keys')
+    assert tuple(kk.shape) == (V, H, W) and kk.is_contiguous(), 'keys must be a contiguous (%d, %d, %d) int64 tensor' % (V, H, W)
+    _lib.check(_lib.lib().occ4d_zbuffer_splat_f32(_ptr(r), ld, n, _ptr(rt), _ptr(k), V, H, W, int(radius), _ptr(kk), _stream()))
+    return keys
+
+
+def zbuffer_resolve(keys, rows, channels=(), background=0.0, feature_background=None, want_depth=True, want_index=True):
+    """The z-buffer's second pass (occ4d_zbuffer_resolve_f32): keys (V, H, W) int64 -> (depth (V, H, W) fp32, index (V, H, W) int32,
+    features (V, H, W, C)) with C = len(channels) columns of `rows` gathered through the index.  Empty pixels, and pixels whose
+    index the n rows do not cover, hold `background` / -1 / `feature_background` (default: `background`)."""
+    kk = _dev(keys, torch.int64, 'keys')
+    assert kk.dim() == 3 and kk.is_contiguous(), 'keys must be a contiguous (V, H, W) int64 tensor'
+    V, H, W = kk.shape
+    r, ld = _rows(_dev(rows, name='rows'), 'rows')
+    n, d = r.shape
+    cols = [int(c) for c in channels]
+    n_ch = len(cols)
+    depth = torch.empty((V, H, W), dtype=torch.float32, device=kk.device) if want_depth else None
+    index = torch.empty((V, H, W), dtype=torch.int32, device=kk.device) if want_index else None
+    feat = torch.empty((V, H, W, n_ch), dtype=torch.float32, device=kk.device)
+    arr = (C.c_int32 * n_ch)(*cols) if n_ch else None
+    fbg = background if feature_background is None else feature_background
+    _lib.check(_lib.lib().occ4d_zbuffer_resolve_f32(_ptr(kk), V, H, W, _ptr(r), max(ld, d), n, d, float(background), _ptr(depth),
+                                                    _ptr(index), arr, n_ch, float(fbg), _ptr(feat) if n_ch else None, _stream()))
+    return depth, index, feat
+
+
+def visibility(rows, rt, k, depth, margin):
+    """Visibility code of every row under every camera against that camera's depth image (occ4d_visibility_f32): -> (V, n) int32,
+    0 visible, 1 occluded (the image holds a depth d > 0 at the row's pixel and depth - d > margin), 2 outside.  depth (V, H, W),
+    last dim contiguous, the H image rows evenly strided."""
+    r, ld, n, rt, k, V = _project_operands(rows, rt, k)
+    dep = _dev(depth, name='depth')
+    assert dep.dim() == 3 and dep.shape[0] == V, 'depth must be (V = %d, H, W), got %s' % (V, tuple(dep.shape))
+    _, H, W = dep.shape
+    ldd = dep.stride(1) if H > 1 else max(W, dep.stride(1))
+    if (W > 1 and dep.stride(2) != 1) or ldd < W or (V > 1 and dep.stride(0) != H * ldd):
+        dep, ldd = dep.contiguous(), W
+    code = torch.empty((V, n), dtype=torch.int32, device=r.device)
+    _lib.check(_lib.lib().occ4d_visibility_f32(_ptr(r), ld, n, _ptr(rt), _ptr(k), V, _ptr(dep), ldd, H, W, float(margin),
+                                               _ptr(code), _stream()))
+    return code
+
+
 def add_rows(a, b):
     """a + b for two (n, d) tensors (exact fp32 add; the sampler's query = target point + offset)."""
     a, lda = _rows(_dev(a, name='a'), 'a')
