@@ -8,12 +8,18 @@ import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libocc4d.so')
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d.h')
-FRONTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_frontend.h')
-EVAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_eval.h')
-OCCL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_occl.h')
-TRACK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_track.h')
-PROJECT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'occ4d_project.h')
+INCLUDE = os.path.join(os.path.dirname(_HERE), 'include')
+HEADER_PATH = os.path.join(INCLUDE, 'occ4d.h')
+# The feature headers beside occ4d.h (whose symbol set and ABI_VERSION stay as they are): attribute prefix -> file.  Same
+# conventions, same parser, same two libraries.  <PREFIX>_HEADER_PATH, <PREFIX>_SIGNATURES and <PREFIX>_CONSTANTS (the header's
+# `#define OCC4D_<PREFIX>_*` without that prefix) are made from this table below; a new header is a new row here.
+FEATURE_HEADERS = {
+    'FRONTEND': 'occ4d_frontend.h',     # the clip front end (frontend.py)
+    'EVAL': 'occ4d_eval.h',             # the evaluation statistics (evaluation.EvalStats); the constants: the layout of the two arrays
+    'OCCL': 'occ4d_occl.h',             # the id histogram behind the live occlusion fractions (occlusion.py); the bin limit, the extra bins
+    'TRACK': 'occ4d_track.h',           # the running merge of the per-instance reruns (inference.perform_inference, track_mode 'all')
+    'PROJECT': 'occ4d_project.h',       # the camera projection, the z-buffer and the visibility test (projection.py)
+}
 
 
 class NativeLibraryError(RuntimeError):
@@ -80,11 +86,16 @@ def parse_prototypes(text, structs):
     return out
 
 
-try:
-    with open(HEADER_PATH) as _f:
-        _HEADER = _f.read()
-except OSError as e:
-    raise NativeLibraryError('include/occ4d.h not found at %s (%s): the ctypes binding is derived from it' % (HEADER_PATH, e))
+def _read_header(path):
+    try:
+        with open(path) as f:
+            return f.read()
+    except OSError as e:
+        raise NativeLibraryError('include/%s not found at %s (%s): the ctypes binding is derived from it'
+                                 % (os.path.basename(path), path, e))
+
+
+_HEADER = _read_header(HEADER_PATH)
 
 # ABI_VERSION, OK / EINVAL / ELAUNCH, PATH_*, PROFILE_*, MAX_BLOCKS, MAX_CROSS: the header's `#define OCC4D_*` become module
 # attributes of the same name without the prefix (tests/test_abi.py pins their values)
@@ -138,52 +149,18 @@ class DecoderWeights(C.Structure):
 SIGNATURES = parse_prototypes(_HEADER, {'occ4d_linear_args': LinearArgs, 'occ4d_pt_layer_weights': PtLayerWeights,
                                         'occ4d_launch_events': LaunchEvents, 'occ4d_decoder_weights': DecoderWeights})
 
-# the clip front end (frontend.py) has a header of its own, include/occ4d_frontend.h: occ4d.h's symbol set and ABI_VERSION
-# stay as they are.  Same conventions, same parser, same two libraries.
-try:
-    with open(FRONTEND_HEADER_PATH) as _f:
-        FRONTEND_SIGNATURES = parse_prototypes(_f.read(), {})
-except OSError as e:
-    raise NativeLibraryError('include/occ4d_frontend.h not found at %s (%s): the ctypes binding is derived from it'
-                             % (FRONTEND_HEADER_PATH, e))
-
-# the evaluation statistics (evaluation.EvalStats) likewise: include/occ4d_eval.h, whose `#define OCC4D_EVAL_*` give the layout
-# of the two statistics arrays (EVAL_CONSTANTS: the names without the OCC4D_EVAL_ prefix)
-try:
-    with open(EVAL_HEADER_PATH) as _f:
-        _EVAL_HEADER = _f.read()
-except OSError as e:
-    raise NativeLibraryError('include/occ4d_eval.h not found at %s (%s): the ctypes binding is derived from it'
-                             % (EVAL_HEADER_PATH, e))
-EVAL_SIGNATURES = parse_prototypes(_EVAL_HEADER, {})
-EVAL_CONSTANTS = {k[len('EVAL_'):]: v for k, v in parse_constants(_EVAL_HEADER).items()}
-
-# the id histogram behind the live occlusion fractions (occlusion.py): include/occ4d_occl.h, whose `#define OCC4D_OCCL_*` give
-# the bin limit and the two extra bins (OCCL_CONSTANTS: the names without the OCC4D_OCCL_ prefix)
-try:
-    with open(OCCL_HEADER_PATH) as _f:
-        _OCCL_HEADER = _f.read()
-except OSError as e:
-    raise NativeLibraryError('include/occ4d_occl.h not found at %s (%s): the ctypes binding is derived from it'
-                             % (OCCL_HEADER_PATH, e))
-OCCL_SIGNATURES = parse_prototypes(_OCCL_HEADER, {})
-OCCL_CONSTANTS = {k[len('OCCL_'):]: v for k, v in parse_constants(_OCCL_HEADER).items()}
-
-# the running merge of the per-instance reruns (inference.perform_inference, track_mode 'all'): include/occ4d_track.h
-try:
-    with open(TRACK_HEADER_PATH) as _f:
-        TRACK_SIGNATURES = parse_prototypes(_f.read(), {})
-except OSError as e:
-    raise NativeLibraryError('include/occ4d_track.h not found at %s (%s): the ctypes binding is derived from it'
-                             % (TRACK_HEADER_PATH, e))
-
-# the camera projection, the z-buffer and the visibility test (projection.py): include/occ4d_project.h
-try:
-    with open(PROJECT_HEADER_PATH) as _f:
-        PROJECT_SIGNATURES = parse_prototypes(_f.read(), {})
-except OSError as e:
-    raise NativeLibraryError('include/occ4d_project.h not found at %s (%s): the ctypes binding is derived from it'
-                             % (PROJECT_HEADER_PATH, e))
+# ... and every symbol any header declares; two headers that declare the same one are an error
+ALL_SIGNATURES = dict(SIGNATURES)
+for _prefix, _name in FEATURE_HEADERS.items():
+    _path = os.path.join(INCLUDE, _name)
+    _text = _read_header(_path)
+    _table = parse_prototypes(_text, {})
+    _twice = sorted(set(_table) & set(ALL_SIGNATURES))
+    if _twice:
+        raise NativeLibraryError('include/%s declares %s, which another header declares too' % (_name, ', '.join(_twice)))
+    ALL_SIGNATURES.update(_table)
+    globals().update({_prefix + '_HEADER_PATH': _path, _prefix + '_SIGNATURES': _table,
+                      _prefix + '_CONSTANTS': {k[len(_prefix) + 1:]: v for k, v in parse_constants(_text).items()}})
 
 _lib = None
 _twin = False            # True only after an explicit load_cpu_twin(): host pointers, no streams (cpu_twin.py)
@@ -194,11 +171,9 @@ def is_twin():
 
 
 def bind(handle, missing=None):
-    """Sets restype / argtypes of every symbol of SIGNATURES, FRONTEND_SIGNATURES, EVAL_SIGNATURES, OCCL_SIGNATURES, TRACK_SIGNATURES
-    and PROJECT_SIGNATURES on a loaded library and returns it.  A symbol the library does
+    """Sets restype / argtypes of every symbol of ALL_SIGNATURES on a loaded library and returns it.  A symbol the library does
     not export is a stale library (NativeLibraryError) unless `missing` is given: then missing(name) stands in for it."""
-    for name, (res, args) in list(SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
-            list(OCCL_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(PROJECT_SIGNATURES.items()):
+    for name, (res, args) in ALL_SIGNATURES.items():
         try:
             fn = getattr(handle, name)
         except AttributeError:

@@ -46,8 +46,7 @@ def _stale(target, deps):
 def build(force=False, verbose=True):
     os.makedirs(OBJDIR, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hpp')]
-    headers += [os.path.join(INCLUDE, f) for f in ('occ4d.h', 'occ4d_frontend.h', 'occ4d_eval.h', 'occ4d_occl.h', 'occ4d_track.h',
-                                                      'occ4d_project.h')]
+    headers += [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.startswith('occ4d') and f.endswith('.h')]
     jobs = []
     objs = []
     for src in sources():

@@ -24,7 +24,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, 'csrc_cpu', 'occ4d_twin.cpp')
 LIB = os.path.join(HERE, 'libocc4d_cpu.so')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
-CSRC = os.path.join(HERE, 'csrc')             # frontend_math.hpp, eval_math.hpp, occl_math.hpp, track_math.hpp, project_math.hpp: per-element source shared with the HIP kernels
+CSRC = os.path.join(HERE, 'csrc')             # contract.hpp and the *_math.hpp: source shared with the HIP kernels
 # -ffp-contract=off: the kNN / FPS distance expressions are pinned without FMA, only std::fma fuses
 # -march=x86-64-v3 (AVX2 + FMA units for the explicit std::fma), not -march=native: the .so built in the build container
 # travels to the GPU box with the tree
@@ -32,10 +32,8 @@ FLAGS = ['-O3', '-std=c++17', '-fopenmp', '-fPIC', '-shared', '-ffp-contract=off
 
 
 def build(force=False):
-    deps = [SRC, os.path.join(INCLUDE, 'occ4d.h'), os.path.join(INCLUDE, 'occ4d_frontend.h'), os.path.join(INCLUDE, 'occ4d_eval.h'),
-            os.path.join(INCLUDE, 'occ4d_occl.h'), os.path.join(INCLUDE, 'occ4d_track.h'), os.path.join(INCLUDE, 'occ4d_project.h'),
-            os.path.join(CSRC, 'frontend_math.hpp'), os.path.join(CSRC, 'project_math.hpp'),
-            os.path.join(CSRC, 'eval_math.hpp'), os.path.join(CSRC, 'occl_math.hpp'), os.path.join(CSRC, 'track_math.hpp')]
+    deps = [SRC] + [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.startswith('occ4d') and f.endswith('.h')]
+    deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hpp')]
     if force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         gxx = shutil.which('g++')
         if gxx is None:

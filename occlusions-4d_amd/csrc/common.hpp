@@ -4,11 +4,9 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include "occ4d.h"
+#include "contract.hpp"      // occ4d::set_error, OCC4D_REQUIRE, OCC4D_TRY
 
 namespace occ4d {
-
-void set_error(const char* fmt, ...);
 
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
@@ -18,14 +16,6 @@ inline int check_launch(const char* what) {
   }
   return OCC4D_OK;
 }
-
-#define OCC4D_REQUIRE(cond, ...)        \
-  do {                                  \
-    if (!(cond)) {                      \
-      occ4d::set_error(__VA_ARGS__);    \
-      return OCC4D_EINVAL;              \
-    }                                   \
-  } while (0)
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 

@@ -1,10 +1,12 @@
-// Per-row classification of the evaluation statistics (include/occ4d_eval.h), shared WORD FOR WORD by the HIP kernels
-// (csrc/evalstats.hip) and the g++ twin (csrc_cpu/occ4d_twin.cpp): which counters a row touches and what it adds to the
-// sums.  Comparisons are fp32; every term of a sum is converted to double before any arithmetic.
+// Per-row classification of the evaluation statistics (include/occ4d_eval.h) and the entry points' argument contracts (host
+// only), shared WORD FOR WORD by the HIP kernels (csrc/evalstats.hip) and the g++ twin (csrc_cpu/occ4d_twin.cpp): which
+// counters a row touches and what it adds to the sums.  Comparisons are fp32; every term of a sum is converted to double
+// before any arithmetic.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
+#include "contract.hpp"
 #include "occ4d_eval.h"
 
 #if defined(__HIPCC__)
@@ -85,6 +87,51 @@ OCC4D_EVAL_HD QueryRow classify_query(const QueryArgs& a, int i) {
     }
   }
   return r;
+}
+
+// ---- argument contracts (host): the status, `empty` = nothing to do
+inline bool layout_ok(int n_groups, int n_classes) {
+  return n_groups >= 1 && n_groups <= OCC4D_EVAL_MAX_GROUPS && n_classes >= 0 && n_classes <= OCC4D_EVAL_MAX_CLASSES;
+}
+inline int64_t counts_len(int n_groups, int n_classes) {
+  return layout_ok(n_groups, n_classes) ? OCC4D_EVAL_HEAD + n_groups * group_stride(n_classes) : -1;
+}
+inline int64_t sums_len(int n_groups) { return layout_ok(n_groups, 0) ? (int64_t)n_groups * OCC4D_EVAL_GROUP_SUMS : -1; }
+
+// fills `a`, its col_* reduced to -1 where the flags or the class count switch the statistic off
+inline int check_query_stats(const float* out, int64_t ldo, int n, int g_out, const int32_t* nn_idx, const float* nn_dist,
+                             const float* target, int64_t ldt, int m, int dt, int col_rgb, int col_track, int col_sem, int out_track,
+                             const int32_t* target_group, int n_groups, int n_classes, float density_threshold, float radius,
+                             int flags, const int64_t* counts, const double* sums, const void* workspace, bool& empty, QueryArgs& a) {
+  const char* who = "occ4d_eval_query_stats_f32";
+  OCC4D_REQUIRE(layout_ok(n_groups, n_classes), "%s: n_groups = %d must be in 1 .. 8, n_classes = %d in 0 .. 32", who, n_groups, n_classes);
+  OCC4D_REQUIRE(n >= 0 && m >= 0 && g_out >= 1 && dt >= 1 && ldo >= g_out && ldt >= dt, "%s: n = %d, m = %d, g_out = %d, ldo = %lld, dt = %d, ldt = %lld",
+                who, n, m, g_out, (long long)ldo, dt, (long long)ldt);
+  OCC4D_REQUIRE(counts && sums && workspace && ((uintptr_t)workspace % 8) == 0, "%s: null counts / sums / workspace, or workspace not 8-byte aligned", who);
+  empty = n == 0;
+  if (empty) return OCC4D_OK;
+  OCC4D_REQUIRE(out && nn_idx && nn_dist && (target || m == 0), "%s: null pointer", who);
+  const bool color = (flags & OCC4D_EVAL_FLAG_COLOR) && col_rgb >= 0;
+  const bool track = (flags & OCC4D_EVAL_FLAG_TRACK) && col_track >= 0;
+  const bool seg = (flags & OCC4D_EVAL_FLAG_SEG) && col_sem >= 0 && n_classes >= 1;
+  OCC4D_REQUIRE(!color || (g_out >= 4 && col_rgb + 3 <= dt), "%s: colour needs g_out = %d >= 4 and col_rgb = %d + 3 <= dt = %d", who, g_out, col_rgb, dt);
+  OCC4D_REQUIRE(!track || (out_track >= 0 && out_track < g_out && col_track < dt), "%s: tracking needs out_track = %d < g_out = %d and col_track = %d < dt = %d",
+                who, out_track, g_out, col_track, dt);
+  OCC4D_REQUIRE(!seg || (g_out >= n_classes && col_sem < dt), "%s: segmentation needs g_out = %d >= n_classes = %d and col_sem = %d < dt = %d", who,
+                g_out, n_classes, col_sem, dt);
+  a = QueryArgs{out, ldo, n, g_out, nn_idx, nn_dist, target, ldt, m, color ? col_rgb : -1, track ? col_track : -1,
+                seg ? col_sem : -1, out_track, target_group, n_groups, n_classes, density_threshold, radius};
+  return OCC4D_OK;
+}
+
+inline int check_target_stats(const float* dist, int m, int n_groups, int n_classes, const int64_t* counts, const double* sums,
+                              const void* workspace, bool& empty) {
+  const char* who = "occ4d_eval_target_stats_f32";
+  OCC4D_REQUIRE(layout_ok(n_groups, n_classes), "%s: n_groups = %d must be in 1 .. 8, n_classes = %d in 0 .. 32", who, n_groups, n_classes);
+  OCC4D_REQUIRE(m >= 0 && counts && sums && workspace && ((uintptr_t)workspace % 8) == 0, "%s: m = %d, null counts / sums / workspace, or workspace not 8-byte aligned", who, m);
+  empty = m == 0;
+  OCC4D_REQUIRE(empty || dist, "%s: null pointer", who);
+  return OCC4D_OK;
 }
 
 }  // namespace occ4d_eval

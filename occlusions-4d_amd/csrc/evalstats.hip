@@ -1,6 +1,6 @@
 // Evaluation statistics (include/occ4d_eval.h): one grid-stride pass over the decoded queries / the target points of a
-// frame, accumulated onto the caller's int64 counts and double sums.  The per-row decisions are csrc/eval_math.hpp, shared
-// with the g++ twin.
+// frame, accumulated onto the caller's int64 counts and double sums.  The per-row decisions and the argument contracts are
+// csrc/eval_math.hpp, shared with the g++ twin.
 //
 // Counts: int32 in LDS per workgroup (a workgroup sees at most n / gridDim + 256 < 2^31 rows), the non-zero ones added to
 // the int64 totals with integer atomics -- order-free.
@@ -153,17 +153,11 @@ __global__ __launch_bounds__(THREADS) void finish_kernel(const double* __restric
   }
 }
 
-bool layout_ok(int n_groups, int n_classes) {
-  return n_groups >= 1 && n_groups <= OCC4D_EVAL_MAX_GROUPS && n_classes >= 0 && n_classes <= OCC4D_EVAL_MAX_CLASSES;
-}
-
 }  // namespace
 
-extern "C" int64_t occ4d_eval_counts_len(int n_groups, int n_classes) {
-  return layout_ok(n_groups, n_classes) ? OCC4D_EVAL_HEAD + n_groups * ev::group_stride(n_classes) : -1;
-}
+extern "C" int64_t occ4d_eval_counts_len(int n_groups, int n_classes) { return ev::counts_len(n_groups, n_classes); }
 
-extern "C" int64_t occ4d_eval_sums_len(int n_groups) { return layout_ok(n_groups, 0) ? (int64_t)n_groups * OCC4D_EVAL_GROUP_SUMS : -1; }
+extern "C" int64_t occ4d_eval_sums_len(int n_groups) { return ev::sums_len(n_groups); }
 
 extern "C" int64_t occ4d_eval_workspace_bytes(int n) {
   if (n < 0) return -1;
@@ -176,42 +170,28 @@ extern "C" int occ4d_eval_query_stats_f32(const float* out, int64_t ldo, int n, 
                                           int out_track, const int32_t* target_group, int n_groups, int n_classes,
                                           float density_threshold, float radius, int flags, int64_t* counts, double* sums,
                                           void* workspace, void* stream) {
-  const char* who = "occ4d_eval_query_stats_f32";
-  OCC4D_REQUIRE(layout_ok(n_groups, n_classes), "%s: n_groups = %d must be in 1 .. 8, n_classes = %d in 0 .. 32", who, n_groups, n_classes);
-  OCC4D_REQUIRE(n >= 0 && m >= 0 && g_out >= 1 && dt >= 1 && ldo >= g_out && ldt >= dt, "%s: n = %d, m = %d, g_out = %d, ldo = %lld, dt = %d, ldt = %lld",
-                who, n, m, g_out, (long long)ldo, dt, (long long)ldt);
-  OCC4D_REQUIRE(counts && sums && workspace && ((uintptr_t)workspace % 8) == 0, "%s: null counts / sums / workspace, or workspace not 8-byte aligned", who);
-  if (n == 0) return OCC4D_OK;
-  OCC4D_REQUIRE(out && nn_idx && nn_dist && (target || m == 0), "%s: null pointer", who);
-  const bool color = (flags & OCC4D_EVAL_FLAG_COLOR) && col_rgb >= 0;
-  const bool track = (flags & OCC4D_EVAL_FLAG_TRACK) && col_track >= 0;
-  const bool seg = (flags & OCC4D_EVAL_FLAG_SEG) && col_sem >= 0 && n_classes >= 1;
-  OCC4D_REQUIRE(!color || (g_out >= 4 && col_rgb + 3 <= dt), "%s: colour needs g_out = %d >= 4 and col_rgb = %d + 3 <= dt = %d", who, g_out, col_rgb, dt);
-  OCC4D_REQUIRE(!track || (out_track >= 0 && out_track < g_out && col_track < dt), "%s: tracking needs out_track = %d < g_out = %d and col_track = %d < dt = %d",
-                who, out_track, g_out, col_track, dt);
-  OCC4D_REQUIRE(!seg || (g_out >= n_classes && col_sem < dt), "%s: segmentation needs g_out = %d >= n_classes = %d and col_sem = %d < dt = %d", who,
-                g_out, n_classes, col_sem, dt);
-  const ev::QueryArgs a{out, ldo, n, g_out, nn_idx, nn_dist, target, ldt, m, color ? col_rgb : -1, track ? col_track : -1,
-                        seg ? col_sem : -1, out_track, target_group, n_groups, n_classes, density_threshold, radius};
+  ev::QueryArgs a; bool empty;
+  OCC4D_TRY(ev::check_query_stats(out, ldo, n, g_out, nn_idx, nn_dist, target, ldt, m, dt, col_rgb, col_track, col_sem, out_track,
+                                  target_group, n_groups, n_classes, density_threshold, radius, flags, counts, sums, workspace,
+                                  empty, a));
+  if (empty) return OCC4D_OK;
   const int blocks = grid_for(n);
   const size_t lds = (size_t)(n_groups * ev::group_stride(n_classes) + 1) * sizeof(int);
   double* partial = static_cast<double*>(workspace);
   query_stats_kernel<<<blocks, THREADS, lds, (hipStream_t)stream>>>(a, counts, partial);
   finish_kernel<<<1, THREADS, 0, (hipStream_t)stream>>>(partial, blocks, QUERY_SUMS, n_groups, OCC4D_EVAL_SUM_ACCURACY_D, sums);
-  return occ4d::check_launch(who);
+  return occ4d::check_launch("occ4d_eval_query_stats_f32");
 }
 
 extern "C" int occ4d_eval_target_stats_f32(const float* dist, int m, const int32_t* target_group, int n_groups, int n_classes,
                                            int64_t* counts, double* sums, void* workspace, void* stream) {
-  const char* who = "occ4d_eval_target_stats_f32";
-  OCC4D_REQUIRE(layout_ok(n_groups, n_classes), "%s: n_groups = %d must be in 1 .. 8, n_classes = %d in 0 .. 32", who, n_groups, n_classes);
-  OCC4D_REQUIRE(m >= 0 && counts && sums && workspace && ((uintptr_t)workspace % 8) == 0, "%s: m = %d, null counts / sums / workspace, or workspace not 8-byte aligned", who, m);
-  if (m == 0) return OCC4D_OK;
-  OCC4D_REQUIRE(dist, "%s: null pointer", who);
+  bool empty;
+  OCC4D_TRY(ev::check_target_stats(dist, m, n_groups, n_classes, counts, sums, workspace, empty));
+  if (empty) return OCC4D_OK;
   const int blocks = grid_for(m);
   const size_t lds = (size_t)(n_groups * ev::group_stride(n_classes) + 1) * sizeof(int);
   double* partial = static_cast<double*>(workspace);
   target_stats_kernel<<<blocks, THREADS, lds, (hipStream_t)stream>>>(dist, m, target_group, n_groups, n_classes, counts, partial);
   finish_kernel<<<1, THREADS, 0, (hipStream_t)stream>>>(partial, blocks, TARGET_SUMS, n_groups, OCC4D_EVAL_SUM_COMPLETENESS_D, sums);
-  return occ4d::check_launch(who);
+  return occ4d::check_launch("occ4d_eval_target_stats_f32");
 }

@@ -1,6 +1,6 @@
 // The clip front end (include/occ4d_frontend.h): RGB-D frames / lidar sweeps -> cloud rows + keep keys.  Element-wise,
-// one thread per pixel / lidar row, every access behind a bounds check, no shared state.  The arithmetic is
-// csrc/frontend_math.hpp, shared with the g++ twin.
+// one thread per pixel / lidar row, every access behind a bounds check, no shared state.  The arithmetic, the lidar row and
+// the argument contracts are csrc/frontend_math.hpp, shared with the g++ twin.
 #include "common.hpp"
 #include "frontend_math.hpp"
 #include "occ4d_frontend.h"
@@ -9,7 +9,7 @@ namespace {
 
 namespace fe = occ4d_frontend;
 
-constexpr int MAX_CLUSTERS = 64;
+constexpr int MAX_CLUSTERS = fe::MAX_CLUSTERS;
 
 struct RgbdArgs {
   const float* depth; const float* rgb; const float* flat; const float* k_inv; const float* rt_inv; const float* clusters;
@@ -55,14 +55,7 @@ __global__ __launch_bounds__(256) void lidar_rows_kernel(const float* __restrict
                                                          float* __restrict__ key) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float* src = rows + i * ld;
-  float* dst = out + i * ldo;
-  float xyz[3] = {src[0], src[1], src[2]};
-  if (transform) fe::lidar_transform(source.m, inv_target.m, xyz);
-  if (z_offset != 0.f) xyz[2] += z_offset;
-  dst[0] = xyz[0]; dst[1] = xyz[1]; dst[2] = xyz[2];
-  for (int c2 = 3; c2 < d; ++c2) dst[c2] = src[c2];
-  key[i] = (!filter || fe::in_cuboid(xyz, c.x_min, c.x_max, c.y_min, c.y_max, c.z_min, c.z_max, false)) ? 1.f : 0.f;
+  fe::lidar_row(rows, ld, d, source.m, inv_target.m, transform != 0, z_offset, filter != 0, c, out, ldo, key, i);
 }
 
 }  // namespace
@@ -71,13 +64,10 @@ extern "C" int occ4d_rgbd_rows_f32(const float* depth, const float* rgb, const f
                                    const float* hue_clusters, int n_clusters, int T, int H, int W, float x_min, float x_max,
                                    float y_min, float y_max, float z_min, float z_max, int floor_fix, int view_idx,
                                    float* out_rows, float* out_target, float* out_key, void* stream) {
-  OCC4D_REQUIRE(depth && rgb && k_inv && rt_inv && out_rows && out_key, "occ4d_rgbd_rows_f32: null pointer");
-  OCC4D_REQUIRE(T >= 0 && H >= 1 && W >= 1 && (int64_t)T * H * W < ((int64_t)1 << 31), "occ4d_rgbd_rows_f32: T = %d, H = %d, W = %d", T, H, W);
-  OCC4D_REQUIRE(!flat || (hue_clusters && n_clusters >= 1 && n_clusters <= MAX_CLUSTERS),
-                "occ4d_rgbd_rows_f32: n_clusters = %d must be in 1 .. %d", n_clusters, MAX_CLUSTERS);
+  int64_t total;
+  OCC4D_TRY(fe::check_rgbd_rows(depth, rgb, flat, k_inv, rt_inv, hue_clusters, n_clusters, T, H, W, out_rows, out_key, total));
   OCC4D_REQUIRE(((uintptr_t)out_rows % 16) == 0 && (!out_target || ((uintptr_t)out_target % 16) == 0),
                 "occ4d_rgbd_rows_f32: output rows must be 16-byte aligned");
-  const int64_t total = (int64_t)T * H * W;
   if (total == 0) return OCC4D_OK;
   const RgbdArgs a{depth, rgb, flat, k_inv, rt_inv, hue_clusters, flat ? n_clusters : 0, H, W, total, x_min, x_max, y_min, y_max,
                    z_min, z_max, floor_fix, (float)view_idx, out_rows, out_target, out_key};
@@ -89,12 +79,9 @@ extern "C" int occ4d_rgbd_rows_f32(const float* depth, const float* rgb, const f
 extern "C" int occ4d_lidar_rows_f32(const float* rows, int64_t ld, int n, int d, const float* source, const float* inv_target,
                                     float z_offset, int cube_mode, double min_z, double other_bounds, float* out_rows,
                                     int64_t ldo, float* out_key, void* stream) {
-  OCC4D_REQUIRE(rows && out_rows && out_key, "occ4d_lidar_rows_f32: null pointer");
-  OCC4D_REQUIRE(n >= 0 && d >= 3 && ld >= d && ldo >= d, "occ4d_lidar_rows_f32: n = %d, d = %d, ld = %lld, ldo = %lld", n, d,
-                (long long)ld, (long long)ldo);
-  OCC4D_REQUIRE((source != nullptr) == (inv_target != nullptr), "occ4d_lidar_rows_f32: source and inv_target go together");
-  OCC4D_REQUIRE(cube_mode >= 0 && cube_mode <= 4, "occ4d_lidar_rows_f32: cube_mode %d (0 = no filter, 1 .. 4)", cube_mode);
-  if (n == 0) return OCC4D_OK;
+  bool empty;
+  OCC4D_TRY(fe::check_lidar_rows(rows, ld, n, d, source, inv_target, cube_mode, out_rows, ldo, out_key, empty));
+  if (empty) return OCC4D_OK;
   Mat4 s{}, it{};
   if (source) {
     for (int k = 0; k < 16; ++k) { s.m[k] = source[k]; it.m[k] = inv_target[k]; }

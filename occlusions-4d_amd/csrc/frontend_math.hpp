@@ -1,9 +1,12 @@
-// Per-element arithmetic of the clip front end (include/occ4d_frontend.h), shared WORD FOR WORD by the HIP kernels
-// (csrc/frontend.hip) and the g++ twin (csrc_cpu/occ4d_twin.cpp): both are compiled with -ffp-contract=off, so only the
-// explicit fmaf() below fuses and the two agree bit for bit with each other and with the reference's numpy results.
+// Per-element arithmetic of the clip front end (include/occ4d_frontend.h), the lidar row and the two entry points' argument
+// contracts (host only), shared WORD FOR WORD by the HIP kernels (csrc/frontend.hip) and the g++ twin
+// (csrc_cpu/occ4d_twin.cpp): both are compiled with -ffp-contract=off, so only the explicit fmaf() below fuses and the two
+// agree bit for bit with each other and with the reference's numpy results.
 #pragma once
 #include <math.h>
 #include <stdint.h>
+
+#include "contract.hpp"
 
 #if defined(__HIPCC__)
 #define OCC4D_HD __host__ __device__ __forceinline__
@@ -106,6 +109,46 @@ inline Cuboid carla_input_cuboid(int cube_mode, double min_z, double ob) {
                z_hi[5] = {0, 0.5, 0.6, 0.5, 0.5};
   return Cuboid{(float)(-ob * x_lo[cube_mode]), (float)(ob * x_hi[cube_mode]), (float)(-ob * y_hi[cube_mode]),
                 (float)(ob * y_hi[cube_mode]), (float)min_z, (float)(ob * z_hi[cube_mode])};
+}
+
+// one lidar row i: the optional transform and ground offset on x, y, z, the other d - 3 columns copied, the cuboid key
+OCC4D_HD void lidar_row(const float* __restrict__ rows, int64_t ld, int d, const float* source, const float* inv_target,
+                        bool transform, float z_offset, bool filter, const Cuboid& c, float* __restrict__ out, int64_t ldo,
+                        float* __restrict__ key, int64_t i) {
+  const float* src = rows + i * ld;
+  float* dst = out + i * ldo;
+  float xyz[3] = {src[0], src[1], src[2]};
+  if (transform) lidar_transform(source, inv_target, xyz);
+  if (z_offset != 0.f) xyz[2] += z_offset;
+  dst[0] = xyz[0]; dst[1] = xyz[1]; dst[2] = xyz[2];
+  for (int k = 3; k < d; ++k) dst[k] = src[k];
+  key[i] = (!filter || in_cuboid(xyz, c.x_min, c.x_max, c.y_min, c.y_max, c.z_min, c.z_max, false)) ? 1.f : 0.f;
+}
+
+// ---- argument contracts (host): the status, and what the call covers
+constexpr int MAX_CLUSTERS = 64;
+
+// total = T * H * W pixels; 0: nothing to do (libocc4d.so checks its outputs' alignment before it says so)
+inline int check_rgbd_rows(const float* depth, const float* rgb, const float* flat, const float* k_inv, const float* rt_inv,
+                           const float* hue_clusters, int n_clusters, int T, int H, int W, const float* out_rows,
+                           const float* out_key, int64_t& total) {
+  OCC4D_REQUIRE(depth && rgb && k_inv && rt_inv && out_rows && out_key, "occ4d_rgbd_rows_f32: null pointer");
+  OCC4D_REQUIRE(T >= 0 && H >= 1 && W >= 1 && (int64_t)T * H * W < ((int64_t)1 << 31), "occ4d_rgbd_rows_f32: T = %d, H = %d, W = %d", T, H, W);
+  OCC4D_REQUIRE(!flat || (hue_clusters && n_clusters >= 1 && n_clusters <= MAX_CLUSTERS),
+                "occ4d_rgbd_rows_f32: n_clusters = %d must be in 1 .. %d", n_clusters, MAX_CLUSTERS);
+  total = (int64_t)T * H * W;
+  return OCC4D_OK;
+}
+
+inline int check_lidar_rows(const float* rows, int64_t ld, int n, int d, const float* source, const float* inv_target, int cube_mode,
+                            const float* out_rows, int64_t ldo, const float* out_key, bool& empty) {
+  OCC4D_REQUIRE(rows && out_rows && out_key, "occ4d_lidar_rows_f32: null pointer");
+  OCC4D_REQUIRE(n >= 0 && d >= 3 && ld >= d && ldo >= d, "occ4d_lidar_rows_f32: n = %d, d = %d, ld = %lld, ldo = %lld", n, d,
+                (long long)ld, (long long)ldo);
+  OCC4D_REQUIRE((source != nullptr) == (inv_target != nullptr), "occ4d_lidar_rows_f32: source and inv_target go together");
+  OCC4D_REQUIRE(cube_mode >= 0 && cube_mode <= 4, "occ4d_lidar_rows_f32: cube_mode %d (0 = no filter, 1 .. 4)", cube_mode);
+  empty = n == 0;
+  return OCC4D_OK;
 }
 
 }  // namespace occ4d_frontend

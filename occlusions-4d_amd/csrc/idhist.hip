@@ -1,5 +1,5 @@
 // Segmented id histogram (include/occ4d_occl.h): one pass over a column of the clip's rows, accumulated onto the caller's
-// int32 counts.  The per-row decision is csrc/occl_math.hpp, shared with the g++ twin.
+// int32 counts.  The per-row decision and the argument contract are csrc/occl_math.hpp, shared with the g++ twin.
 //
 // Every workgroup takes a CONTIGUOUS run of 256-row tiles (so it changes segment as rarely as possible) and keeps an int32
 // table of n_ids + 2 bins in LDS for the segment it is in.  Rows are added with LDS integer atomics; when all counted lanes
@@ -86,18 +86,13 @@ __global__ __launch_bounds__(THREADS) void id_histogram_kernel(const oc::HistArg
 extern "C" int occ4d_id_histogram_f32(const float* rows, int64_t ld, int n, int col, const int64_t* seg_offsets, int n_segments,
                                       int n_ids, const float* key, int pred_col, float pred_a, float pred_b, int32_t* counts,
                                       void* stream) {
-  const char* who = "occ4d_id_histogram_f32";
-  OCC4D_REQUIRE(n_ids >= 1 && n_ids <= OCC4D_OCCL_MAX_IDS, "%s: n_ids = %d must be in 1 .. %d", who, n_ids, OCC4D_OCCL_MAX_IDS);
-  OCC4D_REQUIRE(n >= 0 && n_segments >= 0 && ld >= 1, "%s: n = %d, n_segments = %d, ld = %lld", who, n, n_segments, (long long)ld);
-  OCC4D_REQUIRE(col >= 0 && col < ld, "%s: col = %d must be in 0 .. ld - 1 = %lld", who, col, (long long)ld - 1);
-  OCC4D_REQUIRE(pred_col >= -1 && pred_col < ld, "%s: pred_col = %d must be -1 or in 0 .. ld - 1 = %lld", who, pred_col, (long long)ld - 1);
-  if (n == 0 || n_segments == 0) return OCC4D_OK;
-  OCC4D_REQUIRE(rows && seg_offsets && counts, "%s: null rows / seg_offsets / counts", who);
-  const oc::HistArgs a{rows, ld, n, col, key, pred_col, pred_a, pred_b, n_ids};
+  oc::HistArgs a; bool empty;
+  OCC4D_TRY(oc::check_id_histogram(rows, ld, n, col, seg_offsets, n_segments, n_ids, key, pred_col, pred_a, pred_b, counts, empty, a));
+  if (empty) return OCC4D_OK;
   const int tiles = occ4d::cdiv(n, THREADS);
   const int blocks = grid_for(n, n_segments);
   const int tiles_per_wg = occ4d::cdiv(tiles, blocks);
   const size_t lds = (size_t)(n_ids + OCC4D_OCCL_EXTRA_BINS) * sizeof(int);
   id_histogram_kernel<<<blocks, THREADS, lds, (hipStream_t)stream>>>(a, seg_offsets, n_segments, tiles, tiles_per_wg, counts);
-  return occ4d::check_launch(who);
+  return occ4d::check_launch("occ4d_id_histogram_f32");
 }

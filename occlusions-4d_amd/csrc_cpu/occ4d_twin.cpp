@@ -28,32 +28,29 @@
 #include "occ4d_occl.h"
 #include "occ4d_track.h"
 #include "occ4d_project.h"
-#include "frontend_math.hpp"      // csrc/: the front end's per-element arithmetic, the HIP kernels' own source
-#include "eval_math.hpp"          // csrc/: the evaluation statistics' per-row classification, likewise
-#include "occl_math.hpp"          // csrc/: the id histogram's per-row decision, likewise
-#include "track_math.hpp"         // csrc/: the track merge's squash and winner / best update, likewise
-#include "project_math.hpp"       // csrc/: the projection chain, the pixel rule, the z-buffer key and the visibility code, likewise
+// csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
+#include "frontend_math.hpp"
+#include "eval_math.hpp"
+#include "occl_math.hpp"
+#include "track_math.hpp"
+#include "project_math.hpp"
 
-namespace {
+namespace fe = occ4d_frontend;
+namespace ev = occ4d_eval;
+namespace oc = occ4d_occl;
+namespace tk = occ4d_track;
+namespace pj = occ4d_project;
 
-thread_local char g_err[512] = "";
+static thread_local char g_err[512] = "";
 
-int fail(const char* fmt, ...) {
+void occ4d::set_error(const char* fmt, ...) {      // csrc/contract.hpp: OCC4D_REQUIRE / OCC4D_TRY, the HIP library's own macros
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof g_err, fmt, ap);
   va_end(ap);
-  return OCC4D_EINVAL;
 }
-#define REQ(cond, ...) \
-  do {                 \
-    if (!(cond)) return fail(__VA_ARGS__); \
-  } while (0)
-#define TRY(expr)              \
-  do {                         \
-    const int rc_ = (expr);    \
-    if (rc_ != OCC4D_OK) return rc_; \
-  } while (0)
+
+namespace {
 
 inline float act(float v, int code) {      // 0 identity, 1 relu, 2 swish (model/implicit.py:46-64)
   if (code == 1) return v > 0.f ? v : 0.f;
@@ -144,12 +141,12 @@ void attn_one(const occ4d_pt_layer_weights& w, const float* qi, const float* pi,
 }
 
 int check_layer(const occ4d_pt_layer_weights* w, const char* who) {
-  REQ(w, "%s: null weights", who);
-  REQ(w->dim >= 1 && w->pos_hidden >= 1 && w->dim2 >= 1, "%s: bad dimensions", who);
-  REQ(w->to_q && w->to_k && w->to_v && w->pos0_w && w->pos0_b && w->pos2_w && w->pos2_b && w->attn0_w && w->attn0_b &&
+  OCC4D_REQUIRE(w, "%s: null weights", who);
+  OCC4D_REQUIRE(w->dim >= 1 && w->pos_hidden >= 1 && w->dim2 >= 1, "%s: bad dimensions", who);
+  OCC4D_REQUIRE(w->to_q && w->to_k && w->to_v && w->pos0_w && w->pos0_b && w->pos2_w && w->pos2_b && w->attn0_w && w->attn0_b &&
           w->attn2_w && w->attn2_b,
       "%s: null parameter pointer", who);
-  REQ(!w->post_w || (w->post_b && w->d_out == (w->pre_w ? w->d_in : w->dim)), "%s: layer3 + residual needs d_out == d_in", who);
+  OCC4D_REQUIRE(!w->post_w || (w->post_b && w->d_out == (w->pre_w ? w->d_in : w->dim)), "%s: layer3 + residual needs d_out == d_in", who);
   return OCC4D_OK;
 }
 
@@ -188,9 +185,9 @@ int occ4d_is_cpu_twin(void) { return 1; }      // (only this library exports it)
 // ---------------------------------------------------------------------------------------------------------------- geometry
 int occ4d_knn_f32(const float* query, int64_t q_stride, int n_query, const float* data, int64_t d_stride, int n_data, int k,
                   int metric, void* out_idx, int idx_is_i64, float* out_dist, void*) {
-  REQ(query && data && out_idx && n_query >= 0, "occ4d_knn_f32: null pointer");
-  REQ(k >= 1 && k <= 16 && n_data >= k, "occ4d_knn_f32: k = %d must be in 1 .. 16 and <= n_data = %d", k, n_data);
-  REQ(metric == 0 || metric == 1, "occ4d_knn_f32: metric %d", metric);
+  OCC4D_REQUIRE(query && data && out_idx && n_query >= 0, "occ4d_knn_f32: null pointer");
+  OCC4D_REQUIRE(k >= 1 && k <= 16 && n_data >= k, "occ4d_knn_f32: k = %d must be in 1 .. 16 and <= n_data = %d", k, n_data);
+  OCC4D_REQUIRE(metric == 0 || metric == 1, "occ4d_knn_f32: metric %d", metric);
 #pragma omp parallel for schedule(static)
   for (int i = 0; i < n_query; ++i) {
     int32_t idx[16];
@@ -205,7 +202,7 @@ int occ4d_knn_f32(const float* query, int64_t q_stride, int n_query, const float
 
 int occ4d_knn_dists_f32(const float* query, int64_t q_stride, int n_query, const float* data, int64_t d_stride, int n_data,
                         const int32_t* idx, int k, int metric, float* out_dist, void*) {
-  REQ(query && data && idx && out_dist && n_data >= 1 && k >= 1, "occ4d_knn_dists_f32: bad arguments");
+  OCC4D_REQUIRE(query && data && idx && out_dist && n_data >= 1 && k >= 1, "occ4d_knn_dists_f32: bad arguments");
   for (int64_t p = 0; p < (int64_t)n_query * k; ++p) {
     const int j = std::min(std::max(idx[p], 0), n_data - 1);
     out_dist[p] = dist_metric(query + (p / k) * q_stride, data + (int64_t)j * d_stride, metric);
@@ -215,7 +212,7 @@ int occ4d_knn_dists_f32(const float* query, int64_t q_stride, int n_query, const
 
 int occ4d_fps_start_f32(const float* xyz, int64_t stride, int n, int m, int start, int32_t* out_sorted, int32_t* out_order,
                         void*) {
-  REQ(xyz && out_sorted && n >= 1 && m >= 1 && m <= n && start >= 0 && start < n, "occ4d_fps_f32: bad arguments");
+  OCC4D_REQUIRE(xyz && out_sorted && n >= 1 && m >= 1 && m <= n && start >= 0 && start < n, "occ4d_fps_f32: bad arguments");
   std::vector<float> best((size_t)n, INFINITY);
   std::vector<int32_t> order((size_t)m);
   int cur = start;
@@ -244,14 +241,14 @@ int occ4d_fps_f32(const float* xyz, int64_t stride, int n, int m, int32_t* out_s
 int64_t occ4d_fps_coop_workspace_bytes(void) { return 64; }
 int occ4d_fps_coop_f32(const float* xyz, int64_t stride, int n, int m, int start, int, int32_t* out_sorted, int32_t* out_order,
                        void* workspace, void* st) {
-  REQ(workspace, "occ4d_fps_coop_f32: null workspace");
+  OCC4D_REQUIRE(workspace, "occ4d_fps_coop_f32: null workspace");
   std::memset(workspace, 0, 64);
   return occ4d_fps_start_f32(xyz, stride, n, m, start, out_sorted, out_order, st);
 }
 
 int occ4d_nested_fps_level_i32(const int32_t* order, const int32_t* orig, int n, int m, int32_t* out_pos, int32_t* out_orig,
                                void*) {
-  REQ(order && orig && out_pos && out_orig && n >= 1 && m >= 1 && m <= n, "occ4d_nested_fps_level_i32: bad arguments");
+  OCC4D_REQUIRE(order && orig && out_pos && out_orig && n >= 1 && m >= 1 && m <= n, "occ4d_nested_fps_level_i32: bad arguments");
   std::vector<int32_t> pos((size_t)m);
   for (int t = 0; t < m; ++t) pos[t] = (int32_t)(std::lower_bound(orig, orig + n, order[t]) - orig);
   std::sort(pos.begin(), pos.end());
@@ -265,22 +262,22 @@ int occ4d_nested_fps_level_i32(const int32_t* order, const int32_t* orig, int n,
 
 // ---------------------------------------------------------------------------------------------------------------- rows
 int occ4d_copy_rows_f32(float* dst, int64_t ldd, const float* src, int64_t lds, int n, int d, void*) {
-  REQ(dst && src && n >= 0 && d >= 1, "occ4d_copy_rows_f32: bad arguments");
+  OCC4D_REQUIRE(dst && src && n >= 0 && d >= 1, "occ4d_copy_rows_f32: bad arguments");
   for (int i = 0; i < n; ++i) std::memmove(dst + (int64_t)i * ldd, src + (int64_t)i * lds, sizeof(float) * d);
   return OCC4D_OK;
 }
 int occ4d_fill_rows_f32(float* dst, int64_t ld, int n, int d, float value, void*) {
-  REQ(dst && n >= 0 && d >= 1, "occ4d_fill_rows_f32: bad arguments");
+  OCC4D_REQUIRE(dst && n >= 0 && d >= 1, "occ4d_fill_rows_f32: bad arguments");
   for (int i = 0; i < n; ++i) std::fill(dst + (int64_t)i * ld, dst + (int64_t)i * ld + d, value);
   return OCC4D_OK;
 }
 int occ4d_gather_rows_f32(const float* src, int64_t lds, const int32_t* idx, int n_out, int d, float* out, int64_t ldo, void*) {
-  REQ(src && idx && out && n_out >= 0 && d >= 1, "occ4d_gather_rows_f32: bad arguments");
+  OCC4D_REQUIRE(src && idx && out && n_out >= 0 && d >= 1, "occ4d_gather_rows_f32: bad arguments");
   for (int i = 0; i < n_out; ++i) std::memcpy(out + (int64_t)i * ldo, src + (int64_t)idx[i] * lds, sizeof(float) * d);
   return OCC4D_OK;
 }
 int occ4d_mean_rows_f32(const float* x, int64_t ldx, int n, int d, float* out, void*) {
-  REQ(x && out && n >= 1 && d >= 1, "occ4d_mean_rows_f32: bad arguments");
+  OCC4D_REQUIRE(x && out && n >= 1 && d >= 1, "occ4d_mean_rows_f32: bad arguments");
   for (int c = 0; c < d; ++c) {
     double s = 0.0;
     for (int i = 0; i < n; ++i) s += x[(int64_t)i * ldx + c];
@@ -290,7 +287,7 @@ int occ4d_mean_rows_f32(const float* x, int64_t ldx, int n, int d, float* out, v
 }
 int occ4d_maxpool_gather_f32(const float* y, int64_t ldy, const int32_t* idx, int n_out, int k, int d, float* z, int64_t ldz,
                              void*) {
-  REQ(y && idx && z && k >= 1 && d >= 1, "occ4d_maxpool_gather_f32: bad arguments");
+  OCC4D_REQUIRE(y && idx && z && k >= 1 && d >= 1, "occ4d_maxpool_gather_f32: bad arguments");
   for (int i = 0; i < n_out; ++i)
     for (int c = 0; c < d; ++c) {
       float m = -INFINITY;
@@ -301,7 +298,7 @@ int occ4d_maxpool_gather_f32(const float* y, int64_t ldy, const int32_t* idx, in
 }
 int occ4d_layernorm_f32(const float* x, int64_t ldx, const float* gamma, const float* beta, float eps, int relu_out, float* y,
                         int64_t ldy, int n, int d, void*) {
-  REQ(x && y && n >= 0 && d >= 1, "occ4d_layernorm_f32: bad arguments");
+  OCC4D_REQUIRE(x && y && n >= 0 && d >= 1, "occ4d_layernorm_f32: bad arguments");
   for (int i = 0; i < n; ++i) {
     const float* r = x + (int64_t)i * ldx;
     double mu = 0.0, var = 0.0;
@@ -321,8 +318,8 @@ int occ4d_layernorm_f32(const float* x, int64_t ldx, const float* gamma, const f
 
 // ---------------------------------------------------------------------------------------------------------------- Linear
 int occ4d_linear_f32(const occ4d_linear_args* a, void*) {
-  REQ(a && a->x && a->w && a->y && a->M >= 0 && a->K >= 1 && a->N >= 1, "occ4d_linear_f32: bad arguments");
-  REQ(a->relu_in >= 0 && a->relu_in <= 2, "occ4d_linear_f32: Unknown activation: %d", a->relu_in);
+  OCC4D_REQUIRE(a && a->x && a->w && a->y && a->M >= 0 && a->K >= 1 && a->N >= 1, "occ4d_linear_f32: bad arguments");
+  OCC4D_REQUIRE(a->relu_in >= 0 && a->relu_in <= 2, "occ4d_linear_f32: Unknown activation: %d", a->relu_in);
   const int M = a->M, K = a->K, N = a->N;
 #pragma omp parallel
   {
@@ -348,7 +345,7 @@ int occ4d_linear_f32(const occ4d_linear_args* a, void*) {
 // ---------------------------------------------------------------------------------------------------------------- decoder pieces
 int occ4d_posenc_f32(const float* pts, int64_t stride, int n, int c, int n_freq, double base_freq, float* out, int64_t ldo,
                      void*) {
-  REQ(pts && out && n >= 0 && c >= 1 && n_freq >= 0, "occ4d_posenc_f32: bad arguments");
+  OCC4D_REQUIRE(pts && out && n >= 0 && c >= 1 && n_freq >= 0, "occ4d_posenc_f32: bad arguments");
   for (int i = 0; i < n; ++i) {
     const float* p = pts + (int64_t)i * stride;
     float* o = out + (int64_t)i * ldo;
@@ -365,7 +362,7 @@ int occ4d_posenc_f32(const float* pts, int64_t stride, int n, int c, int n_freq,
   return OCC4D_OK;
 }
 int occ4d_interp_weights_f32(const float* dist, int n, int k, float* w, void*) {
-  REQ(dist && w && n >= 0 && k >= 1, "occ4d_interp_weights_f32: bad arguments");
+  OCC4D_REQUIRE(dist && w && n >= 0 && k >= 1, "occ4d_interp_weights_f32: bad arguments");
   for (int i = 0; i < n; ++i) {
     float s = 0.f;
     for (int j = 0; j < k; ++j) {
@@ -379,7 +376,7 @@ int occ4d_interp_weights_f32(const float* dist, int n, int k, float* w, void*) {
 }
 int occ4d_interp_add_f32(float* x, int64_t ldx, const float* cvec, const float* table, int64_t ldt, const int32_t* idx,
                          const float* w, int n, int k, int d, void*) {
-  REQ(x && table && idx && w && n >= 0 && k >= 1 && d >= 1, "occ4d_interp_add_f32: bad arguments");
+  OCC4D_REQUIRE(x && table && idx && w && n >= 0 && k >= 1 && d >= 1, "occ4d_interp_add_f32: bad arguments");
   for (int i = 0; i < n; ++i)
     for (int c = 0; c < d; ++c) {
       float s = cvec ? cvec[c] : 0.f;
@@ -389,7 +386,7 @@ int occ4d_interp_add_f32(float* x, int64_t ldx, const float* cvec, const float* 
   return OCC4D_OK;
 }
 int occ4d_squash_f32(float* out, int64_t ld, int n, int g, const int32_t* ops_host, void*) {
-  REQ(out && ops_host && n >= 0 && g >= 1, "occ4d_squash_f32: bad arguments");
+  OCC4D_REQUIRE(out && ops_host && n >= 0 && g >= 1, "occ4d_squash_f32: bad arguments");
   for (int i = 0; i < n; ++i)
     for (int c = 0; c < g; ++c) {
       float& v = out[(int64_t)i * ld + c];
@@ -401,7 +398,7 @@ int occ4d_squash_f32(float* out, int64_t ld, int n, int g, const int32_t* ops_ho
 // ---------------------------------------------------------------------------------------------------------------- pre / post steps
 int occ4d_grid_points_f32(int nx, int ny, int nz, float x0, float sx, float y0, float sy, float z0, float sz, float t, float* out,
                           void*) {
-  REQ(out && nx >= 1 && ny >= 1 && nz >= 1, "occ4d_grid_points_f32: bad arguments");
+  OCC4D_REQUIRE(out && nx >= 1 && ny >= 1 && nz >= 1, "occ4d_grid_points_f32: bad arguments");
   int64_t i = 0;
   for (int ix = 0; ix < nx; ++ix)
     for (int iy = 0; iy < ny; ++iy)
@@ -417,7 +414,7 @@ int occ4d_grid_points_f32(int nx, int ny, int nz, float x0, float sx, float y0, 
 }
 int occ4d_compact_count_f32(const float* key, int64_t ld, int n, float threshold, int strict, int* block_counts, int* total_kept,
                             void*) {
-  REQ(key && block_counts && total_kept && n >= 0 && ld >= 1, "occ4d_compact_count_f32: bad arguments");
+  OCC4D_REQUIRE(key && block_counts && total_kept && n >= 0 && ld >= 1, "occ4d_compact_count_f32: bad arguments");
   int total = 0;
   for (int b = 0; b * 256 < n; ++b) {
     block_counts[b] = total;                                              // exclusive prefix
@@ -432,7 +429,7 @@ int occ4d_compact_count_f32(const float* key, int64_t ld, int n, float threshold
 int occ4d_compact_rows_f32(const float* src, int64_t ld, int n, int d, const float* key, int64_t ld_key, float threshold,
                            int strict, const int* block_offsets, float* out_rows, float* out_key, void*) {
   // (out_rows may be null when no row is kept -- an empty torch tensor has no storage --, as in csrc/postops.hip)
-  REQ(src && key && block_offsets && n >= 0 && d >= 1 && ld >= d && ld_key >= 1, "occ4d_compact_rows_f32: bad arguments");
+  OCC4D_REQUIRE(src && key && block_offsets && n >= 0 && d >= 1 && ld >= d && ld_key >= 1, "occ4d_compact_rows_f32: bad arguments");
   int64_t kept = 0;
   for (int i = 0; i < n; ++i) {
     const float kv = key[(int64_t)i * ld_key];
@@ -450,8 +447,8 @@ int occ4d_split_count_f32(const float* implicit_output, int64_t ld, int n, float
 }
 int occ4d_split_write_f32(const float* pts, const float* outp, int64_t ld, int n, int g, float threshold, const int*, int compress,
                           int n_cls, float* solid, float* air, void*) {
-  REQ(pts && outp && n >= 0 && g >= 1 && ld >= g, "occ4d_split_write_f32: bad arguments");
-  REQ(!compress || n_cls >= 1, "occ4d_split_write_f32: bad n_classes");
+  OCC4D_REQUIRE(pts && outp && n >= 0 && g >= 1 && ld >= g, "occ4d_split_write_f32: bad arguments");
+  OCC4D_REQUIRE(!compress || n_cls >= 1, "occ4d_split_write_f32: bad n_classes");
   int64_t ns = 0, na = 0;
   for (int i = 0; i < n; ++i) {
     const float* p = pts + (int64_t)i * 4;
@@ -485,12 +482,9 @@ int occ4d_rgbd_rows_f32(const float* depth, const float* rgb, const float* flat,
                         const float* hue_clusters, int n_clusters, int T, int H, int W, float x_min, float x_max, float y_min,
                         float y_max, float z_min, float z_max, int floor_fix, int view_idx, float* out_rows, float* out_target,
                         float* out_key, void*) {
-  namespace fe = occ4d_frontend;
-  REQ(depth && rgb && k_inv && rt_inv && out_rows && out_key, "occ4d_rgbd_rows_f32: null pointer");
-  REQ(T >= 0 && H >= 1 && W >= 1 && (int64_t)T * H * W < ((int64_t)1 << 31), "occ4d_rgbd_rows_f32: T = %d, H = %d, W = %d", T, H, W);
-  REQ(!flat || (hue_clusters && n_clusters >= 1 && n_clusters <= 64), "occ4d_rgbd_rows_f32: n_clusters = %d must be in 1 .. 64",
-      n_clusters);
-  const int64_t hw = (int64_t)H * W, total = hw * T;
+  int64_t total;
+  OCC4D_TRY(fe::check_rgbd_rows(depth, rgb, flat, k_inv, rt_inv, hue_clusters, n_clusters, T, H, W, out_rows, out_key, total));
+  const int64_t hw = (int64_t)H * W;
 #pragma omp parallel for schedule(static)
   for (int64_t p = 0; p < total; ++p) {
     const int t = (int)(p / hw), pix = (int)(p % hw);
@@ -512,60 +506,31 @@ int occ4d_rgbd_rows_f32(const float* depth, const float* rgb, const float* flat,
 
 int occ4d_lidar_rows_f32(const float* rows, int64_t ld, int n, int d, const float* source, const float* inv_target, float z_offset,
                          int cube_mode, double min_z, double other_bounds, float* out_rows, int64_t ldo, float* out_key, void*) {
-  namespace fe = occ4d_frontend;
-  REQ(rows && out_rows && out_key, "occ4d_lidar_rows_f32: null pointer");
-  REQ(n >= 0 && d >= 3 && ld >= d && ldo >= d, "occ4d_lidar_rows_f32: n = %d, d = %d, ld = %lld, ldo = %lld", n, d, (long long)ld,
-      (long long)ldo);
-  REQ((source != nullptr) == (inv_target != nullptr), "occ4d_lidar_rows_f32: source and inv_target go together");
-  REQ(cube_mode >= 0 && cube_mode <= 4, "occ4d_lidar_rows_f32: cube_mode %d (0 = no filter, 1 .. 4)", cube_mode);
+  bool empty;
+  OCC4D_TRY(fe::check_lidar_rows(rows, ld, n, d, source, inv_target, cube_mode, out_rows, ldo, out_key, empty));
+  if (empty) return OCC4D_OK;
   const fe::Cuboid c = fe::carla_input_cuboid(cube_mode, min_z, other_bounds);
 #pragma omp parallel for schedule(static)
-  for (int i = 0; i < n; ++i) {
-    const float* src = rows + (int64_t)i * ld;
-    float* dst = out_rows + (int64_t)i * ldo;
-    float xyz[3] = {src[0], src[1], src[2]};
-    if (source) fe::lidar_transform(source, inv_target, xyz);
-    if (z_offset != 0.f) xyz[2] += z_offset;
-    dst[0] = xyz[0]; dst[1] = xyz[1]; dst[2] = xyz[2];
-    for (int k = 3; k < d; ++k) dst[k] = src[k];
-    out_key[i] = (cube_mode == 0 || fe::in_cuboid(xyz, c.x_min, c.x_max, c.y_min, c.y_max, c.z_min, c.z_max, false)) ? 1.f : 0.f;
-  }
+  for (int i = 0; i < n; ++i)
+    fe::lidar_row(rows, ld, d, source, inv_target, source != nullptr, z_offset, cube_mode != 0, c, out_rows, ldo, out_key, i);
   return OCC4D_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- evaluation
 // include/occ4d_eval.h: the loops of csrc/evalstats.hip over csrc/eval_math.hpp, rows in order, sums sequential
-int64_t occ4d_eval_counts_len(int n_groups, int n_classes) {
-  if (n_groups < 1 || n_groups > OCC4D_EVAL_MAX_GROUPS || n_classes < 0 || n_classes > OCC4D_EVAL_MAX_CLASSES) return -1;
-  return OCC4D_EVAL_HEAD + n_groups * occ4d_eval::group_stride(n_classes);
-}
-int64_t occ4d_eval_sums_len(int n_groups) {
-  return (n_groups < 1 || n_groups > OCC4D_EVAL_MAX_GROUPS) ? -1 : (int64_t)n_groups * OCC4D_EVAL_GROUP_SUMS;
-}
+int64_t occ4d_eval_counts_len(int n_groups, int n_classes) { return ev::counts_len(n_groups, n_classes); }
+int64_t occ4d_eval_sums_len(int n_groups) { return ev::sums_len(n_groups); }
 int64_t occ4d_eval_workspace_bytes(int n) { return n < 0 ? -1 : 8; }
 
 int occ4d_eval_query_stats_f32(const float* out, int64_t ldo, int n, int g_out, const int32_t* nn_idx, const float* nn_dist,
                                const float* target, int64_t ldt, int m, int dt, int col_rgb, int col_track, int col_sem, int out_track,
                                const int32_t* target_group, int n_groups, int n_classes, float density_threshold, float radius,
                                int flags, int64_t* counts, double* sums, void* workspace, void*) {
-  namespace ev = occ4d_eval;
-  const char* who = "occ4d_eval_query_stats_f32";
-  REQ(occ4d_eval_counts_len(n_groups, n_classes) > 0, "%s: n_groups = %d must be in 1 .. 8, n_classes = %d in 0 .. 32", who, n_groups, n_classes);
-  REQ(n >= 0 && m >= 0 && g_out >= 1 && dt >= 1 && ldo >= g_out && ldt >= dt, "%s: n = %d, m = %d, g_out = %d, ldo = %lld, dt = %d, ldt = %lld", who,
-      n, m, g_out, (long long)ldo, dt, (long long)ldt);
-  REQ(counts && sums && workspace && ((uintptr_t)workspace % 8) == 0, "%s: null counts / sums / workspace, or workspace not 8-byte aligned", who);
-  if (n == 0) return OCC4D_OK;
-  REQ(out && nn_idx && nn_dist && (target || m == 0), "%s: null pointer", who);
-  const bool color = (flags & OCC4D_EVAL_FLAG_COLOR) && col_rgb >= 0;
-  const bool track = (flags & OCC4D_EVAL_FLAG_TRACK) && col_track >= 0;
-  const bool seg = (flags & OCC4D_EVAL_FLAG_SEG) && col_sem >= 0 && n_classes >= 1;
-  REQ(!color || (g_out >= 4 && col_rgb + 3 <= dt), "%s: colour needs g_out = %d >= 4 and col_rgb = %d + 3 <= dt = %d", who, g_out, col_rgb, dt);
-  REQ(!track || (out_track >= 0 && out_track < g_out && col_track < dt), "%s: tracking needs out_track = %d < g_out = %d and col_track = %d < dt = %d", who,
-      out_track, g_out, col_track, dt);
-  REQ(!seg || (g_out >= n_classes && col_sem < dt), "%s: segmentation needs g_out = %d >= n_classes = %d and col_sem = %d < dt = %d", who, g_out,
-      n_classes, col_sem, dt);
-  const ev::QueryArgs a{out, ldo, n, g_out, nn_idx, nn_dist, target, ldt, m, color ? col_rgb : -1, track ? col_track : -1,
-                        seg ? col_sem : -1, out_track, target_group, n_groups, n_classes, density_threshold, radius};
+  ev::QueryArgs a; bool empty;
+  OCC4D_TRY(ev::check_query_stats(out, ldo, n, g_out, nn_idx, nn_dist, target, ldt, m, dt, col_rgb, col_track, col_sem, out_track,
+                                  target_group, n_groups, n_classes, density_threshold, radius, flags, counts, sums, workspace,
+                                  empty, a));
+  if (empty) return OCC4D_OK;
   const int64_t stride = ev::group_stride(n_classes);
   double call[OCC4D_EVAL_MAX_GROUPS * OCC4D_EVAL_GROUP_SUMS] = {};      // the call's own totals, added onto the running values at the end
   for (int i = 0; i < n; ++i) {
@@ -600,13 +565,9 @@ int occ4d_eval_query_stats_f32(const float* out, int64_t ldo, int n, int g_out, 
 
 int occ4d_eval_target_stats_f32(const float* dist, int m, const int32_t* target_group, int n_groups, int n_classes, int64_t* counts,
                                 double* sums, void* workspace, void*) {
-  namespace ev = occ4d_eval;
-  const char* who = "occ4d_eval_target_stats_f32";
-  REQ(occ4d_eval_counts_len(n_groups, n_classes) > 0, "%s: n_groups = %d must be in 1 .. 8, n_classes = %d in 0 .. 32", who, n_groups, n_classes);
-  REQ(m >= 0 && counts && sums && workspace && ((uintptr_t)workspace % 8) == 0, "%s: m = %d, null counts / sums / workspace, or workspace not 8-byte aligned",
-      who, m);
-  if (m == 0) return OCC4D_OK;
-  REQ(dist, "%s: null pointer", who);
+  bool empty;
+  OCC4D_TRY(ev::check_target_stats(dist, m, n_groups, n_classes, counts, sums, workspace, empty));
+  if (empty) return OCC4D_OK;
   const int64_t stride = ev::group_stride(n_classes);
   double call[OCC4D_EVAL_MAX_GROUPS * OCC4D_EVAL_GROUP_SUMS] = {};
   for (int j = 0; j < m; ++j) {
@@ -629,20 +590,15 @@ int occ4d_eval_target_stats_f32(const float* dist, int m, const int32_t* target_
 // here, so the contract on them is checked.
 int occ4d_id_histogram_f32(const float* rows, int64_t ld, int n, int col, const int64_t* seg_offsets, int n_segments, int n_ids,
                            const float* key, int pred_col, float pred_a, float pred_b, int32_t* counts, void*) {
-  namespace oc = occ4d_occl;
   const char* who = "occ4d_id_histogram_f32";
-  REQ(n_ids >= 1 && n_ids <= OCC4D_OCCL_MAX_IDS, "%s: n_ids = %d must be in 1 .. %d", who, n_ids, OCC4D_OCCL_MAX_IDS);
-  REQ(n >= 0 && n_segments >= 0 && ld >= 1, "%s: n = %d, n_segments = %d, ld = %lld", who, n, n_segments, (long long)ld);
-  REQ(col >= 0 && col < ld, "%s: col = %d must be in 0 .. ld - 1 = %lld", who, col, (long long)ld - 1);
-  REQ(pred_col >= -1 && pred_col < ld, "%s: pred_col = %d must be -1 or in 0 .. ld - 1 = %lld", who, pred_col, (long long)ld - 1);
-  if (n == 0 || n_segments == 0) return OCC4D_OK;
-  REQ(rows && seg_offsets && counts, "%s: null rows / seg_offsets / counts", who);
-  REQ(seg_offsets[0] == 0 && seg_offsets[n_segments] == n, "%s: seg_offsets must run from 0 to n = %d, got %lld .. %lld", who, n,
-      (long long)seg_offsets[0], (long long)seg_offsets[n_segments]);
+  oc::HistArgs a; bool empty;
+  OCC4D_TRY(oc::check_id_histogram(rows, ld, n, col, seg_offsets, n_segments, n_ids, key, pred_col, pred_a, pred_b, counts, empty, a));
+  if (empty) return OCC4D_OK;
+  OCC4D_REQUIRE(seg_offsets[0] == 0 && seg_offsets[n_segments] == n, "%s: seg_offsets must run from 0 to n = %d, got %lld .. %lld", who, n,
+                (long long)seg_offsets[0], (long long)seg_offsets[n_segments]);
   for (int s = 0; s < n_segments; ++s)
-    REQ(seg_offsets[s] <= seg_offsets[s + 1], "%s: seg_offsets must ascend (segment %d: %lld > %lld)", who, s,
-        (long long)seg_offsets[s], (long long)seg_offsets[s + 1]);
-  const oc::HistArgs a{rows, ld, n, col, key, pred_col, pred_a, pred_b, n_ids};
+    OCC4D_REQUIRE(seg_offsets[s] <= seg_offsets[s + 1], "%s: seg_offsets must ascend (segment %d: %lld > %lld)", who, s,
+                  (long long)seg_offsets[s], (long long)seg_offsets[s + 1]);
   const int bins = n_ids + OCC4D_OCCL_EXTRA_BINS;
   for (int64_t i = 0; i < n; ++i) {
     const int bin = oc::bin_of(a, i);
@@ -657,46 +613,25 @@ int occ4d_id_histogram_f32(const float* rows, int64_t ld, int n, int col, const 
 // include/occ4d_track.h: the passes of csrc/trackmerge.hip over csrc/track_math.hpp, elements in order.
 int occ4d_track_merge_add_f32(const float* out, int64_t ld_out, int n, int g, const int32_t* ops_host, int track_col, float inst_id,
                               int first, float* acc, int64_t ld_acc, float* best, float* winner, void*) {
-  namespace tk = occ4d_track;
-  const char* who = "occ4d_track_merge_add_f32";
-  REQ(n >= 0 && g >= 1 && g <= 32, "%s: n = %d, g = %d: need n >= 0, 1 <= g <= 32", who, n, g);
-  REQ(ld_out >= g && ld_acc >= g, "%s: ld_out = %lld, ld_acc = %lld must be >= g = %d", who, (long long)ld_out, (long long)ld_acc, g);
-  REQ(track_col >= -1 && track_col < g, "%s: track_col = %d must be -1 or in 0 .. g - 1 = %d", who, track_col, g - 1);
-  REQ(first == 0 || first == 1, "%s: first = %d must be 0 or 1", who, first);
-  if (ops_host)
-    for (int c = 0; c < g; ++c) REQ(ops_host[c] >= 0 && ops_host[c] <= 2, "%s: op code %d", who, ops_host[c]);
-  if (n == 0) return OCC4D_OK;
-  REQ(out && acc, "%s: null out / acc", who);
-  REQ(track_col < 0 || (best && winner), "%s: null best / winner with track_col = %d", who, track_col);
-  const uint64_t codes = tk::pack_codes(ops_host, g);
+  tk::AddArgs a; bool empty;
+  OCC4D_TRY(tk::check_merge_add(out, ld_out, n, g, ops_host, track_col, inst_id, first, acc, ld_acc, best, winner, empty, a));
+  if (empty) return OCC4D_OK;
   for (int64_t i = 0; i < n; ++i)
     for (int c = 0; c < g; ++c) {
-      const float v = tk::squash(out[i * ld_out + c], tk::code_of(codes, c));
-      if (c == track_col) {
-        float b = first ? 0.f : best[i], w = first ? -1.f : winner[i];
-        tk::winner_update(v, inst_id, b, w);
-        best[i] = b;
-        winner[i] = w;
-      }
       float& dst = acc[i * ld_acc + c];
-      dst = first ? v : dst + v;
+      const float raw = out[i * ld_out + c];
+      dst = first ? tk::add_one<true>(a, raw, 0.f, i, c) : tk::add_one<false>(a, raw, dst, i, c);
     }
   return OCC4D_OK;
 }
 int occ4d_track_merge_finish_f32(float* acc, int64_t ld_acc, int n, int g, int n_runs, int track_col, const float* winner, void*) {
-  const char* who = "occ4d_track_merge_finish_f32";
-  REQ(n >= 0 && g >= 1 && g <= 32, "%s: n = %d, g = %d: need n >= 0, 1 <= g <= 32", who, n, g);
-  REQ(ld_acc >= g, "%s: ld_acc = %lld must be >= g = %d", who, (long long)ld_acc, g);
-  REQ(track_col >= -1 && track_col < g, "%s: track_col = %d must be -1 or in 0 .. g - 1 = %d", who, track_col, g - 1);
-  REQ(n_runs >= 1, "%s: n_runs = %d must be >= 1", who, n_runs);
-  if (n == 0) return OCC4D_OK;
-  REQ(acc, "%s: null acc", who);
-  REQ(track_col < 0 || winner, "%s: null winner with track_col = %d", who, track_col);
-  const float runs = (float)n_runs;
+  tk::FinishArgs f; bool empty;
+  OCC4D_TRY(tk::check_merge_finish(acc, ld_acc, n, g, n_runs, track_col, winner, empty, f));
+  if (empty) return OCC4D_OK;
   for (int64_t i = 0; i < n; ++i)
     for (int c = 0; c < g; ++c) {
       float& v = acc[i * ld_acc + c];
-      v = c == track_col ? winner[i] : v / runs;
+      v = tk::finish_one(f, v, i, c);
     }
   return OCC4D_OK;
 }
@@ -704,128 +639,54 @@ int occ4d_track_merge_finish_f32(float* acc, int64_t ld_acc, int n, int g, int n
 // ---------------------------------------------------------------------------------------------------------------- projection
 // include/occ4d_project.h: the passes of csrc/project.hip over csrc/project_math.hpp, items in order; the atomic minimum of the
 // splat is a plain minimum here.
-static int project_check_points(const char* who, const float* rows, int64_t ld, int n, const float* rt, const float* k, int V) {
-  REQ(n >= 0 && V >= 0, "%s: n = %d, V = %d must be >= 0", who, n, V);
-  REQ(ld >= 3, "%s: ld = %lld must be >= 3", who, (long long)ld);
-  if (n == 0 || V == 0) return OCC4D_OK;
-  REQ(rows && rt && k, "%s: null rows / rt / k", who);
-  return OCC4D_OK;
-}
-static int project_check_image(const char* who, int V, int H, int W) {
-  namespace pj = occ4d_project;
-  REQ(H >= 1 && W >= 1 && H <= pj::MAX_SIDE && W <= pj::MAX_SIDE, "%s: H = %d, W = %d must be in 1 .. %d", who, H, W, pj::MAX_SIDE);
-  REQ((int64_t)V * H * W < ((int64_t)1 << 31), "%s: V H W = %lld must be < 2^31", who, (long long)V * H * W);
-  return OCC4D_OK;
-}
 int occ4d_project_points_f32(const float* rows, int64_t ld, int n, const float* rt, const float* k, int V, int flip_xy, float* uvz,
                              void*) {
-  namespace pj = occ4d_project;
-  const char* who = "occ4d_project_points_f32";
-  TRY(project_check_points(who, rows, ld, n, rt, k, V));
-  if (n == 0 || V == 0) return OCC4D_OK;
-  REQ(uvz, "%s: null uvz", who);
-  for (int v = 0; v < V; ++v)
-    for (int64_t i = 0; i < n; ++i) {
-      const float* p = rows + i * ld;
-      float r[3];
-      pj::project(rt + 16 * v, k + 16 * v, p[0], p[1], p[2], r);
-      float* o = uvz + 3 * ((int64_t)v * n + i);
-      o[0] = flip_xy ? r[1] : r[0];
-      o[1] = flip_xy ? r[0] : r[1];
-      o[2] = r[2];
-    }
+  pj::PointArgs a; bool empty;
+  OCC4D_TRY(pj::check_project_points(rows, ld, n, rt, k, V, uvz, empty, a));
+  if (empty) return OCC4D_OK;
+  for (int64_t e = 0; e < a.items; ++e) pj::points_item(a, e, flip_xy != 0, uvz);
   return OCC4D_OK;
 }
 int occ4d_zbuffer_splat_f32(const float* rows, int64_t ld, int n, const float* rt, const float* k, int V, int H, int W, int radius,
                             unsigned long long* keys, void*) {
-  namespace pj = occ4d_project;
-  const char* who = "occ4d_zbuffer_splat_f32";
-  TRY(project_check_points(who, rows, ld, n, rt, k, V));
-  TRY(project_check_image(who, V, H, W));
-  REQ(radius >= 0 && radius <= pj::MAX_RADIUS, "%s: radius = %d must be in 0 .. %d", who, radius, pj::MAX_RADIUS);
-  if (n == 0 || V == 0) return OCC4D_OK;
-  REQ(keys, "%s: null keys", who);
-  for (int v = 0; v < V; ++v)
-    for (int64_t i = 0; i < n; ++i) {
-      const float* p = rows + i * ld;
-      float uvz[3];
-      int px, py;
-      pj::project(rt + 16 * v, k + 16 * v, p[0], p[1], p[2], uvz);
-      if (!pj::centre_pixel(uvz, H, W, &px, &py)) continue;
-      const unsigned long long key = pj::pack_key(uvz[2], (uint32_t)i);
-      const int x0 = std::max(px - radius, 0), x1 = std::min(px + radius, W - 1);
-      const int y0 = std::max(py - radius, 0), y1 = std::min(py + radius, H - 1);
-      unsigned long long* image = keys + (int64_t)v * H * W;
-      for (int y = y0; y <= y1; ++y)
-        for (int x = x0; x <= x1; ++x) {
-          unsigned long long& dst = image[(int64_t)y * W + x];
-          dst = std::min(dst, key);
-        }
-    }
+  pj::PointArgs a; bool empty;
+  OCC4D_TRY(pj::check_zbuffer_splat(rows, ld, n, rt, k, V, H, W, radius, keys, empty, a));
+  if (empty) return OCC4D_OK;
+  const auto plain_min = [](unsigned long long* dst, unsigned long long key) { *dst = std::min(*dst, key); };
+  for (int64_t e = 0; e < a.items; ++e) pj::splat_item(a, e, H, W, radius, keys, plain_min);
   return OCC4D_OK;
 }
 int occ4d_zbuffer_resolve_f32(const unsigned long long* keys, int V, int H, int W, const float* rows, int64_t ld, int n, int d,
                               float depth_background, float* depth, int32_t* index, const int32_t* cols_host, int C,
                               float feat_background, float* feat, void*) {
-  namespace pj = occ4d_project;
-  const char* who = "occ4d_zbuffer_resolve_f32";
-  REQ(n >= 0 && V >= 0, "%s: n = %d, V = %d must be >= 0", who, n, V);
-  TRY(project_check_image(who, V, H, W));
-  REQ(C >= 0 && C <= pj::MAX_CHANNELS, "%s: C = %d must be in 0 .. %d", who, C, pj::MAX_CHANNELS);
-  if (C > 0) {
-    REQ(cols_host && feat, "%s: null cols_host / feat with C = %d", who, C);
-    REQ(d >= 1 && ld >= d, "%s: d = %d, ld = %lld: need 1 <= d <= ld", who, d, (long long)ld);
-    REQ(rows || n == 0, "%s: null rows with C = %d", who, C);
-    for (int c = 0; c < C; ++c)
-      REQ(cols_host[c] >= 0 && cols_host[c] < d, "%s: column %d must be in 0 .. d - 1 = %d", who, cols_host[c], d - 1);
-  }
-  if (V == 0) return OCC4D_OK;
-  REQ(keys, "%s: null keys", who);
-  const int64_t pixels = (int64_t)V * H * W;
-  for (int64_t p = 0; p < pixels; ++p) {
-    const unsigned long long key = keys[p];
-    const bool background = pj::key_is_background(key, n);
-    if (depth) depth[p] = background ? depth_background : pj::key_depth(key);
-    if (index) index[p] = background ? -1 : (int32_t)pj::key_row(key);
-    for (int c = 0; c < C; ++c)
-      feat[p * C + c] = background ? feat_background : rows[(int64_t)pj::key_row(key) * ld + cols_host[c]];
-  }
+  pj::ResolveArgs r; bool empty;
+  OCC4D_TRY(pj::check_zbuffer_resolve(keys, V, H, W, rows, ld, n, d, depth_background, depth, index, cols_host, C, feat_background,
+                                      feat, empty, r));
+  if (empty) return OCC4D_OK;
+  for (int64_t p = 0; p < r.pixels; ++p) pj::resolve_item(r, p);
   return OCC4D_OK;
 }
 int occ4d_visibility_f32(const float* rows, int64_t ld, int n, const float* rt, const float* k, int V, const float* depth,
                          int64_t ld_depth, int H, int W, float margin, int32_t* code, void*) {
-  namespace pj = occ4d_project;
-  const char* who = "occ4d_visibility_f32";
-  TRY(project_check_points(who, rows, ld, n, rt, k, V));
-  TRY(project_check_image(who, V, H, W));
-  REQ(ld_depth >= W, "%s: ld_depth = %lld must be >= W = %d", who, (long long)ld_depth, W);
-  if (n == 0 || V == 0) return OCC4D_OK;
-  REQ(depth && code, "%s: null depth / code", who);
-  for (int v = 0; v < V; ++v)
-    for (int64_t i = 0; i < n; ++i) {
-      const float* p = rows + i * ld;
-      float uvz[3];
-      int px = 0, py = 0;
-      pj::project(rt + 16 * v, k + 16 * v, p[0], p[1], p[2], uvz);
-      const bool inside = pj::centre_pixel(uvz, H, W, &px, &py);
-      const float dimg = inside ? depth[((int64_t)v * H + py) * ld_depth + px] : 0.f;
-      code[(int64_t)v * n + i] = pj::visibility_code(inside, uvz[2], dimg, margin);
-    }
+  pj::PointArgs a; bool empty;
+  OCC4D_TRY(pj::check_visibility(rows, ld, n, rt, k, V, depth, ld_depth, H, W, code, empty, a));
+  if (empty) return OCC4D_OK;
+  for (int64_t e = 0; e < a.items; ++e) pj::visibility_item(a, e, depth, ld_depth, H, W, margin, code);
   return OCC4D_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- E3 / E2
 int64_t occ4d_pt_layer_prepared_floats(const occ4d_pt_layer_weights* w, int) { return w ? 64 : -1; }
 int occ4d_pt_layer_prepare_f32(const occ4d_pt_layer_weights* w, float* prepared, int, void*) {
-  TRY(check_layer(w, "occ4d_pt_layer_prepare_f32"));
-  REQ(prepared, "occ4d_pt_layer_prepare_f32: null buffer");
+  OCC4D_TRY(check_layer(w, "occ4d_pt_layer_prepare_f32"));
+  OCC4D_REQUIRE(prepared, "occ4d_pt_layer_prepare_f32: null buffer");
   return OCC4D_OK;                       // (as written: nothing is derived from the weights)
 }
 int64_t occ4d_pt_layer_scene_floats(const occ4d_pt_layer_weights* w, int m) { return w ? up4((int64_t)2 * m * w->dim) : -1; }
 int occ4d_pt_layer_scene_f32(const occ4d_pt_layer_weights* w, const float*, const float* x2, int64_t ldx2, int m, float* scene,
                              int, void*) {
-  TRY(check_layer(w, "occ4d_pt_layer_scene_f32"));
-  REQ(x2 && scene && m >= 1 && w->cross, "occ4d_pt_layer_scene_f32: bad arguments");
+  OCC4D_TRY(check_layer(w, "occ4d_pt_layer_scene_f32"));
+  OCC4D_REQUIRE(x2 && scene && m >= 1 && w->cross, "occ4d_pt_layer_scene_f32: bad arguments");
   layer_tables(*w, x2, ldx2, m, scene, scene + (int64_t)m * w->dim);
   return OCC4D_OK;
 }
@@ -836,9 +697,9 @@ int occ4d_pt_layer_fwd_f32(const occ4d_pt_layer_weights* w, const float*, const 
                            const int32_t* knn_idx, const float* scene, float* out, int64_t ldo, float*, int,
                            occ4d_launch_events* ev, void*) {
   const char* who = "occ4d_pt_layer_fwd_f32";
-  TRY(check_layer(w, who));
-  REQ(x && pos && out && n >= 0 && k >= 1 && k <= 16, "%s: bad arguments (k = %d)", who, k);
-  REQ(!w->cross || (pos2 && m >= k && (x2 || scene)), "%s: cross-attention needs x2 / pos2 with m >= k", who);
+  OCC4D_TRY(check_layer(w, who));
+  OCC4D_REQUIRE(x && pos && out && n >= 0 && k >= 1 && k <= 16, "%s: bad arguments (k = %d)", who, k);
+  OCC4D_REQUIRE(!w->cross || (pos2 && m >= k && (x2 || scene)), "%s: cross-attention needs x2 / pos2 with m >= k", who);
   if (ev) ev->used = 0;
   const int D = w->dim, d_in = w->pre_w ? w->d_in : D;
   if (n == 0) return OCC4D_OK;
@@ -849,7 +710,7 @@ int occ4d_pt_layer_fwd_f32(const occ4d_pt_layer_weights* w, const float*, const 
     if (w->pre_w) matvec(w->pre_w, d_in, w->pre_b, x + (int64_t)i * ldx, D, d_in, y.data() + (size_t)i * D);
     else std::memcpy(y.data() + (size_t)i * D, x + (int64_t)i * ldx, sizeof(float) * D);
   }
-  if (!w->cross) { pos2 = pos; p2s = ps; m = n; REQ(m >= k, "%s: n = %d < k = %d", who, n, k); }
+  if (!w->cross) { pos2 = pos; p2s = ps; m = n; OCC4D_REQUIRE(m >= k, "%s: n = %d < k = %d", who, n, k); }
   // to_k / to_v of the key cloud (:171-172), to_q of the queries (:170)
   std::vector<float> tab;
   const float *kf, *vf;
@@ -890,15 +751,15 @@ int occ4d_down_pool_fwd_f32(const float* x, int64_t ldx, int n, int d_in, const 
                             const float* gamma, const float* beta, const float* mean, const float* var, float eps,
                             const int32_t* nn_idx, int n_new, int k, float* z, int64_t ldz, float* workspace, void* st) {
   const char* who = "occ4d_down_pool_fwd_f32";
-  REQ(x && w && b && nn_idx && z && workspace && n >= 1 && n_new >= 1 && k >= 1, "%s: bad arguments", who);
-  REQ(norm >= 0 && norm <= 2, "%s: Unknown norm type: %d", who, norm);
-  REQ(norm == 0 || (gamma && beta), "%s: norm needs gamma / beta", who);
-  REQ(norm != 2 || (mean && var), "%s: batch norm needs running statistics", who);
+  OCC4D_REQUIRE(x && w && b && nn_idx && z && workspace && n >= 1 && n_new >= 1 && k >= 1, "%s: bad arguments", who);
+  OCC4D_REQUIRE(norm >= 0 && norm <= 2, "%s: Unknown norm type: %d", who, norm);
+  OCC4D_REQUIRE(norm == 0 || (gamma && beta), "%s: norm needs gamma / beta", who);
+  OCC4D_REQUIRE(norm != 2 || (mean && var), "%s: batch norm needs running statistics", who);
   float* y = workspace;                                                      // (n, d_out): the MLP on ALL points   (model/modules.py:152)
 #pragma omp parallel for schedule(static)
   for (int i = 0; i < n; ++i) matvec(w, d_in, b, x + (int64_t)i * ldx, d_out, d_in, y + (int64_t)i * d_out);
   if (norm == 1) {
-    TRY(occ4d_layernorm_f32(y, d_out, gamma, beta, eps, 1, y, d_out, n, d_out, st));
+    OCC4D_TRY(occ4d_layernorm_f32(y, d_out, gamma, beta, eps, 1, y, d_out, n, d_out, st));
   } else {
     for (int64_t i = 0; i < (int64_t)n; ++i)
       for (int c = 0; c < d_out; ++c) {
@@ -912,31 +773,31 @@ int occ4d_down_pool_fwd_f32(const float* x, int64_t ldx, int n, int d_in, const 
 
 // ---------------------------------------------------------------------------------------------------------------- D1-D7
 static int check_decoder(const occ4d_decoder_weights* w, const char* who) {
-  REQ(w, "%s: null weights", who);
-  REQ(w->n_blocks >= 1 && w->n_blocks <= OCC4D_MAX_BLOCKS && w->n_cross >= 0 && w->n_cross <= OCC4D_MAX_CROSS,
+  OCC4D_REQUIRE(w, "%s: null weights", who);
+  OCC4D_REQUIRE(w->n_blocks >= 1 && w->n_blocks <= OCC4D_MAX_BLOCKS && w->n_cross >= 0 && w->n_cross <= OCC4D_MAX_CROSS,
       "%s: n_blocks = %d, n_cross = %d", who, w->n_blocks, w->n_cross);
-  REQ(w->activation == 0 || w->activation == 1, "%s: Unknown activation: %d", who, w->activation);
-  REQ(w->k_local >= 1 && w->k_local <= 16 && (w->n_cross == 0 || (w->k_cross >= 1 && w->k_cross <= 16)),
+  OCC4D_REQUIRE(w->activation == 0 || w->activation == 1, "%s: Unknown activation: %d", who, w->activation);
+  OCC4D_REQUIRE(w->k_local >= 1 && w->k_local <= 16 && (w->n_cross == 0 || (w->k_cross >= 1 && w->k_cross <= 16)),
       "%s: k_local = %d, k_cross = %d (1 .. 16)", who, w->k_local, w->k_cross);
-  REQ(w->lin_in_w && w->lin_in_b && w->lin_out_w && w->lin_out_b, "%s: lin_in / lin_out missing", who);
-  for (int j = 0; j < w->n_cross; ++j) TRY(check_layer(&w->cross[j], who));
+  OCC4D_REQUIRE(w->lin_in_w && w->lin_in_b && w->lin_out_w && w->lin_out_b, "%s: lin_in / lin_out missing", who);
+  for (int j = 0; j < w->n_cross; ++j) OCC4D_TRY(check_layer(&w->cross[j], who));
   return OCC4D_OK;
 }
 int64_t occ4d_decoder_prepared_floats(const occ4d_decoder_weights* w, int) { return w ? 64 : -1; }
 int occ4d_decoder_prepare_f32(const occ4d_decoder_weights* w, float* prepared, int, void*) {
-  TRY(check_decoder(w, "occ4d_decoder_prepare_f32"));
-  REQ(prepared, "occ4d_decoder_prepare_f32: null buffer");
+  OCC4D_TRY(check_decoder(w, "occ4d_decoder_prepare_f32"));
+  OCC4D_REQUIRE(prepared, "occ4d_decoder_prepare_f32: null buffer");
   return OCC4D_OK;
 }
 int64_t occ4d_decoder_scene_floats(const occ4d_decoder_weights* w, int m) { return w && m >= 1 ? dec_scene(*w, m).total : -1; }
 int occ4d_decoder_prepare_scene_f32(const occ4d_decoder_weights* w, const float*, const float* xyz, int64_t xyz_stride,
                                     const float* feats, int64_t ld_feats, const float* fglobal, int m, float* scene, int, void* st) {
   const char* who = "occ4d_decoder_prepare_scene_f32";
-  TRY(check_decoder(w, who));
-  REQ(xyz && feats && fglobal && scene && m >= 1, "%s: bad arguments", who);
+  OCC4D_TRY(check_decoder(w, who));
+  OCC4D_REQUIRE(xyz && feats && fglobal && scene && m >= 1, "%s: bad arguments", who);
   const DecScene S = dec_scene(*w, m);
-  TRY(occ4d_copy_rows_f32(scene + S.xyz, 3, xyz, xyz_stride, m, 3, st));
-  TRY(occ4d_copy_rows_f32(scene + S.feats, w->d_latent_local, feats, ld_feats, m, w->d_latent_local, st));
+  OCC4D_TRY(occ4d_copy_rows_f32(scene + S.xyz, 3, xyz, xyz_stride, m, 3, st));
+  OCC4D_TRY(occ4d_copy_rows_f32(scene + S.feats, w->d_latent_local, feats, ld_feats, m, w->d_latent_local, st));
   std::memcpy(scene + S.fglobal, fglobal, sizeof(float) * (w->d_latent - w->d_latent_local));
   for (int j = 0; j < w->n_cross; ++j)      // to_k / to_v rows of the abstract cloud: once per scene instead of once per call (D7)
     layer_tables(w->cross[j], scene + S.feats, w->d_latent_local, m, scene + S.layer[j], scene + S.layer[j] + (int64_t)m * w->cross[j].dim);
@@ -948,8 +809,8 @@ int occ4d_decoder_query_fwd_f32(const occ4d_decoder_weights* w, const float*, co
                                 int64_t qs, int n, const int32_t* knn_local, const int32_t* knn_cross, float* out, int64_t ld_out,
                                 float* penult, int64_t ld_pen, float*, int, occ4d_launch_events* ev, void*) {
   const char* who = "occ4d_decoder_query_fwd_f32";
-  TRY(check_decoder(w, who));
-  REQ(scene && queries && out && n >= 0 && m >= w->k_local && (w->n_cross == 0 || m >= w->k_cross), "%s: bad arguments", who);
+  OCC4D_TRY(check_decoder(w, who));
+  OCC4D_REQUIRE(scene && queries && out && n >= 0 && m >= w->k_local && (w->n_cross == 0 || m >= w->k_cross), "%s: bad arguments", who);
   if (ev) ev->used = 0;
   const DecScene S = dec_scene(*w, m);
   const float *xyz = scene + S.xyz, *feats = scene + S.feats, *fglobal = scene + S.fglobal;

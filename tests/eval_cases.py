@@ -5,6 +5,7 @@ are written out here and compared with the header's defines by a test."""
 import itertools
 
 import numpy as np
+import pytest
 import torch
 
 import occlusions4d_amd as pk
@@ -240,3 +241,23 @@ def add_cloud(stats, c, device, track_mode='one', **kw):
     return stats.add_frame(torch.from_numpy(c['q']).to(dev), torch.from_numpy(c['out']).to(dev), c['target'], density_threshold=0.5,
                            point_occupancy_radius=c['radius'], color_mode='rgb', predict_segmentation=False, track_mode=track_mode,
                            data_kind='greater', target_group=c['group'], **kw)
+
+
+def check_argument_errors(device):
+    """The contract of the query statistics, as the library on `device` states it (csrc/eval_math.hpp: one source for both
+    libraries)."""
+    z = lambda *shape, **kw: torch.zeros(*shape, device=device, **kw)
+    counts, sums = z(17, dtype=torch.int64), z(8, dtype=torch.float64)
+    out, idx, dist, tgt = z(8, 5)[2:6], z(4, dtype=torch.int32), z(4), z(3, 9)      # (out: four rows with two rows of slack each side)
+    with pytest.raises(AssertionError, match='col_rgb'):
+        pk.ops.eval_query_stats(out, idx, dist, tgt, counts, sums, flags=FLAG_COLOR, col_rgb=7)
+    with pytest.raises(AssertionError, match='out_track'):
+        pk.ops.eval_query_stats(out, idx, dist, tgt, counts, sums, flags=FLAG_TRACK, col_track=8, out_track=5)
+    with pytest.raises(AssertionError, match='n_classes'):
+        pk.ops.eval_query_stats(out, idx, dist, z(3, 11), z(1 + 16 + 169, dtype=torch.int64), sums,
+                                flags=FLAG_SEG, col_sem=5, n_classes=13)
+    with pytest.raises(AssertionError):
+        pk.ops.eval_query_stats(out, idx, dist, tgt, counts[:16], sums)
+    with pytest.raises(AssertionError):
+        pk.evaluation.EvalStats(9, 0, device)
+    assert not counts.any() and not sums.any()

@@ -2,6 +2,7 @@
 tests/gen_frontend_fixture.py (the reference's own results, stage by stage) against occlusions4d_amd.frontend on one device.
 Everything is compared BIT FOR BIT: values, row order, sizes, ratios and the state of both global generators afterwards."""
 import numpy as np
+import pytest
 import torch
 
 import gen_frontend_fixture as gen
@@ -128,3 +129,33 @@ def check_carla_stages(device, mode, ref_frame):
             same(rows[:, :3], st['xyz_%s_v%d_t%d' % (which, v, t)], 'lidar xyz %s v%d t%d' % (which, v, t))
             same(rows[:, 3:], lidar[v][t][:, 3:], 'lidar attributes')
             assert np.array_equal(np.flatnonzero(key > 0.5), st['kept_m%d_%s_v%d_t%d' % (mode, which, v, t)].astype(np.int64))
+
+
+def check_argument_errors(device):
+    """Shape violations raise AssertionError, as elsewhere in the package; the library's own checks (EINVAL) are those of
+    csrc/frontend_math.hpp, one source for both libraries."""
+    inp = greater_inputs()
+    kw = dict(gen.GREATER_CASES_BY_NAME['a'], device=device)
+    with pytest.raises(AssertionError, match='cam_K'):
+        pk.frontend.greater_clip(**dict(inp, cam_K=inp['cam_K'][:, :2]), **kw)
+    with pytest.raises(AssertionError, match='rgb'):
+        pk.frontend.greater_clip(**dict(inp, rgb=inp['rgb'][..., :2]), **kw)
+    with pytest.raises(AssertionError, match='depth'):
+        pk.frontend.greater_clip(**dict(inp, depth=inp['depth'][0]), **kw)
+    with pytest.raises(AssertionError):
+        pk.frontend.greater_clip(**inp, **dict(kw, src_view=5))
+    with pytest.raises(AssertionError, match='n_clusters'):                    # the library's own check (EINVAL)
+        pk.frontend.greater_clip(**dict(inp, hue_clusters=np.arange(65, dtype=np.float32)), **kw)
+    lidar, cin = carla_inputs()
+    with pytest.raises(AssertionError, match='sensor_RT'):
+        pk.frontend.carla_clip(lidar, cin['sensor_RT'][:2], device=device)
+    with pytest.raises(AssertionError, match='x, y, z'):
+        pk.frontend.lidar_rows(torch.zeros(5, 2, device=device))
+    with pytest.raises(AssertionError, match='cube_mode'):
+        pk.frontend.lidar_rows(torch.zeros(5, 4, device=device), cube_mode=9)
+    lib = pk._lib.lib()
+    rows, out, key = (torch.zeros(shape, device=device) for shape in ((4, 4), (4, 4), (4,)))
+    source = torch.eye(4)                                                      # (a HOST matrix in both libraries)
+    rc = lib.occ4d_lidar_rows_f32(rows.data_ptr(), 4, 4, 4, source.data_ptr(), None, 0.0, 0, 0.0, 1.0, out.data_ptr(), 4, key.data_ptr(),
+                                  None)
+    assert rc == pk._lib.EINVAL and b'go together' in lib.occ4d_last_error()

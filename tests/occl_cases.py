@@ -5,6 +5,7 @@ Counts must be EQUAL: there is no tolerance anywhere."""
 import itertools
 
 import numpy as np
+import pytest
 import torch
 
 import frontend_cases as fc
@@ -289,3 +290,24 @@ def through_the_sampler(got, kind, bias, cube_bounds):
     res = sampler([f[None] for f in targets], [torch.tensor([f.shape[0]]) for f in targets],
                   torch.from_numpy(meta['valo_ids'])[None], torch.tensor([meta['num_valo_ids']]), 0)
     assert tuple(res[0].shape) == (1, 64, 4) and tuple(res[1].shape) == (1, 64, 4)
+
+
+def check_argument_errors(device):
+    """The contract of the histogram, as the library on `device` states it (csrc/occl_math.hpp: one source for both libraries).
+    Offsets handed over as a TENSOR that break the contract are not here: only a library that has them in host memory can
+    reject them (tests/test_occl_host.py)."""
+    rows = torch.zeros(10, 4, device=device)
+    with pytest.raises(AssertionError, match='n_ids'):
+        pk.ops.id_histogram(rows, 0, [0, 10], 0)
+    with pytest.raises(AssertionError, match='n_ids'):
+        pk.ops.id_histogram(rows, 0, [0, 10], 4097)
+    with pytest.raises(AssertionError, match='col'):
+        pk.ops.id_histogram(rows, 4, [0, 10], 4)
+    with pytest.raises(AssertionError, match='pred_col'):
+        pk.ops.id_histogram(rows, 0, [0, 10], 4, pred_col=4, pred_values=(1.0,))
+    with pytest.raises(AssertionError, match='seg_offsets'):
+        pk.ops.id_histogram(rows, 0, [0, 7, 3, 10], 4)
+    with pytest.raises(AssertionError, match='seg_offsets'):
+        pk.ops.id_histogram(rows, 0, [0, 9], 4)
+    assert pk.ops.id_histogram(rows[:0], 0, [0], 4).shape == (0, 6)
+    assert int(pk.ops.id_histogram(rows[:0], 0, [0, 0, 0], 4).sum()) == 0

@@ -8,6 +8,7 @@ import ctypes.util
 import types
 
 import numpy as np
+import pytest
 import torch
 
 import gen_project_fixture as gen
@@ -412,3 +413,55 @@ def check_evaluate_clip(device):
     else:
         raise RuntimeError('two groups were accepted')
     assert np.array_equal(by_fn.state()['counts'], a['counts'])            # (the rejected calls added nothing)
+
+
+def check_argument_errors(device):
+    """The contract of the four entry points, as the library on `device` states it (csrc/project_math.hpp: one source for both
+    libraries).  Every non-null pointer is a real tensor that covers the call even if it were accepted."""
+    z = lambda *shape, **kw: torch.zeros(*shape, device=device, **kw)
+    rows, rt, k = z(10, 6), torch.eye(4, device=device).reshape(1, 16), torch.eye(4, device=device).reshape(1, 16)
+    ops = pk.ops
+    with pytest.raises(AssertionError, match='radius'):
+        ops.zbuffer_splat(rows, rt, k, 4, 4, radius=5)
+    with pytest.raises(AssertionError, match='radius'):
+        ops.zbuffer_splat(rows, rt, k, 4, 4, radius=-1)
+    with pytest.raises(AssertionError, match='H = 0'):
+        ops.zbuffer_splat(rows, rt, k, 0, 4)
+    with pytest.raises(AssertionError, match='W = 40000'):
+        ops.zbuffer_splat(rows, rt, k, 4, 40000)
+    with pytest.raises(AssertionError, match='keys must be'):
+        ops.zbuffer_splat(rows, rt, k, 4, 4, keys=z(1, 4, 5, dtype=torch.int64))
+    with pytest.raises(AssertionError, match='x, y, z'):
+        ops.project_points(z(10, 2), rt, k)
+    with pytest.raises(AssertionError, match='rt / k'):
+        ops.project_points(rows, rt, z(2, 16))
+    keys = ops.zbuffer_splat(rows, rt, k, 4, 4)
+    with pytest.raises(AssertionError, match='column 6'):
+        ops.zbuffer_resolve(keys, rows, [0, 6])
+    with pytest.raises(AssertionError, match='column -1'):
+        ops.zbuffer_resolve(keys, rows, [-1])
+    with pytest.raises(AssertionError, match='C = 33'):
+        ops.zbuffer_resolve(keys, rows, [0] * 33)
+    with pytest.raises(AssertionError, match='depth must be'):
+        ops.visibility(rows, rt, k, z(2, 4, 4), 0.0)
+    L, p = pk._lib.lib(), pk.ops._ptr                                 # what no tensor can express: short strides, null arrays
+    code = z(10, dtype=torch.int32)
+    img = z(1, 4, 4)
+    rt3, k3, uvz = rt.repeat(3, 1), k.repeat(3, 1), z(30)
+    assert L.occ4d_project_points_f32(p(rows), 2, 10, p(rt), p(k), 1, 0, p(uvz), None) == pk._lib.EINVAL
+    assert L.occ4d_project_points_f32(None, 6, 10, p(rt), p(k), 1, 0, p(uvz), None) == pk._lib.EINVAL
+    assert L.occ4d_project_points_f32(p(rows), 6, 10, p(rt), p(k), 1, 0, None, None) == pk._lib.EINVAL
+    assert L.occ4d_project_points_f32(p(rows), 6, -1, p(rt), p(k), 1, 0, None, None) == pk._lib.EINVAL
+    assert L.occ4d_zbuffer_splat_f32(p(rows), 6, 10, p(rt), p(k), 1, 4, 4, 0, None, None) == pk._lib.EINVAL
+    assert L.occ4d_zbuffer_splat_f32(p(rows), 6, 10, p(rt3), p(k3), 3, 32768, 32768, 0, p(keys), None) == pk._lib.EINVAL
+    assert L.occ4d_zbuffer_resolve_f32(None, 1, 4, 4, p(rows), 6, 10, 6, 0.0, p(img), None, None, 0, 0.0, None, None) == pk._lib.EINVAL
+    assert L.occ4d_zbuffer_resolve_f32(p(keys), 1, 4, 4, p(rows), 5, 10, 6, 0.0, p(img), None, (ctypes.c_int32 * 1)(0), 1, 0.0, p(img),
+                                       None) == pk._lib.EINVAL
+    assert L.occ4d_visibility_f32(p(rows), 6, 10, p(rt), p(k), 1, p(img), 3, 4, 4, 0.0, p(code), None) == pk._lib.EINVAL
+    assert L.occ4d_visibility_f32(p(rows), 6, 10, p(rt), p(k), 1, None, 4, 4, 4, 0.0, p(code), None) == pk._lib.EINVAL
+    assert b'occ4d_visibility_f32' in L.occ4d_last_error()
+    assert L.occ4d_project_points_f32(None, 6, 0, None, None, 1, 0, None, None) == pk._lib.OK                    # n = 0, V = 0
+    assert L.occ4d_zbuffer_splat_f32(None, 6, 10, None, None, 0, 4, 4, 0, None, None) == pk._lib.OK
+    assert L.occ4d_zbuffer_resolve_f32(None, 0, 4, 4, None, 6, 10, 6, 0.0, None, None, None, 0, 0.0, None, None) == pk._lib.OK
+    assert L.occ4d_visibility_f32(None, 6, 0, None, None, 1, None, 4, 4, 4, 0.0, None, None) == pk._lib.OK
+    assert bool((keys == -1).all()) and float(rows.abs().sum()) == 0.0            # (rows at the camera centre: depth 0, no splat)

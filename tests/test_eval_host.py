@@ -118,20 +118,7 @@ def test_bad_rows_are_skipped_and_summary_raises(twin):
 
 
 def test_argument_errors(twin):
-    counts, sums = torch.zeros(17, dtype=torch.int64), torch.zeros(8, dtype=torch.float64)
-    out, idx, dist, tgt = torch.zeros((4, 5)), torch.zeros(4, dtype=torch.int32), torch.zeros(4), torch.zeros((3, 9))
-    with pytest.raises(AssertionError, match='col_rgb'):
-        pk.ops.eval_query_stats(out, idx, dist, tgt, counts, sums, flags=ec.FLAG_COLOR, col_rgb=7)
-    with pytest.raises(AssertionError, match='out_track'):
-        pk.ops.eval_query_stats(out, idx, dist, tgt, counts, sums, flags=ec.FLAG_TRACK, col_track=8, out_track=5)
-    with pytest.raises(AssertionError, match='n_classes'):
-        pk.ops.eval_query_stats(out, idx, dist, torch.zeros((3, 11)), torch.zeros(1 + 16 + 169, dtype=torch.int64), sums,
-                                flags=ec.FLAG_SEG, col_sem=5, n_classes=13)
-    with pytest.raises(AssertionError):
-        pk.ops.eval_query_stats(out, idx, dist, tgt, counts[:16], sums)
-    with pytest.raises(AssertionError):
-        pk.evaluation.EvalStats(9, 0, CPU)
-    assert not counts.any() and not sums.any()
+    ec.check_argument_errors(CPU)
 
 
 # ------------------------------------------------------------------------------------------------------------------- EvalStats

@@ -137,30 +137,7 @@ def test_geometry_mirrors(twin):
 
 
 def test_error_conventions(twin):
-    """Shape violations raise AssertionError, as elsewhere in the package."""
-    inp = fc.greater_inputs()
-    kw = dict(gen.GREATER_CASES_BY_NAME['a'])
-    with pytest.raises(AssertionError, match='cam_K'):
-        pk.frontend.greater_clip(**dict(inp, cam_K=inp['cam_K'][:, :2]), **kw)
-    with pytest.raises(AssertionError, match='rgb'):
-        pk.frontend.greater_clip(**dict(inp, rgb=inp['rgb'][..., :2]), **kw)
-    with pytest.raises(AssertionError, match='depth'):
-        pk.frontend.greater_clip(**dict(inp, depth=inp['depth'][0]), **kw)
-    with pytest.raises(AssertionError):
-        pk.frontend.greater_clip(**inp, **dict(kw, src_view=5))
-    with pytest.raises(AssertionError, match='n_clusters'):                    # the library's own check (EINVAL)
-        pk.frontend.greater_clip(**dict(inp, hue_clusters=np.arange(65, dtype=np.float32)), **kw)
-    lidar, cin = fc.carla_inputs()
-    with pytest.raises(AssertionError, match='sensor_RT'):
-        pk.frontend.carla_clip(lidar, cin['sensor_RT'][:2])
-    with pytest.raises(AssertionError, match='x, y, z'):
-        pk.frontend.lidar_rows(torch.zeros(5, 2))
-    with pytest.raises(AssertionError, match='cube_mode'):
-        pk.frontend.lidar_rows(torch.zeros(5, 4), cube_mode=9)
-    lib = pk._lib.lib()
-    z = torch.zeros(4, 4)
-    rc = lib.occ4d_lidar_rows_f32(z.data_ptr(), 4, 4, 4, z.data_ptr(), None, 0.0, 0, 0.0, 1.0, z.data_ptr(), 4, z.data_ptr(), None)
-    assert rc == pk._lib.EINVAL and b'go together' in lib.occ4d_last_error()
+    fc.check_argument_errors(CPU)
 
 
 def test_cpu_tensors_are_rejected_without_the_twin():

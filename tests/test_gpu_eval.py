@@ -30,6 +30,10 @@ def test_special_cases(name, args):
             s.summary()
 
 
+def test_argument_errors():
+    ec.check_argument_errors(DEV)
+
+
 @pytest.mark.parametrize('idx', [42, 44])                # N = 262 401 (two trips, 1024 partials) with 8 and 3 groups
 def test_two_identical_calls_give_bit_identical_sums(idx):
     case = ec.make_case(*ec.matrix()[idx][1])

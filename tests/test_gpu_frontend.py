@@ -51,6 +51,10 @@ def _ulps(a, b):
     return np.abs(ia - ib)
 
 
+def test_error_conventions():
+    fc.check_argument_errors(DEV)
+
+
 @pytest.mark.parametrize('T,H,W', [(12, 240, 320), (3, 37, 53)])
 def test_synthetic_clip_counts_order_and_coordinates(T, H, W):
     rng = np.random.default_rng(H * W)

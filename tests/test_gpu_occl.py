@@ -18,6 +18,10 @@ def test_histogram_case_matrix(n):
     assert oc.check_matrix(n, DEV) == 3 * 3 * (2 * 3 + 1)
 
 
+def test_histogram_argument_errors():
+    oc.check_argument_errors(DEV)
+
+
 def test_tables_do_not_depend_on_the_stream_or_the_run():
     """Three streams at once and a repeated run: integer tables are order-free."""
     n, n_ids, S = 262401, 12, 48

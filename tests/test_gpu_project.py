@@ -39,6 +39,10 @@ def test_round_trip_with_the_front_end():
     pc.check_roundtrip(DEV)
 
 
+def test_argument_errors():
+    pc.check_argument_errors(DEV)
+
+
 def test_zbuffer_does_not_depend_on_the_stream_or_the_run():
     """Three streams at once and a repeated call: equal bits (the minimum of a set has no order)."""
     n, V, H, W, radius = 110000, 3, 240, 320, 1

@@ -27,6 +27,10 @@ def test_merge_case_matrix(n):
     assert tc.check_matrix(n, DEV) == tc.cells_of(n)
 
 
+def test_argument_errors():
+    tc.check_argument_errors(DEV)
+
+
 def test_merge_does_not_depend_on_the_stream_or_the_run():
     """Three streams at once and a repeated call: equal bits (no atomics, every element has one owner)."""
     n, g, K, track_col = 262401, 5, 5, 4

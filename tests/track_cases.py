@@ -5,6 +5,7 @@ Everything is compared EQUAL: the non-NaN elements bit for bit (so -0 is not +0)
 import types
 
 import numpy as np
+import pytest
 import torch
 
 import gen_track_fixture as gen
@@ -275,3 +276,52 @@ def check_clip_reuses_the_encodes(device, monkeypatch):
         for x, y in zip(a, b):
             assert x.dtype == y.dtype and np.array_equal(x, y, equal_nan=True)
     assert not np.array_equal(shared[0][2], shared[1][2])               # (two different output frames)
+
+
+def check_argument_errors(device):
+    """The contract of the two entry points, as the library on `device` states it (csrc/track_math.hpp: one source for both
+    libraries).  Every non-null pointer is a real tensor that covers the call even if it were accepted."""
+    z = lambda *shape: torch.zeros(*shape, device=device)
+    o, acc, col = z(10, 5), z(10, 5), z(10)
+    add, fin = pk.ops.track_merge_add, pk.ops.track_merge_finish
+    with pytest.raises(AssertionError, match='track_col'):
+        add(o, acc, col, col.clone(), 1, 5)
+    with pytest.raises(AssertionError, match='track_col'):
+        add(o, acc, col, col.clone(), 1, -2)
+    with pytest.raises(AssertionError, match='op code'):
+        add(o, acc, col, col.clone(), 1, 4, [0, 1, 2, 3, 0])
+    with pytest.raises(AssertionError, match='op code'):
+        add(o, acc, col, col.clone(), 1, 4, [0, 1, -1, 0, 0])
+    with pytest.raises(AssertionError, match='null best / winner'):
+        add(o, acc, None, None, 1, 4)
+    with pytest.raises(AssertionError, match='null best / winner'):
+        add(o, acc, col, None, 1, 4)
+    with pytest.raises(AssertionError, match='g = 33'):
+        add(z(4, 33), z(4, 33), None, None, 1, -1)
+    with pytest.raises(AssertionError, match='inst_id'):
+        add(o, acc, col, col.clone(), 2.5, 4)
+    with pytest.raises(AssertionError, match='inst_id'):
+        add(o, acc, col, col.clone(), 2 ** 24 + 1, 4)
+    with pytest.raises(AssertionError, match='acc must be'):
+        add(o, z(10, 6), col, col.clone(), 1, 4)
+    with pytest.raises(AssertionError, match='n_runs'):
+        fin(acc, col, 0, 4)
+    with pytest.raises(AssertionError, match='track_col'):
+        fin(acc, col, 2, 5)
+    with pytest.raises(AssertionError, match='null winner'):
+        fin(acc, None, 2, 4)
+    with pytest.raises(AssertionError, match='g = 33'):
+        fin(z(4, 33), None, 2, -1)
+    L, p = pk._lib.lib(), pk.ops._ptr                                 # what no tensor can express: short strides, null arrays
+    assert L.occ4d_track_merge_add_f32(p(o), 4, 10, 5, None, -1, 1.0, 1, p(acc), 5, None, None, None) == pk._lib.EINVAL
+    assert L.occ4d_track_merge_add_f32(p(o), 5, 10, 5, None, -1, 1.0, 1, p(acc), 4, None, None, None) == pk._lib.EINVAL
+    assert L.occ4d_track_merge_add_f32(None, 5, 10, 5, None, -1, 1.0, 1, p(acc), 5, None, None, None) == pk._lib.EINVAL
+    assert L.occ4d_track_merge_add_f32(p(o), 5, 10, 5, None, -1, 1.0, 1, None, 5, None, None, None) == pk._lib.EINVAL
+    assert L.occ4d_track_merge_add_f32(p(o), 5, 10, 5, None, -1, 1.0, 2, p(acc), 5, None, None, None) == pk._lib.EINVAL
+    assert L.occ4d_track_merge_add_f32(p(o), 5, -1, 5, None, -1, 1.0, 1, p(acc), 5, None, None, None) == pk._lib.EINVAL
+    assert L.occ4d_track_merge_finish_f32(p(acc), 4, 10, 5, 2, -1, None, None) == pk._lib.EINVAL
+    assert L.occ4d_track_merge_finish_f32(None, 5, 10, 5, 2, -1, None, None) == pk._lib.EINVAL
+    assert b'occ4d_track_merge_finish_f32' in L.occ4d_last_error()
+    assert L.occ4d_track_merge_add_f32(None, 5, 0, 5, None, 4, 1.0, 1, None, 5, None, None, None) == pk._lib.OK      # n = 0
+    assert L.occ4d_track_merge_finish_f32(None, 5, 0, 5, 1, 4, None, None) == pk._lib.OK
+    assert float(acc.abs().sum()) == 0.0 and float(o.abs().sum()) == 0.0
