@@ -19,6 +19,7 @@ FEATURE_HEADERS = {
     'OCCL': 'occ4d_occl.h',             # the id histogram behind the live occlusion fractions (occlusion.py); the bin limit, the extra bins
     'TRACK': 'occ4d_track.h',           # the running merge of the per-instance reruns (inference.perform_inference, track_mode 'all')
     'PROJECT': 'occ4d_project.h',       # the camera projection, the z-buffer and the visibility test (projection.py)
+    'INST': 'occ4d_inst.h',             # the instance statistics (evaluation.InstanceStats): the layout of the frame table and the two arrays
 }
 
 

@@ -28,18 +28,21 @@
 #include "occ4d_occl.h"
 #include "occ4d_track.h"
 #include "occ4d_project.h"
+#include "occ4d_inst.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
 #include "occl_math.hpp"
 #include "track_math.hpp"
 #include "project_math.hpp"
+#include "inst_math.hpp"
 
 namespace fe = occ4d_frontend;
 namespace ev = occ4d_eval;
 namespace oc = occ4d_occl;
 namespace tk = occ4d_track;
 namespace pj = occ4d_project;
+namespace in = occ4d_inst;
 
 static thread_local char g_err[512] = "";
 
@@ -672,6 +675,67 @@ int occ4d_visibility_f32(const float* rows, int64_t ld, int n, const float* rt, 
   OCC4D_TRY(pj::check_visibility(rows, ld, n, rt, k, V, depth, ld_depth, H, W, code, empty, a));
   if (empty) return OCC4D_OK;
   for (int64_t e = 0; e < a.items; ++e) pj::visibility_item(a, e, depth, ld_depth, H, W, margin, code);
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- instance statistics
+// include/occ4d_inst.h: the passes of csrc/inststats.hip over csrc/inst_math.hpp, rows and ids in order.
+int64_t occ4d_inst_frame_len(int n_ids) { return in::frame_len(n_ids); }
+int64_t occ4d_inst_counts_len(int n_groups) { return in::counts_len(n_groups); }
+int64_t occ4d_inst_sums_len(int n_groups) { return in::sums_len(n_groups); }
+
+int occ4d_inst_confusion_f32(const float* density, int64_t ld_density, const float* pred_id, int64_t ld_pred, int n, const int32_t* nn_idx,
+                             const float* nn_dist, const float* target_id, int64_t ld_target, int m, int n_ids, float density_threshold,
+                             float radius, int64_t* frame, void*) {
+  in::ConfusionArgs a; bool empty;
+  OCC4D_TRY(in::check_confusion(density, ld_density, pred_id, ld_pred, n, nn_idx, nn_dist, target_id, ld_target, m, n_ids,
+                                density_threshold, radius, frame, empty, a));
+  if (empty) return OCC4D_OK;
+  for (int64_t i = 0; i < n; ++i) {
+    const int cell = in::confusion_cell(a, i);
+    if (cell == in::ROW_BAD) ++frame[OCC4D_INST_BAD_ROWS];
+    else ++frame[in::frame_confusion(n_ids) + cell];
+  }
+  return OCC4D_OK;
+}
+
+int occ4d_inst_points_f32(const float* rows, int64_t ld, int n, const float* id, int64_t ld_id, int n_ids, int side, int64_t* frame,
+                          void*) {
+  in::PointArgs a; bool empty;
+  OCC4D_TRY(in::check_points(rows, ld, n, id, ld_id, n_ids, side, frame, empty, a));
+  if (empty) return OCC4D_OK;
+  int64_t* table = frame + in::frame_points(n_ids, side);
+  for (int64_t i = 0; i < n; ++i) {
+    int64_t q[3];
+    const int k = in::point_row(a, i, q);
+    if (k == in::ROW_SKIP) continue;
+    if (k == in::ROW_BAD) {
+      ++frame[OCC4D_INST_BAD_ROWS];
+      continue;
+    }
+    int64_t* e = table + (int64_t)k * OCC4D_INST_POINT_WORDS;
+    ++e[OCC4D_INST_POINT_COUNT];
+    for (int d = 0; d < 3; ++d) e[OCC4D_INST_POINT_SX + d] += q[d];
+  }
+  return OCC4D_OK;
+}
+
+int occ4d_inst_fold(const int64_t* frame, int n_ids, const int32_t* inst_group, int n_groups, int64_t* counts, double* sums, void*) {
+  OCC4D_TRY(in::check_fold(frame, n_ids, n_groups, counts, sums));
+  in::IdTerms terms[OCC4D_INST_MAX_IDS];
+  int64_t bad = frame[OCC4D_INST_BAD_ROWS];
+  for (int i = 0; i < n_ids; ++i) {
+    terms[i] = in::fold_id(frame, n_ids, inst_group, n_groups, i);
+    bad += terms[i].group == -2;
+  }
+  for (int g = 0; g < n_groups; ++g) {
+    int64_t c[OCC4D_INST_GROUP_COUNTS];
+    double s[OCC4D_INST_GROUP_SUMS];
+    in::fold_group(terms, n_ids, g, c, s);
+    for (int k = 0; k < OCC4D_INST_GROUP_COUNTS; ++k) counts[OCC4D_INST_HEAD + g * OCC4D_INST_GROUP_COUNTS + k] += c[k];
+    for (int k = 0; k < OCC4D_INST_GROUP_SUMS; ++k) sums[g * OCC4D_INST_GROUP_SUMS + k] += s[k];
+  }
+  counts[OCC4D_INST_BAD_ROWS] += bad;
   return OCC4D_OK;
 }
 

@@ -31,6 +31,11 @@ _EC = _lib.EVAL_CONSTANTS
 # GREATER rows are (x, y, z, instance, view, R, G, B, mark_track), CARLA rows (x, y, z, cosine, instance, semantic, view,
 # R, G, B, mark_track)
 TARGET_COLUMNS = {'greater': dict(col_rgb=5, col_track=8, col_sem=-1), 'carla': dict(col_rgb=7, col_track=10, col_sem=5)}
+# target column of the instance id of the two data kinds (the rows above).  A table of its own: the dicts of TARGET_COLUMNS are
+# splatted into ops.eval_query_stats
+INSTANCE_COLUMNS = {'greater': 3, 'carla': 4}
+_IC = _lib.INST_CONSTANTS
+_INST_COUNT_NAMES = ('N_GT', 'N_PRED', 'N_MATCH', 'SUM_INTER', 'SUM_UNION', 'N_CENTROID')
 _COUNT_NAMES = ('OCC_TP', 'OCC_FP', 'OCC_FN', 'OCC_TN', 'TRACK_TP', 'TRACK_FP', 'TRACK_FN', 'TRACK_TN', 'SEG_IGNORED',
                 'N_ACCURACY', 'N_COMPLETENESS', 'N_COLOR', 'N_SEG')
 
@@ -46,7 +51,9 @@ class EvalStats:
     arrays, `counts` (int64) and `sums` (float64), that `add_frame` accumulates onto with no host read of their contents,
     that sum across frames, clips and ranks (`merge`, `+=`, `all_reduce`) and that `summary()` turns into the usual figures
     with ONE host read.  Every statistic is kept per group (n_groups <= 8: the caller's partition of the target points,
-    e.g. visible / occluded); semantic_classes (<= 32) sizes the segmentation confusion matrix, 0 = none."""
+    e.g. visible / occluded); semantic_classes (<= 32) sizes the segmentation confusion matrix, 0 = none.
+    In track_mode 'all' the TRACK_* counts compare a winner id with 0.5 and mean nothing: InstanceStats is the scorer for that
+    mode."""
 
     def __init__(self, n_groups=1, semantic_classes=0, device=None):
         self.n_groups, self.semantic_classes = int(n_groups), int(semantic_classes)
@@ -171,8 +178,167 @@ class EvalStats:
         return res
 
 
+class InstanceStats:
+    """Additive instance-level statistics of a dense instance labelling (perform_inference with track_mode 'all': the merged
+    mark_track channel holds the id of the most confident rerun, or -1) against ground-truth frames (include/occ4d_inst.h): per
+    frame a device table -- the (n_ids + 1)^2 confusion of ALL queries, class n_ids = none, and per id the count and the
+    fixed-point coordinate sums of the predicted-solid rows and of the target points -- that `add_frame` fills and folds onto
+    `counts` (int64) and `sums` (float64) with no host read.  The two arrays sum across frames, clips and ranks (`merge`, `+=`,
+    `all_reduce`); `summary()` turns them into instance IoU, panoptic quality and the centroid error with ONE host read, and
+    `frame_tables()` reads the latest frame's table: where every tracked object is.  Every figure is kept per group
+    (n_groups <= 8: the caller's partition of the ids, e.g. `occlusion_groups`); n_ids <= 64.  A sibling of EvalStats, whose
+    TRACK_* counts mean nothing for a winner id."""
+
+    def __init__(self, n_ids, n_groups=1, device=None):
+        self.n_ids, self.n_groups = int(n_ids), int(n_groups)
+        n_frame, n_counts, n_sums = ops.inst_layout(self.n_ids, self.n_groups)
+        self.device = torch.device('cpu' if _lib.is_twin() else 'cuda') if device is None else torch.device(device)
+        self.frame = torch.zeros((n_frame,), dtype=torch.int64, device=self.device)
+        self.counts = torch.zeros((n_counts,), dtype=torch.int64, device=self.device)
+        self.sums = torch.zeros((n_sums,), dtype=torch.float64, device=self.device)
+
+    _tensor = EvalStats._tensor
+
+    def add_frame(self, points_query, implicit_output, target_rows, *, density_threshold, point_occupancy_radius, color_mode,
+                  data_kind, inst_group=None, nn=None, solid=None, col_inst=None, pred_id=None):
+        """Adds one output frame: points_query (N, 3 or 4), implicit_output (N, G) (squashed and merged, as perform_inference
+        returns it), target_rows (M, Dt) (device tensors or numpy, uploaded once).  inst_group: (n_ids,) integer group id per
+        instance id.  nn = (idx (N,), dist (N,)): the query -> target 1-NN if the caller has it; solid: the predicted-solid rows
+        of ops.split_solid_air (xyz, t, then the G channels) if the caller has split them.  The target's instance column
+        defaults from data_kind (INSTANCE_COLUMNS).  pred_id (N,): another labelling of the queries to score instead of the
+        mark_track channel.  The frame table is zero-filled, filled by the confusion pass and the two point passes and folded;
+        no host read."""
+        q, out, tgt = self._tensor(points_query), self._tensor(implicit_output), self._tensor(target_rows)
+        assert q.dim() == 2 and q.shape[1] in (3, 4) and out.dim() == 2 and out.shape[0] == q.shape[0], 'points_query (N, 3 or 4), implicit_output (N, G)'
+        assert tgt.dim() == 2 and tgt.shape[0] >= 1 and tgt.shape[1] >= 3, 'target_rows must be (M >= 1, Dt >= 3)'
+        col = INSTANCE_COLUMNS.get(data_kind) if col_inst is None else int(col_inst)
+        assert col is not None and 0 <= col < tgt.shape[1], 'no instance column: data_kind = %r, col_inst = %r, Dt = %d' % (data_kind, col_inst, tgt.shape[1])
+        track = inference.get_track_idx(color_mode)
+        if pred_id is None:
+            assert track < out.shape[1], 'implicit_output has no mark_track channel %d (G = %d)' % (track, out.shape[1])
+        else:
+            pred_id = self._tensor(pred_id)
+            assert pred_id.shape == (q.shape[0],), 'pred_id must be (N,)'
+        grp = None if inst_group is None else self._tensor(np.asarray(inst_group) if not torch.is_tensor(inst_group) else inst_group,
+                                                          torch.int32).contiguous()
+        if q.shape[0] == 0:
+            return self
+        if nn is None:
+            idx, dist = ops.knn(q[:, :3], tgt[:, :3], 1, metric=1, return_dist=True)
+            nn = (idx[:, 0], dist[:, 0])
+        idx, dist = self._tensor(nn[0], torch.int32), self._tensor(nn[1])
+        if pred_id is not None:               # the solid rows carry the track channel, not this labelling: split it alongside
+            q4 = q if q.shape[1] == 4 else torch.nn.functional.pad(q, (0, 1))
+            both = torch.cat([out[:, :1], pred_id[:, None]], dim=1)
+            solid = ops.split_solid_air(q4.contiguous(), both, density_threshold)[0]
+            solid_ids, pred_col = solid[:, 5], pred_id
+        else:
+            if solid is None:
+                q4 = q if q.shape[1] == 4 else torch.nn.functional.pad(q, (0, 1))
+                solid = ops.split_solid_air(q4.contiguous(), out, density_threshold)[0]
+            solid = self._tensor(solid)
+            solid_ids, pred_col = solid[:, 4 + track], out[:, track]
+        self.frame.zero_()
+        ops.inst_confusion(out[:, 0], pred_col, idx, dist, tgt[:, col], self.frame, n_ids=self.n_ids,
+                           density_threshold=density_threshold, radius=point_occupancy_radius)
+        ops.inst_points(solid, solid_ids, self.frame, n_ids=self.n_ids, side=_IC['SIDE_PRED'])
+        ops.inst_points(tgt, tgt[:, col], self.frame, n_ids=self.n_ids, side=_IC['SIDE_GT'])
+        ops.inst_fold(self.frame, self.counts, self.sums, n_ids=self.n_ids, n_groups=self.n_groups, inst_group=grp)
+        return self
+
+    def _same_layout(self, other):
+        assert isinstance(other, InstanceStats) and other.n_groups == self.n_groups, 'InstanceStats of different n_groups do not add'
+
+    def merge(self, other):
+        self._same_layout(other)
+        self.counts += other.counts.to(self.device)
+        self.sums += other.sums.to(self.device)
+        return self
+
+    __iadd__ = merge
+
+    def all_reduce(self, group=None):
+        """torch.distributed SUM over both arrays (the same layout on every rank)."""
+        import torch.distributed as dist
+        dist.all_reduce(self.counts, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(self.sums, op=dist.ReduceOp.SUM, group=group)
+        return self
+
+    def state(self):
+        """The accumulators as numpy (copies: a later add does not change them); from_state() is the way back.  The frame
+        table is not part of the state."""
+        return dict(n_ids=self.n_ids, n_groups=self.n_groups, counts=self.counts.cpu().numpy().copy(), sums=self.sums.cpu().numpy().copy())
+
+    @classmethod
+    def from_state(cls, state, device=None):
+        self = cls(int(state['n_ids']), int(state['n_groups']), device)
+        counts, sums = np.asarray(state['counts'], np.int64), np.asarray(state['sums'], np.float64)
+        assert counts.shape == tuple(self.counts.shape) and sums.shape == tuple(self.sums.shape)
+        self.counts.copy_(torch.from_numpy(counts))
+        self.sums.copy_(torch.from_numpy(sums))
+        return self
+
+    def frame_tables(self):
+        """The latest frame's table, from one host read: 'confusion' (n_ids + 1, n_ids + 1) int64 (row = ground truth, column
+        = prediction, the last class = none), 'bad_rows', and per side 'pred' / 'gt' a dict of 'count' (n_ids,) int64 and
+        'centroid' (n_ids, 3) float64, nan where the count is 0: the position of every object in this frame (its trajectory,
+        when read once per output frame)."""
+        K, C, W = self.n_ids, self.n_ids + 1, _IC['POINT_WORDS']
+        f = self.frame.cpu().numpy()
+        head = _IC['FRAME_HEAD']
+        res = dict(confusion=f[head:head + C * C].reshape(C, C).copy(), bad_rows=int(f[_IC['BAD_ROWS']]))
+        for name, side in (('pred', _IC['SIDE_PRED']), ('gt', _IC['SIDE_GT'])):
+            t = f[head + C * C + side * K * W:head + C * C + (side + 1) * K * W].reshape(K, W)
+            count = t[:, _IC['POINT_COUNT']].copy()
+            s = t[:, _IC['POINT_SX']:_IC['POINT_SX'] + 3].astype(np.float64)
+            res[name] = dict(count=count, centroid=_ratio(s, count[:, None]) / float(1 << _IC['FRACTION_BITS']))
+        return res
+
+    def summary(self):
+        """The figures per group, as float64 arrays of shape (n_groups,) (nan where the denominator is 0), from one host read:
+        instance_miou (mean IoU over the annotated instances), instance_iou_micro (summed intersections over summed unions),
+        rq, sq, pq (recognition, segmentation and panoptic quality: an annotated instance is matched when its IoU > 0.5),
+        centroid_error / centroid_error_sq (mean distance / squared distance between the centroid of an instance's predicted-
+        solid queries and that of its target points).  'counts': the raw counts by name ((n_groups,) int64 each), 'bad_rows'.
+        Raises ValueError when rows or ids were skipped (bad_rows > 0)."""
+        G = self.n_groups
+        both = torch.cat([self.counts.view(torch.float64), self.sums]).cpu()           # (bit reinterpretation: ONE transfer)
+        counts, sums = both[:self.counts.numel()].view(torch.int64).numpy(), both[self.counts.numel():].numpy()
+        bad = int(counts[_IC['BAD_ROWS']])
+        if bad > 0:
+            raise ValueError('InstanceStats: %d rows or ids were skipped (nn_idx outside the target, an id that is no integer in '
+                             '[0, %d) and not negative, a coordinate beyond 1024, or a group id outside [0, %d))' % (bad, self.n_ids, G))
+        per = counts[_IC['HEAD']:].reshape(G, _IC['GROUP_COUNTS'])
+        c = {name.lower(): per[:, _IC[name]].copy() for name in _INST_COUNT_NAMES}
+        s = sums.reshape(G, _IC['GROUP_SUMS'])
+        match = c['n_match']
+        res = dict(instance_miou=_ratio(s[:, _IC['SUM_IOU']], c['n_gt']), instance_iou_micro=_ratio(c['sum_inter'], c['sum_union']),
+                   rq=_ratio(match, match + 0.5 * (c['n_pred'] - match) + 0.5 * (c['n_gt'] - match)),
+                   sq=_ratio(s[:, _IC['SUM_IOU_MATCHED']], match),
+                   centroid_error=_ratio(s[:, _IC['SUM_CENTROID_D']], c['n_centroid']),
+                   centroid_error_sq=_ratio(s[:, _IC['SUM_CENTROID_D2']], c['n_centroid']))
+        res['pq'] = res['sq'] * res['rq']
+        res.update(counts=c, bad_rows=bad)
+        return res
+
+
+def occlusion_groups(live_occl_row, valo_ids_pad, num_valo_ids, n_ids, edges=(0.25, 0.75)):
+    """(n_ids,) int32 group of every instance id for InstanceStats, from the outputs of occlusion.live_occlusion (host
+    arithmetic): live_occl_row (max_valo_ids,) = the occlusion fractions of one input frame, valo_ids_pad / num_valo_ids = the
+    ids they belong to.  A valo id with fraction f gets group np.searchsorted(edges, f, side='right') (0 .. len(edges)); every
+    other id the last group, len(edges) + 1: an InstanceStats for it needs n_groups = len(edges) + 2."""
+    edges = np.asarray(edges, np.float64)
+    assert edges.ndim == 1 and bool((np.diff(edges) > 0).all()), 'edges must ascend'
+    group = np.full((int(n_ids),), len(edges) + 1, dtype=np.int32)
+    ids = np.asarray(valo_ids_pad)[:int(num_valo_ids)].astype(np.int64)
+    frac = np.asarray(live_occl_row, np.float64)[:int(num_valo_ids)]
+    keep = (ids >= 0) & (ids < int(n_ids))
+    group[ids[keep]] = np.searchsorted(edges, frac[keep], side='right').astype(np.int32)
+    return group
+
+
 def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt=False, reuse_encode=True, stats=None,
-                  stats_group_fn=None, stats_occlusion=None):
+                  stats_group_fn=None, stats_occlusion=None, inst_stats=None, inst_group_fn=None):
     """batch: dict with 'pcl_input' (1,N,8), 'pcl_input_sem' (1,N,1-3), 'pcl_target' list of (1,T,9-11) tensors and
     batch['meta_data']['pcl_target_size'] (list of (1,) tensors), as the reference's test data loader yields them
     (data/data_greater.py:593-606, data/data_carla.py:651-661).  args: namespace with the test_args fields used
@@ -181,7 +347,9 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
     decode); stats_group_fn(frame_rows) -> (T,) integer array: the group of every target point.  None: nothing is scored.
     stats_occlusion: instead of stats_group_fn, a dict 'depth' (T_out, H, W), 'cam_RT' (T_out, 3, 4), 'cam_K' ((3, 3) or
     (T_out, 3, 3)), 'margin': the group of a target point of output frame t is its projection.visibility code against depth[t]
-    under camera t (VISIBLE 0 / OCCLUDED 1 / OUTSIDE 2; `stats` needs n_groups >= 3), computed on the device."""
+    under camera t (VISIBLE 0 / OCCLUDED 1 / OUTSIDE 2; `stats` needs n_groups >= 3), computed on the device.
+    inst_stats: an InstanceStats that every output frame is added to in the same way (track_mode 'all': the instance
+    labelling); inst_group_fn(time_idx, frame_rows) -> (n_ids,) integer array: the group of every instance id, None: group 0."""
     assert stats_group_fn is None or stats_occlusion is None, 'stats_group_fn and stats_occlusion exclude each other'
     if stats_occlusion is not None and stats is not None:
         assert stats.n_groups >= 3, 'stats_occlusion needs an EvalStats with n_groups >= 3, got %d' % stats.n_groups
@@ -210,6 +378,9 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
                                               stats_occlusion['depth'][time_idx], occ_rt[time_idx],
                                               occ_k if np.ndim(occ_k) == 2 else occ_k[time_idx], stats_occlusion['margin'])[0]
             stats_kw = dict(stats=stats, stats_target=frame, stats_group=group)
+        if inst_stats is not None:
+            stats_kw.update(inst_stats=inst_stats, stats_target=frame,
+                            inst_group=None if inst_group_fn is None else inst_group_fn(time_idx, frame))
         res = inference.perform_inference(
             pcl_input.clone(), sem_inference, frame if save_gt else None, networks, device, 'if', args.min_z,
             args.cr_cube_bounds, args.color_mode, time_idx, logger, sample_implicit=args.sample_implicit,

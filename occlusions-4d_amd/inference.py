@@ -151,7 +151,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                       point_occupancy_radius=0.2, semantic_classes=13,
                       density_threshold=0.5, data_kind='', cube_mode=4, compress_air=False,
                       encoded=None, return_encoded=False, neighbour_lists=None, stats=None, stats_target=None,
-                      stats_group=None, track_merge='device'):
+                      stats_group=None, track_merge='device', inst_stats=None, inst_group=None):
     """One encode of the input point-cloud video + decode of all query points of one output
     frame.  Returns dict(output_solid, output_air, pcl_abstract, features_global,
     implicit_output, points_query) of float32 numpy arrays.
@@ -162,7 +162,10 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     reference for these queries (LocalPclResnetFC.forward's extension; either entry may be None); `stats` = an
     evaluation.EvalStats this frame is added to, scored on the device against `pcl_target_frame` (or `stats_target` when that
     is not passed: no gt_solid / gt_air then) with `stats_group` = the group id per target point; the query -> target search
-    and the solid split are shared with the gt branch and the result dict is what it is without `stats`.
+    and the solid split are shared with the gt branch and the result dict is what it is without `stats`; `inst_stats` = an
+    evaluation.InstanceStats this frame is added to in the same way (the scorer of track_mode 'all': the merged mark_track
+    channel as an instance labelling) with `inst_group` = the group id per instance id; it shares the upload of the target
+    rows, the search and the split with `stats`, and changes neither the result dict nor the one host wait.
     In track_mode 'all', `encoded` / '_encoded' are dicts {instance id: (pcl_abstract, features_global)}, one entry per rerun.
     `track_merge`: where the reruns of track_mode 'all' are merged.  'device': a running merge in the library
     (ops.track_merge_add / track_merge_finish: the squash, the sums and the winner / best update in one pass per rerun), the
@@ -232,9 +235,9 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
 
         gt_available = pcl_target_frame is not None
         nn_dev = target_dev = None
-        if stats is not None:                 # one upload of the target rows, one search for both consumers
+        if stats is not None or inst_stats is not None:       # one upload of the target rows, one search for all consumers
             stats_rows = pcl_target_frame if gt_available else stats_target
-            assert stats_rows is not None, 'stats needs a target frame: pcl_target_frame or stats_target'
+            assert stats_rows is not None, 'stats / inst_stats need a target frame: pcl_target_frame or stats_target'
             target_dev = torch.as_tensor(np.ascontiguousarray(stats_rows, dtype=np.float32) if isinstance(stats_rows, np.ndarray)
                                          else stats_rows).to(device=device, dtype=torch.float32)
             nn_dev = nn_target(queries_dev[:, :3], target_dev[:, :3])
@@ -257,6 +260,10 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                             point_occupancy_radius=point_occupancy_radius, color_mode=color_mode,
                             predict_segmentation=predict_segmentation, track_mode=track_mode, data_kind=data_kind,
                             target_group=stats_group, nn=nn_dev, solid=solid)
+        if inst_stats is not None:
+            inst_stats.add_frame(queries_dev, output_dev, target_dev, density_threshold=density_threshold,
+                                 point_occupancy_radius=point_occupancy_radius, color_mode=color_mode, data_kind=data_kind,
+                                 inst_group=inst_group, nn=nn_dev, solid=solid)
         # (the reference's concatenate with the int64 argmax promotes the compressed air rows to float64: converted on
         # the device, not by a host pass over the array)
         solid_h = copies.fetch(solid)

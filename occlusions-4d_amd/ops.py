@@ -1196,6 +1196,70 @@ def eval_target_stats(dist, counts, sums, *, n_groups=1, n_classes=0, target_gro
                                                       _ptr(ws), _stream()))
 
 
+def inst_layout(n_ids, n_groups=1):
+    """(len(frame), len(counts), len(sums)) of the instance statistics arrays (include/occ4d_inst.h) for this many ids / groups."""
+    L = _lib.lib()
+    lens = (int(L.occ4d_inst_frame_len(int(n_ids))), int(L.occ4d_inst_counts_len(int(n_groups))), int(L.occ4d_inst_sums_len(int(n_groups))))
+    assert min(lens) > 0, 'n_ids = %s must be in 1 .. %d and n_groups = %s in 1 .. %d' % (
+        n_ids, _lib.INST_CONSTANTS['MAX_IDS'], n_groups, _lib.INST_CONSTANTS['MAX_GROUPS'])
+    return lens
+
+
+def _inst_column(t, n, name, dtype=torch.float32):
+    """(tensor, element stride) of an (n,) operand used as it is: a column view of a wider array keeps its stride."""
+    t = _dev(t, dtype, name)
+    assert tuple(t.shape) == (n,), '%s must be (%d,), got %s' % (name, n, tuple(t.shape))
+    if n > 1 and t.stride(0) < 1:
+        t = t.contiguous()
+    return t, (t.stride(0) if n > 1 else 1)
+
+
+def _inst_frame(frame, n_ids):
+    f = _dev(frame, torch.int64, 'frame')
+    assert f.is_contiguous() and f.numel() == inst_layout(n_ids)[0], 'frame must be a contiguous int64 tensor of occ4d_inst_frame_len(n_ids) words'
+    return f
+
+
+def inst_confusion(density, pred_id, nn_idx, nn_dist, target_id, frame, *, n_ids, density_threshold=0.5, radius=0.2):
+    """Adds the instance confusion of the N queries of a frame onto the zero-filled or running `frame` table, in place
+    (occ4d_inst_confusion_f32): density (N,), pred_id (N,), target_id (M,) float32 (column views keep their stride), nn_idx (N,)
+    int32, nn_dist (N,).  No host read."""
+    n = density.shape[0]
+    d, ld_d = _inst_column(density, n, 'density')
+    p, ld_p = _inst_column(pred_id, n, 'pred_id')
+    t, ld_t = _inst_column(target_id, target_id.shape[0], 'target_id')
+    idx, dist = _dev(nn_idx, torch.int32, 'nn_idx'), _dev(nn_dist, name='nn_dist')
+    assert idx.shape == (n,) and dist.shape == (n,), 'nn_idx / nn_dist must be (N,)'
+    idx, dist = idx.contiguous(), dist.contiguous()
+    f = _inst_frame(frame, n_ids)
+    _lib.check(_lib.lib().occ4d_inst_confusion_f32(_ptr(d), ld_d, _ptr(p), ld_p, n, _ptr(idx), _ptr(dist), _ptr(t), ld_t, t.shape[0],
+                                                   int(n_ids), float(density_threshold), float(radius), _ptr(f), _stream()))
+
+
+def inst_points(rows, ids, frame, *, n_ids, side):
+    """Adds the per-instance point counts and fixed-point coordinate sums of rows (n, >= 3) with ids (n,) onto side `side`
+    (0 predicted, 1 ground truth) of the `frame` table, in place (occ4d_inst_points_f32).  No host read."""
+    r, ld = _rows(_dev(rows, name='rows'), 'rows')
+    n = r.shape[0]
+    assert r.shape[1] >= 3, 'rows must be (n, >= 3)'
+    i, ld_i = _inst_column(ids, n, 'ids')
+    f = _inst_frame(frame, n_ids)
+    _lib.check(_lib.lib().occ4d_inst_points_f32(_ptr(r), ld, n, _ptr(i), ld_i, int(n_ids), int(side), _ptr(f), _stream()))
+
+
+def inst_fold(frame, counts, sums, *, n_ids, n_groups=1, inst_group=None):
+    """Adds one frame table onto the running `counts` (int64) / `sums` (float64), in place (occ4d_inst_fold); inst_group
+    (n_ids,) int32 or None (every id in group 0).  `frame` is left as it is.  No host read."""
+    f = _inst_frame(frame, n_ids)
+    c, s = _dev(counts, torch.int64, 'counts'), _dev(sums, torch.float64, 'sums')
+    assert c.is_contiguous() and s.is_contiguous() and (c.numel(), s.numel()) == inst_layout(n_ids, n_groups)[1:]
+    grp = None
+    if inst_group is not None:
+        grp = _dev(inst_group, torch.int32, 'inst_group')
+        assert grp.shape == (int(n_ids),) and grp.is_contiguous(), 'inst_group must be a contiguous (n_ids,) int32 tensor'
+    _lib.check(_lib.lib().occ4d_inst_fold(_ptr(f), int(n_ids), _ptr(grp), int(n_groups), _ptr(c), _ptr(s), _stream()))
+
+
 def id_histogram(rows, col, seg_offsets, n_ids, key=None, pred_col=-1, pred_values=(), out=None):
     """Segmented histogram of the ids in column `col` of rows (n, d): -> (S, n_ids + 2) int32 on the device, ADDED onto `out`
     when given (occ4d_id_histogram_f32, include/occ4d_occl.h).  seg_offsets: S + 1 ascending row offsets from 0 to n -- a host
