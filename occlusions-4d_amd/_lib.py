@@ -20,6 +20,7 @@ FEATURE_HEADERS = {
     'TRACK': 'occ4d_track.h',           # the running merge of the per-instance reruns (inference.perform_inference, track_mode 'all')
     'PROJECT': 'occ4d_project.h',       # the camera projection, the z-buffer and the visibility test (projection.py)
     'INST': 'occ4d_inst.h',             # the instance statistics (evaluation.InstanceStats): the layout of the frame table and the two arrays
+    'REFINE': 'occ4d_refine.h',         # the coarse-to-fine decode of the query grid (inference.perform_inference(refine=...))
 }
 
 

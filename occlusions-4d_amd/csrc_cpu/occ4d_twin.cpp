@@ -29,6 +29,7 @@
 #include "occ4d_track.h"
 #include "occ4d_project.h"
 #include "occ4d_inst.h"
+#include "occ4d_refine.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -36,6 +37,7 @@
 #include "track_math.hpp"
 #include "project_math.hpp"
 #include "inst_math.hpp"
+#include "refine_math.hpp"
 
 namespace fe = occ4d_frontend;
 namespace ev = occ4d_eval;
@@ -43,6 +45,7 @@ namespace oc = occ4d_occl;
 namespace tk = occ4d_track;
 namespace pj = occ4d_project;
 namespace in = occ4d_inst;
+namespace rf = occ4d_refine;
 
 static thread_local char g_err[512] = "";
 
@@ -636,6 +639,34 @@ int occ4d_track_merge_finish_f32(float* acc, int64_t ld_acc, int n, int g, int n
       float& v = acc[i * ld_acc + c];
       v = tk::finish_one(f, v, i, c);
     }
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- grid refinement
+// include/occ4d_refine.h: the passes of csrc/refine.hip over csrc/refine_math.hpp, blocks, points and rows in order.  A selected
+// row's position is block_offsets[tile] + its rank in the tile, as on the device: never a running count over the whole grid.
+int occ4d_refine_mark_f32(const float* rep_density, int64_t ld_rep, int nx, int ny, int nz, int b, int dilate, int op, float low,
+                          int32_t* active, float* key, void*) {
+  rf::MarkArgs a; bool empty;
+  OCC4D_TRY(rf::check_mark(rep_density, ld_rep, nx, ny, nz, b, dilate, op, low, active, key, empty, a));
+  if (empty) return OCC4D_OK;
+  for (int64_t blk = 0; blk < a.grid.blocks; ++blk) active[blk] = rf::active_of(a, blk);
+  for (int64_t i = 0; i < a.grid.n; ++i) key[i] = rf::key_of(a, i);
+  return OCC4D_OK;
+}
+int occ4d_refine_expand_f32(const float* key, const int32_t* block_offsets, const float* rep_out, int64_t ld_rep, const float* fine_out,
+                            int64_t ld_fine, int n_fine, int nx, int ny, int nz, int b, int g, float* out, int64_t ld_out, void*) {
+  rf::ExpandArgs e; bool empty;
+  OCC4D_TRY(rf::check_expand(key, block_offsets, rep_out, ld_rep, fine_out, ld_fine, n_fine, nx, ny, nz, b, g, out, ld_out, empty, e));
+  if (empty) return OCC4D_OK;
+  for (int64_t tile = 0; tile < e.tiles; ++tile) {
+    int64_t rank = 0;
+    for (int64_t i = tile * rf::TILE; i < std::min(e.grid.n, (tile + 1) * rf::TILE); ++i) {
+      const bool selected = rf::kept(key[i]);
+      std::memcpy(out + i * ld_out, rf::source_row(e, i, selected, (int64_t)block_offsets[tile] + rank), sizeof(float) * g);
+      rank += selected;
+    }
+  }
   return OCC4D_OK;
 }
 

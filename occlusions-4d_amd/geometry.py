@@ -102,6 +102,13 @@ def _grid_counts(num_sample, ext):
     return [int(np.ceil(density * e)) for e in ext]
 
 
+def grid_counts(num_sample, min_z, cube_bounds, data_kind, cube_mode):
+    """(nx, ny, nz) of the cell-centred query grid that point_sample_mode 'grid' generates for these arguments (x slowest, z
+    fastest: nx * ny * nz >= num_sample rows)."""
+    bounds = _query_bounds(min_z, cube_bounds, data_kind, cube_mode)
+    return tuple(_grid_counts(num_sample, [hi - lo for lo, hi in bounds]))
+
+
 def sample_implicit_points_blind_device(num_sample, min_z, cube_bounds, time_idx, data_kind, cube_mode,
                                         point_sample_mode, device):
     """sample_implicit_points_blind_numpy with the result resident on `device`: the grid is generated by

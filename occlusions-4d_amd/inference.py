@@ -8,6 +8,7 @@ device; one device-to-host copy happens at the end instead of one per batch (:20
 The optional ground-truth 1-NN labelling branch (:270-276, sklearn KDTree on targets)
 is provided on the streaming k = 1 kernel; track_mode 'all' reruns the path once per instance id.
 """
+import functools
 import os
 
 import numpy as np
@@ -144,6 +145,33 @@ class _HostCopies:
         return h.numpy() if torch.is_tensor(h) else h
 
 
+_REQUIRED = object()
+
+
+class GridRefine:
+    """One-level coarse-to-fine decode of the dense query grid (perform_inference(refine=...), include/occ4d_refine.h).  The
+    grid is cut into blocks of `block` points per axis (2 .. 8; edge blocks are clipped).  Pass 1 decodes one representative
+    per block, the grid point at min(block index * block + block // 2, n_axis - 1) per axis.  A block is hot when its
+    representative's squashed density d satisfies not (d < low); it is active when a block within Chebyshev distance `dilate`
+    (0 .. 2) is hot.  Pass 2 decodes the other points of the active blocks; every point that was not decoded takes its
+    block's representative row.  `low` has no default: the value that loses no solid query depends on the trained density
+    field."""
+
+    def __init__(self, block=2, low=_REQUIRED, dilate=1):
+        if low is _REQUIRED:
+            raise TypeError("GridRefine needs `low`: the density below which a block's representative counts as air")
+        for name, v, lo, hi in (('block', block, 2, 8), ('dilate', dilate, 0, 2)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError('GridRefine: %s = %r must be an integer in %d .. %d' % (name, v, lo, hi))
+        low = float(low)
+        if low != low:
+            raise ValueError('GridRefine: low is NaN')
+        self.block, self.low, self.dilate = int(block), low, int(dilate)
+
+    def __repr__(self):
+        return 'GridRefine(block=%d, low=%r, dilate=%d)' % (self.block, self.low, self.dilate)
+
+
 def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, device, task, min_z,
                       cube_bounds, color_mode, time_idx, logger,
                       sample_implicit=True, num_sample=16384, point_sample_mode='random',
@@ -151,7 +179,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                       point_occupancy_radius=0.2, semantic_classes=13,
                       density_threshold=0.5, data_kind='', cube_mode=4, compress_air=False,
                       encoded=None, return_encoded=False, neighbour_lists=None, stats=None, stats_target=None,
-                      stats_group=None, track_merge='device', inst_stats=None, inst_group=None):
+                      stats_group=None, track_merge='device', inst_stats=None, inst_group=None, refine=None):
     """One encode of the input point-cloud video + decode of all query points of one output
     frame.  Returns dict(output_solid, output_air, pcl_abstract, features_global,
     implicit_output, points_query) of float32 numpy arrays.
@@ -170,10 +198,30 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     `track_merge`: where the reruns of track_mode 'all' are merged.  'device': a running merge in the library
     (ops.track_merge_add / track_merge_finish: the squash, the sums and the winner / best update in one pass per rerun), the
     merged tensor stays on the device for the split and the scoring, and the host blocks once, at the end.  'host': every
-    rerun is copied to the host, multi_track_merge runs in numpy and the merged array is uploaded again.  Same bits."""
+    rerun is copied to the host, multi_track_merge runs in numpy and the merged array is uploaded again.  Same bits.
+    `refine`: a GridRefine, or None = every query is decoded.  point_sample_mode 'grid' only, and not with `neighbour_lists`
+    (ValueError).  Every run decodes one representative per block and then the other points of the active blocks; the
+    dense (N, G) output is rebuilt on the device, so the split, compress_air, `stats`, `inst_stats`, the track merge and the
+    result dict work on it as on a dense decode.  THE CONTRACT, and nothing stronger: every decoded row equals the dense
+    call's row bit for bit; every row that was not decoded is a copy of its block's representative row, whose density is
+    below `low`.  With refine.low <= density_threshold, output_solid is therefore a subset of the dense call's, in the same
+    order, and the same set exactly when no solid query lies in an inactive block.  One device->host read per run (two
+    counts, 8 bytes) sizes the second pass.  The result gains 'refine' = dict(n_queries, n_decoded): host ints, summed over
+    the reruns.  (Bit for bit under the default kernel selection, whose one dependence of a row on its place in the mini-batch
+    decode_refined reproduces; under another kernels.Selection only within the mini-batch-split bound, 1e-5.)"""
     assert task == 'if'
     assert sample_implicit
     assert track_merge in ('device', 'host'), track_merge
+    grid_shape = None
+    if refine is not None:
+        if not isinstance(refine, GridRefine):
+            raise ValueError('refine must be a GridRefine or None, got %r' % (refine,))
+        if point_sample_mode != 'grid':
+            raise ValueError("refine needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
+        if neighbour_lists is not None:
+            raise ValueError('refine decodes gathered queries: neighbour_lists cannot be given with it')
+        grid_shape = geometry.grid_counts(num_sample, min_z, cube_bounds, data_kind, cube_mode)
+    refine_stats = dict(n_queries=0, n_decoded=0)
     output_track_idx = get_track_idx(color_mode)
     input_inst_idx = 0 if data_kind == 'greater' else 1
     pcl_net, implicit_net = networks
@@ -211,8 +259,11 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
             res = infer_device(pcl_input, queries_dev, pcl_net, implicit_net, batch_size, color_mode,
                                predict_segmentation, track_mode, semantic_classes,
                                encoded=_encoded_for(encoded, inst_id), neighbour_lists=neighbour_lists,
-                               squash=not device_merge)
+                               squash=not device_merge, refine=refine, grid_counts=grid_shape)
             encoded_out[inst_id] = (res['pcl_abstract'], res['features_global'])
+            if refine is not None:
+                for k in refine_stats:
+                    refine_stats[k] += res['refine'][k]
             if device_merge:                  # this rerun onto the running merge: squash, sum, winner / best in one pass
                 raw = res['implicit_output']
                 if run == 0:
@@ -279,6 +330,8 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     ops.check_pending()                      # cooperative-FPS status words (everything above has completed)
     result = dict(output_solid=solid, output_air=air, pcl_abstract=pcl_abstract,
                   features_global=features_global, implicit_output=implicit_output, points_query=points_query)
+    if refine is not None:
+        result['refine'] = refine_stats
     if return_encoded:
         result['_encoded'] = encoded_out[-1] if single_run else encoded_out
     if gt_available:
@@ -367,10 +420,12 @@ def multi_track_merge(track_instance_ids, pcl_abstract, features_global, implici
 
 def infer_device(pcl_input, points_query, pcl_net, implicit_net, batch_size, color_mode,
                  predict_segmentation=False, track_mode='none', semantic_classes=13, encoded=None,
-                 neighbour_lists=None, squash=True):
+                 neighbour_lists=None, squash=True, refine=None, grid_counts=None):
     """Device-resident core of perform_inference: encode once, decode every mini-batch, squash.
     All tensors are CUDA; returns CUDA tensors (implicit_output (N,G), pcl_abstract (M,3+E),
-    features_global (D)).  squash=False: implicit_output holds the network's RAW outputs (the caller squashes)."""
+    features_global (D)).  squash=False: implicit_output holds the network's RAW outputs (the caller squashes).
+    refine: a GridRefine for points_query = the (nx, ny, nz) = `grid_counts` grid: two decode passes and the expansion stand
+    in for the dense decode (decode_refined), and the result gains 'refine' = dict(n_queries, n_decoded)."""
     if encoded is not None:
         (pcl_abstract, features_global) = encoded
     else:
@@ -384,11 +439,116 @@ def infer_device(pcl_input, points_query, pcl_net, implicit_net, batch_size, col
     if neighbour_lists is not None:
         lists = tuple(None if a is None else torch.as_tensor(a).to(points_query.device) for a in neighbour_lists)
         assert len(lists) == 2 and all(a is None or a.shape[0] == n for a in lists)
-    decode_batches(implicit_net, points_query, 0, n, batch_size, pcl_abstract, features_global, out, lists=lists)
-    if squash:
-        ops.squash(out, squash_codes(implicit_net.d_out, color_mode, predict_segmentation, track_mode,
-                                     semantic_classes))
-    return dict(implicit_output=out, pcl_abstract=pcl_abstract, features_global=features_global)
+    codes = squash_codes(implicit_net.d_out, color_mode, predict_segmentation, track_mode, semantic_classes)
+    res = dict(implicit_output=out, pcl_abstract=pcl_abstract, features_global=features_global)
+    if refine is None:
+        decode_batches(implicit_net, points_query, 0, n, batch_size, pcl_abstract, features_global, out, lists=lists)
+    else:
+        assert lists is None and grid_counts is not None, 'refine: no neighbour_lists, and the grid counts of points_query'
+        res['refine'] = decode_refined(implicit_net, points_query, grid_counts, refine, batch_size, pcl_abstract,
+                                       features_global, out, codes[0])
+    if squash:                           # (on copied rows too: the squash of a copy is the copy of the squashed row)
+        ops.squash(out, codes)
+    return res
+
+
+# A decoded row's bits depend on ONE thing beside the query itself: its slot in the mini-batch.  The fused attention kernel packs
+# 9 consecutive queries of a mini-batch per workgroup (DECODE_ALIGN below), and the ninth of them (position % 9 == 8) takes
+# another reduction order than the first eight: the two kinds of slot differ in the last bits (4.8e-7 at most on the tracking
+# fixture), rows within a kind do not, and neither the batch's length nor a shift by a multiple of 9 changes anything.  The
+# gathered passes of the coarse-to-fine decode therefore give every query a slot of the kind it has in the dense decode.
+SLOT_PERIOD = 9
+ODD_SLOT = 8
+
+
+def _dense_slot_is_odd(grid_index, chunk):
+    """Whether the dense decode (mini-batches of `chunk` rows from row 0) puts grid row `grid_index` into a ninth slot."""
+    return (grid_index % chunk) % SLOT_PERIOD == ODD_SLOT
+
+
+def _like_slots(odd):
+    """odd (m,) bool, in batch order -> slot (m,) int64: a position of its own for every row, whose kind is the row's -- the
+    ninth slots 8, 17, 26, ... for the odd rows, the other positions 0 .. 7, 9 .. 16, ... for the rest, each kind in the rows'
+    order.  The batch that holds them has `_slots_len(rows of the other kind, odd rows)` rows; the positions no row takes are
+    padding."""
+    odd = odd.to(torch.int64)
+    odd_rank = torch.cumsum(odd, 0) - odd
+    other_rank = torch.arange(odd.shape[0], dtype=torch.int64, device=odd.device) - odd_rank
+    return torch.where(odd.bool(), odd_rank * SLOT_PERIOD + ODD_SLOT, other_rank + other_rank // (SLOT_PERIOD - 1))
+
+
+def _slots_len(n_other, n_odd):
+    last_other = (n_other - 1) + (n_other - 1) // (SLOT_PERIOD - 1) if n_other > 0 else -1
+    last_odd = (n_odd - 1) * SLOT_PERIOD + ODD_SLOT if n_odd > 0 else -1
+    return max(last_other, last_odd) + 1
+
+
+def _slot_batch(batch_size):
+    """(the dense decode's mini-batch length, the batch_size of a gathered pass: the largest one below it that keeps a row's
+    position in its mini-batch congruent to its position in the pass modulo 9)."""
+    chunk = decode_chunk(batch_size)
+    gathered = chunk - chunk % SLOT_PERIOD if chunk >= SLOT_PERIOD else chunk
+    assert decode_chunk(gathered) % SLOT_PERIOD == 0 or gathered < SLOT_PERIOD, 'OCC4D_DECODE_ALIGN must be a multiple of 9'
+    return chunk, gathered
+
+
+def _decode_in_slots(implicit_net, rows, slot, length, filler, batch_size, pcl_abstract, features_global, g):
+    """Decodes rows (m, 4) at the positions `slot` (m,) of a batch of `length` rows (the rest: copies of the query `filler`)
+    -> their (m, g) raw outputs."""
+    batch = filler.expand(length, rows.shape[1]).contiguous()
+    batch.index_copy_(0, slot, rows)
+    out = torch.empty((length, g), dtype=torch.float32, device=rows.device)
+    decode_batches(implicit_net, batch, 0, length, batch_size, pcl_abstract, features_global, out)
+    return ops.gather_rows(out, slot.to(torch.int32))
+
+
+@functools.lru_cache(maxsize=8)
+def _grid_plan(counts, block, chunk, device):
+    """What depends on the grid alone: (flat grid index of every block's representative, in flat block order, (blocks,) int32;
+    the representatives' slots (blocks,) int64 and the length of their batch; (n,) float32: 1.0 where the dense decode puts the
+    grid row into a ninth slot), on `device`."""
+    axes = []
+    for n in counts:
+        first = torch.arange((n + block - 1) // block, dtype=torch.int64) * block + block // 2
+        axes.append(torch.clamp(first, max=n - 1))
+    nx, ny, nz = counts
+    rep = ((axes[0][:, None, None] * ny + axes[1][None, :, None]) * nz + axes[2][None, None, :]).reshape(-1)
+    rep_odd = _dense_slot_is_odd(rep, chunk)
+    n_odd = int(rep_odd.sum())
+    grid_odd = _dense_slot_is_odd(torch.arange(nx * ny * nz, dtype=torch.int64), chunk).to(torch.float32)
+    return (rep.to(torch.int32).to(device), _like_slots(rep_odd).to(device), _slots_len(rep.shape[0] - n_odd, n_odd),
+            grid_odd.to(device))
+
+
+def decode_refined(implicit_net, points_query, counts, refine, batch_size, pcl_abstract, features_global, out, density_op):
+    """The coarse-to-fine decode of the (nx, ny, nz) = `counts` grid `points_query` into the dense `out` (N, G), RAW outputs:
+    the representatives' OWN rows of the grid tensor are gathered and decoded, the mark selects (on the raw density with its
+    squash code `density_op`), the order-preserving compaction gathers the selected rows, they are decoded, and one pass
+    expands.  Mini-batches are independent and every gathered query is decoded in a mini-batch slot of the kind the dense
+    decode gives it (SLOT_PERIOD above; a few padding rows fill the slots no query takes), so every decoded row has the
+    dense decode's bits.  One device->host read per call: the selected count and, with it, the count of ninth-slot rows
+    among them.  -> dict(n_queries, n_decoded): n_decoded counts the representatives and the selected rows, not the padding."""
+    counts = tuple(int(c) for c in counts)
+    n, g = out.shape
+    assert points_query.shape[0] == n == counts[0] * counts[1] * counts[2], \
+        'points_query holds %d rows, the grid %s' % (points_query.shape[0], counts)
+    chunk, gathered = _slot_batch(batch_size)
+    rep_rows, rep_slot, rep_len, grid_odd = _grid_plan(counts, refine.block, chunk, points_query.device)
+    filler = points_query[:1]
+    rep_out = _decode_in_slots(implicit_net, ops.gather_rows(points_query, rep_rows), rep_slot, rep_len, filler, gathered,
+                               pcl_abstract, features_global, g)
+    key, _ = ops.refine_mark(rep_out[:, 0], counts, refine.block, refine.dilate, refine.low, op=density_op)
+    # the selected rows with their kind of slot as a fifth column; the two counts in one read
+    tagged = torch.cat([points_query, grid_odd[:, None]], dim=1)
+    fine_rows, count, offsets = ops.compact_rows_with_offsets(tagged, key, 0.5, sync=False)
+    n_fine, n_odd = (int(v) for v in torch.stack([count[0].to(torch.int64), (key * grid_odd).sum(dtype=torch.float64).to(torch.int64)]).tolist())
+    fine_out = None
+    if n_fine > 0:
+        fine_rows = fine_rows[:n_fine]
+        fine_out = _decode_in_slots(implicit_net, fine_rows[:, :4].contiguous(), _like_slots(fine_rows[:, 4] > 0.5),
+                                    _slots_len(n_fine - n_odd, n_odd), filler, gathered, pcl_abstract, features_global, g)
+    ops.refine_expand(key, offsets, rep_out, fine_out, counts, refine.block, out=out)
+    return dict(n_queries=n, n_decoded=rep_rows.shape[0] + n_fine)
 
 
 # decode streams: kernels.Selection.decode_streams (default 2, OCC4D_DECODE_STREAMS; 1 = the reference's strictly serial loop)

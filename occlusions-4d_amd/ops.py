@@ -1114,13 +1114,15 @@ class RadiusGrid:
 
 def _compact(rows, key, threshold, strict, sync):
     """compact_rows (sync: the kept count is read and sizes the outputs) / compact_rows_nosync (all n rows allocated) ->
-    (rows, keys, count (1,) int32 on the device -- None when sync and n == 0)."""
+    (rows, keys, count (1,) int32 on the device -- None when sync and n == 0 --, the exclusive prefix of the kept rows per 256
+    rows (ceil(n / 256),) int32 on the device)."""
     r, ld = _rows(_dev(rows, name='rows'), 'rows')
     k = _dev(key, name='key')
     assert k.dim() == 1 and k.shape[0] == r.shape[0]
     n, d = r.shape
     if n == 0:
-        return r.new_empty((0, d)), k.new_empty((0,)), None if sync else torch.zeros((1,), dtype=torch.int32, device=r.device)
+        return (r.new_empty((0, d)), k.new_empty((0,)), None if sync else torch.zeros((1,), dtype=torch.int32, device=r.device),
+                torch.empty((0,), dtype=torch.int32, device=r.device))
     lk = k.stride(0) if n > 1 else 1
     nb = (n + 255) // 256
     scratch = torch.empty(nb + 1, dtype=torch.int32, device=r.device)
@@ -1132,7 +1134,7 @@ def _compact(rows, key, threshold, strict, sync):
     out_key = torch.empty((kept,), dtype=torch.float32, device=r.device)
     _lib.check(_lib.lib().occ4d_compact_rows_f32(_ptr(r), ld, n, d, _ptr(k), lk, float(threshold), int(strict),
                                                  _ptr(scratch), _ptr(out_rows), _ptr(out_key), st))
-    return out_rows, out_key, scratch[nb:nb + 1]
+    return out_rows, out_key, scratch[nb:nb + 1], scratch[:nb]
 
 
 def compact_rows(rows, key, threshold, strict=True):
@@ -1145,8 +1147,68 @@ def compact_rows_nosync(rows, key, threshold, strict=True):
     """compact_rows without the device->host read: -> (buffer (n, d) whose first `count` rows are rows[key > threshold] in
     order -- the rest is uninitialised --, count (1,) int32 ON THE DEVICE).  For callers that collect several counts and
     read them in one transfer (the point sampler: one synchronisation per stage instead of one per selection)."""
-    out_rows, _, count = _compact(rows, key, threshold, strict, False)
+    out_rows, _, count, _ = _compact(rows, key, threshold, strict, False)
     return out_rows, count
+
+
+def compact_rows_with_offsets(rows, key, threshold, strict=True, sync=True):
+    """compact_rows that also hands out what the selection was made with: -> (rows kept (n', d), n' as a host int -- the one
+    4-byte device->host read --, block_offsets (ceil(n / 256),) int32 on the device: the exclusive prefix of the kept rows per
+    256 rows, as occ4d_compact_rows_f32 takes it and refine_expand does).  sync=False: as compact_rows_nosync, no read: -> (buffer
+    (n, d) whose first n' rows are the kept ones, n' as a (1,) int32 ON THE DEVICE, block_offsets)."""
+    out_rows, _, count, offsets = _compact(rows, key, threshold, strict, sync)
+    return out_rows, (out_rows.shape[0] if sync else count), offsets
+
+
+def _refine_grid(counts, block):
+    """(nx, ny, nz, b, number of grid points, number of blocks) of a refinement (include/occ4d_refine.h)."""
+    nx, ny, nz = (int(c) for c in counts)
+    b = int(block)
+    assert b >= 1, 'block = %d' % b
+    return nx, ny, nz, b, nx * ny * nz, ((nx + b - 1) // b) * ((ny + b - 1) // b) * ((nz + b - 1) // b)
+
+
+def refine_mark(rep_density, counts, block, dilate, low, op=0):
+    """The mark of the coarse-to-fine decode (occ4d_refine_mark_f32, include/occ4d_refine.h) on the (nx, ny, nz) = `counts` grid
+    with blocks of edge `block`: rep_density (blocks,) = the density of every block's representative (a strided column view is
+    taken as it is), RAW when `op` is its squash code (0 identity, 1 sigmoid, 2 clamp).  A block is hot when
+    not (squash(density) < low), active when a block within Chebyshev distance `dilate` is hot; a grid point is selected when
+    its block is active and it is not the representative.  -> (key (n,) float32: 1.0 selected / 0.0, active (blocks,) int32)."""
+    nx, ny, nz, b, n, blocks = _refine_grid(counts, block)
+    d = _dev(rep_density, name='rep_density')
+    assert d.dim() == 1 and d.shape[0] == blocks, 'rep_density must be (%d,), got %s' % (blocks, tuple(d.shape))
+    key = torch.empty((n,), dtype=torch.float32, device=d.device)
+    active = torch.empty((blocks,), dtype=torch.int32, device=d.device)
+    _lib.check(_lib.lib().occ4d_refine_mark_f32(_ptr(d), d.stride(0) if blocks > 1 else 1, nx, ny, nz, b, int(dilate), int(op),
+                                                float(low), _ptr(active), _ptr(key), _stream()))
+    return key, active
+
+
+def refine_expand(key, block_offsets, rep_out, fine_out, counts, block, out=None):
+    """The dense (n, g) output of the coarse-to-fine decode (occ4d_refine_expand_f32): a selected row (key 1.0) takes its row
+    of fine_out (n_fine, g) -- the decoded selected queries in grid order; position = block_offsets[i // 256] + rank in its
+    256-row tile, used only inside fine_out --, every other row takes row block(i) of rep_out (blocks, g).  key and
+    block_offsets: what refine_mark and compact_rows_with_offsets(.., key, 0.5) returned.  fine_out may be None when nothing
+    was selected.  `out`: an (n, g) tensor with a contiguous last dim, written in place (columns behind g are not touched)."""
+    nx, ny, nz, b, n, blocks = _refine_grid(counts, block)
+    r, ld_rep = _merge_rows(rep_out, 'rep_out')
+    g = r.shape[1]
+    assert r.shape[0] == blocks, 'rep_out must hold %d rows, got %d' % (blocks, r.shape[0])
+    k = _merge_column(key, n, 'key')
+    offs = _dev(block_offsets, torch.int32, 'block_offsets')
+    assert tuple(offs.shape) == ((n + 255) // 256,) and offs.is_contiguous(), 'block_offsets must be (%d,)' % ((n + 255) // 256)
+    n_fine, f, ld_fine = 0, None, g
+    if fine_out is not None and fine_out.shape[0] > 0:
+        f, ld_fine = _merge_rows(fine_out, 'fine_out')
+        assert f.shape[1] == g, 'fine_out must have g = %d columns' % g
+        n_fine = f.shape[0]
+    if out is None:
+        out = torch.empty((n, g), dtype=torch.float32, device=r.device)
+    o, ld_out = _merge_rows(out, 'out')
+    assert tuple(o.shape) == (n, g), 'out must be %s, got %s' % ((n, g), tuple(o.shape))
+    _lib.check(_lib.lib().occ4d_refine_expand_f32(_ptr(k), _ptr(offs), _ptr(r), ld_rep, _ptr(f), ld_fine, n_fine, nx, ny, nz, b, g,
+                                                  _ptr(o), ld_out, _stream()))
+    return out
 
 
 def eval_layout(n_groups, n_classes):
