@@ -46,18 +46,14 @@ def _ratio(num, den):
     return np.divide(num, den, out=np.full(np.broadcast(num, den).shape, np.nan), where=den != 0)
 
 
-class EvalStats:
-    """Additive evaluation statistics of decoded frames against their ground-truth frames (include/occ4d_eval.h): two device
-    arrays, `counts` (int64) and `sums` (float64), that `add_frame` accumulates onto with no host read of their contents,
-    that sum across frames, clips and ranks (`merge`, `+=`, `all_reduce`) and that `summary()` turns into the usual figures
-    with ONE host read.  Every statistic is kept per group (n_groups <= 8: the caller's partition of the target points,
-    e.g. visible / occluded); semantic_classes (<= 32) sizes the segmentation confusion matrix, 0 = none.
-    In track_mode 'all' the TRACK_* counts compare a winner id with 0.5 and mean nothing: InstanceStats is the scorer for that
-    mode."""
+class _AdditiveStats:
+    """What EvalStats and InstanceStats share: two device accumulators, `counts` (int64) and `sums` (float64), that sum across
+    frames, clips and ranks, their numpy state, their one-transfer read and the inputs of an `add_frame`.  A subclass names its
+    constructor arguments in order (_FIELDS: the state's keys) and those that size the two arrays (_LAYOUT_FIELDS: objects of
+    one class that agree on these add)."""
+    _FIELDS = _LAYOUT_FIELDS = ()
 
-    def __init__(self, n_groups=1, semantic_classes=0, device=None):
-        self.n_groups, self.semantic_classes = int(n_groups), int(semantic_classes)
-        n_counts, n_sums = ops.eval_layout(self.n_groups, self.semantic_classes)
+    def _allocate(self, device, n_counts, n_sums):
         self.device = torch.device('cpu' if _lib.is_twin() else 'cuda') if device is None else torch.device(device)
         self.counts = torch.zeros((n_counts,), dtype=torch.int64, device=self.device)
         self.sums = torch.zeros((n_sums,), dtype=torch.float64, device=self.device)
@@ -67,50 +63,34 @@ class EvalStats:
             a = torch.from_numpy(np.ascontiguousarray(a))
         return a.to(device=self.device, dtype=dtype)
 
-    def add_frame(self, points_query, implicit_output, target_rows, *, density_threshold, point_occupancy_radius, color_mode,
-                  predict_segmentation, track_mode, data_kind, target_group=None, nn=None, solid=None, col_rgb=None,
-                  col_track=None, col_sem=None):
-        """Adds one output frame: points_query (N, 3 or 4), implicit_output (N, G) (squashed, as perform_inference returns it),
-        target_rows (M, Dt) (device tensors or numpy, uploaded once).  target_group: (M,) integer group id per target point.
-        nn = (idx (N,), dist (N,)): the query -> target 1-NN if the caller has it; solid: the predicted-solid rows
-        (xyz first) if the caller has split them.  The target columns default from data_kind (TARGET_COLUMNS).  Colour is
-        scored for color_mode 'rgb' / 'rgb_nosigmoid', tracking for track_mode != 'none', segmentation for
-        predict_segmentation with semantic_classes > 0 and a semantic column."""
+    def _frame_inputs(self, points_query, implicit_output, target_rows):
+        """The three arrays of an add_frame on the device, checked: q (N, 3 or 4), out (N, G), tgt (M, Dt)."""
         q, out, tgt = self._tensor(points_query), self._tensor(implicit_output), self._tensor(target_rows)
         assert q.dim() == 2 and q.shape[1] in (3, 4) and out.dim() == 2 and out.shape[0] == q.shape[0], 'points_query (N, 3 or 4), implicit_output (N, G)'
         assert tgt.dim() == 2 and tgt.shape[0] >= 1 and tgt.shape[1] >= 3, 'target_rows must be (M >= 1, Dt >= 3)'
-        cols = dict(TARGET_COLUMNS.get(data_kind, dict(col_rgb=-1, col_track=-1, col_sem=-1)))
-        cols.update({k: int(v) for k, v in dict(col_rgb=col_rgb, col_track=col_track, col_sem=col_sem).items() if v is not None})
-        flags = 0
-        if color_mode in ('rgb', 'rgb_nosigmoid'):
-            flags |= _EC['FLAG_COLOR']
-        if track_mode != 'none':
-            flags |= _EC['FLAG_TRACK']
-        if predict_segmentation and self.semantic_classes > 0:
-            flags |= _EC['FLAG_SEG']
-        grp = None if target_group is None else self._tensor(np.asarray(target_group) if not torch.is_tensor(target_group)
-                                                            else target_group, torch.int32).contiguous()
-        kw = dict(n_groups=self.n_groups, n_classes=self.semantic_classes, target_group=grp)
+        return q, out, tgt
+
+    def _frame_search(self, q, tgt, nn, group):
+        """(idx (N,) int32, dist (N,), grp) on the device: the query -> target 1-NN (searched unless the caller has it as `nn`)
+        and the group ids, or None when there is no query: nothing to add, and nothing is searched."""
+        grp = None if group is None else self._tensor(np.asarray(group) if not torch.is_tensor(group) else group,
+                                                      torch.int32).contiguous()
         if q.shape[0] == 0:
-            return self
+            return None
         if nn is None:
             idx, dist = ops.knn(q[:, :3], tgt[:, :3], 1, metric=1, return_dist=True)
             nn = (idx[:, 0], dist[:, 0])
-        idx, dist = self._tensor(nn[0], torch.int32), self._tensor(nn[1])
-        if solid is None:
-            q4 = q if q.shape[1] == 4 else torch.nn.functional.pad(q, (0, 1))
-            solid = ops.split_solid_air(q4.contiguous(), out, density_threshold)[0]
-        solid = self._tensor(solid)
-        if solid.shape[0] > 0:               # completeness: every target point to its nearest predicted-solid query
-            _, back = ops.knn(tgt[:, :3], solid[:, :3], 1, metric=1, return_dist=True)
-            ops.eval_target_stats(back[:, 0], self.counts, self.sums, **kw)
-        ops.eval_query_stats(out, idx, dist, tgt, self.counts, self.sums, density_threshold=density_threshold,
-                             radius=point_occupancy_radius, flags=flags, out_track=inference.get_track_idx(color_mode), **cols, **kw)
-        return self
+        return self._tensor(nn[0], torch.int32), self._tensor(nn[1]), grp
+
+    @staticmethod
+    def _split_solid(q, values, density_threshold):
+        """The predicted-solid rows (xyz, t, then `values`' columns) when the caller has not split them."""
+        q4 = q if q.shape[1] == 4 else torch.nn.functional.pad(q, (0, 1))
+        return ops.split_solid_air(q4.contiguous(), values, density_threshold)[0]
 
     def _same_layout(self, other):
-        assert isinstance(other, EvalStats) and (other.n_groups, other.semantic_classes) == (self.n_groups, self.semantic_classes), \
-            'EvalStats of different (n_groups, semantic_classes) do not add'
+        assert type(other) is type(self) and all(getattr(other, f) == getattr(self, f) for f in self._LAYOUT_FIELDS), \
+            '%s of different %s do not add' % (type(self).__name__, ' / '.join(self._LAYOUT_FIELDS))
 
     def merge(self, other):
         self._same_layout(other)
@@ -129,16 +109,69 @@ class EvalStats:
 
     def state(self):
         """The object as numpy (copies: a later add does not change them); from_state() is the way back."""
-        return dict(n_groups=self.n_groups, semantic_classes=self.semantic_classes, counts=self.counts.cpu().numpy().copy(),
+        return dict({f: getattr(self, f) for f in self._FIELDS}, counts=self.counts.cpu().numpy().copy(),
                     sums=self.sums.cpu().numpy().copy())
 
     @classmethod
     def from_state(cls, state, device=None):
-        self = cls(int(state['n_groups']), int(state['semantic_classes']), device)
+        self = cls(*(int(state[f]) for f in cls._FIELDS), device)
         counts, sums = np.asarray(state['counts'], np.int64), np.asarray(state['sums'], np.float64)
         assert counts.shape == tuple(self.counts.shape) and sums.shape == tuple(self.sums.shape)
         self.counts.copy_(torch.from_numpy(counts))
         self.sums.copy_(torch.from_numpy(sums))
+        return self
+
+    def _read(self):
+        """(counts, sums) as numpy from ONE transfer (the int64 words travel reinterpreted as float64 bits)."""
+        both = torch.cat([self.counts.view(torch.float64), self.sums]).cpu()
+        return both[:self.counts.numel()].view(torch.int64).numpy(), both[self.counts.numel():].numpy()
+
+
+class EvalStats(_AdditiveStats):
+    """Additive evaluation statistics of decoded frames against their ground-truth frames (include/occ4d_eval.h): two device
+    arrays, `counts` (int64) and `sums` (float64), that `add_frame` accumulates onto with no host read of their contents,
+    that sum across frames, clips and ranks (`merge`, `+=`, `all_reduce`) and that `summary()` turns into the usual figures
+    with ONE host read.  Every statistic is kept per group (n_groups <= 8: the caller's partition of the target points,
+    e.g. visible / occluded); semantic_classes (<= 32) sizes the segmentation confusion matrix, 0 = none.
+    In track_mode 'all' the TRACK_* counts compare a winner id with 0.5 and mean nothing: InstanceStats is the scorer for that
+    mode."""
+
+    _FIELDS = _LAYOUT_FIELDS = ('n_groups', 'semantic_classes')
+
+    def __init__(self, n_groups=1, semantic_classes=0, device=None):
+        self.n_groups, self.semantic_classes = int(n_groups), int(semantic_classes)
+        self._allocate(device, *ops.eval_layout(self.n_groups, self.semantic_classes))
+
+    def add_frame(self, points_query, implicit_output, target_rows, *, density_threshold, point_occupancy_radius, color_mode,
+                  predict_segmentation, track_mode, data_kind, target_group=None, nn=None, solid=None, col_rgb=None,
+                  col_track=None, col_sem=None):
+        """Adds one output frame: points_query (N, 3 or 4), implicit_output (N, G) (squashed, as perform_inference returns it),
+        target_rows (M, Dt) (device tensors or numpy, uploaded once).  target_group: (M,) integer group id per target point.
+        nn = (idx (N,), dist (N,)): the query -> target 1-NN if the caller has it; solid: the predicted-solid rows
+        (xyz first) if the caller has split them.  The target columns default from data_kind (TARGET_COLUMNS).  Colour is
+        scored for color_mode 'rgb' / 'rgb_nosigmoid', tracking for track_mode != 'none', segmentation for
+        predict_segmentation with semantic_classes > 0 and a semantic column."""
+        q, out, tgt = self._frame_inputs(points_query, implicit_output, target_rows)
+        cols = dict(TARGET_COLUMNS.get(data_kind, dict(col_rgb=-1, col_track=-1, col_sem=-1)))
+        cols.update({k: int(v) for k, v in dict(col_rgb=col_rgb, col_track=col_track, col_sem=col_sem).items() if v is not None})
+        flags = 0
+        if color_mode in ('rgb', 'rgb_nosigmoid'):
+            flags |= _EC['FLAG_COLOR']
+        if track_mode != 'none':
+            flags |= _EC['FLAG_TRACK']
+        if predict_segmentation and self.semantic_classes > 0:
+            flags |= _EC['FLAG_SEG']
+        found = self._frame_search(q, tgt, nn, target_group)
+        if found is None:
+            return self
+        idx, dist, grp = found
+        kw = dict(n_groups=self.n_groups, n_classes=self.semantic_classes, target_group=grp)
+        solid = self._tensor(self._split_solid(q, out, density_threshold) if solid is None else solid)
+        if solid.shape[0] > 0:               # completeness: every target point to its nearest predicted-solid query
+            _, back = ops.knn(tgt[:, :3], solid[:, :3], 1, metric=1, return_dist=True)
+            ops.eval_target_stats(back[:, 0], self.counts, self.sums, **kw)
+        ops.eval_query_stats(out, idx, dist, tgt, self.counts, self.sums, density_threshold=density_threshold,
+                             radius=point_occupancy_radius, flags=flags, out_track=inference.get_track_idx(color_mode), **cols, **kw)
         return self
 
     def summary(self):
@@ -150,8 +183,7 @@ class EvalStats:
         'counts': the raw counts by name ((n_groups,) int64 each), 'confusion' (n_groups, C, C), 'bad_rows'.  Raises
         ValueError when rows were skipped (bad_rows > 0)."""
         G, C, K = self.n_groups, self.semantic_classes, _EC['GROUP_COUNTS']
-        both = torch.cat([self.counts.view(torch.float64), self.sums]).cpu()           # (bit reinterpretation: ONE transfer)
-        counts, sums = both[:self.counts.numel()].view(torch.int64).numpy(), both[self.counts.numel():].numpy()
+        counts, sums = self._read()
         bad = int(counts[_EC['BAD_ROWS']])
         if bad > 0:
             raise ValueError('EvalStats: %d rows were skipped (nn_idx outside the target, or a group id outside [0, %d))' % (bad, G))
@@ -178,7 +210,7 @@ class EvalStats:
         return res
 
 
-class InstanceStats:
+class InstanceStats(_AdditiveStats):
     """Additive instance-level statistics of a dense instance labelling (perform_inference with track_mode 'all': the merged
     mark_track channel holds the id of the most confident rerun, or -1) against ground-truth frames (include/occ4d_inst.h): per
     frame a device table -- the (n_ids + 1)^2 confusion of ALL queries, class n_ids = none, and per id the count and the
@@ -187,17 +219,15 @@ class InstanceStats:
     `all_reduce`); `summary()` turns them into instance IoU, panoptic quality and the centroid error with ONE host read, and
     `frame_tables()` reads the latest frame's table: where every tracked object is.  Every figure is kept per group
     (n_groups <= 8: the caller's partition of the ids, e.g. `occlusion_groups`); n_ids <= 64.  A sibling of EvalStats, whose
-    TRACK_* counts mean nothing for a winner id."""
+    TRACK_* counts mean nothing for a winner id.  The frame table is not part of `state()`; the lengths of `counts` and `sums`
+    depend on n_groups alone (ops.inst_layout), so objects of different n_ids add."""
+    _FIELDS, _LAYOUT_FIELDS = ('n_ids', 'n_groups'), ('n_groups',)
 
     def __init__(self, n_ids, n_groups=1, device=None):
         self.n_ids, self.n_groups = int(n_ids), int(n_groups)
         n_frame, n_counts, n_sums = ops.inst_layout(self.n_ids, self.n_groups)
-        self.device = torch.device('cpu' if _lib.is_twin() else 'cuda') if device is None else torch.device(device)
+        self._allocate(device, n_counts, n_sums)
         self.frame = torch.zeros((n_frame,), dtype=torch.int64, device=self.device)
-        self.counts = torch.zeros((n_counts,), dtype=torch.int64, device=self.device)
-        self.sums = torch.zeros((n_sums,), dtype=torch.float64, device=self.device)
-
-    _tensor = EvalStats._tensor
 
     def add_frame(self, points_query, implicit_output, target_rows, *, density_threshold, point_occupancy_radius, color_mode,
                   data_kind, inst_group=None, nn=None, solid=None, col_inst=None, pred_id=None):
@@ -208,9 +238,7 @@ class InstanceStats:
         defaults from data_kind (INSTANCE_COLUMNS).  pred_id (N,): another labelling of the queries to score instead of the
         mark_track channel.  The frame table is zero-filled, filled by the confusion pass and the two point passes and folded;
         no host read."""
-        q, out, tgt = self._tensor(points_query), self._tensor(implicit_output), self._tensor(target_rows)
-        assert q.dim() == 2 and q.shape[1] in (3, 4) and out.dim() == 2 and out.shape[0] == q.shape[0], 'points_query (N, 3 or 4), implicit_output (N, G)'
-        assert tgt.dim() == 2 and tgt.shape[0] >= 1 and tgt.shape[1] >= 3, 'target_rows must be (M >= 1, Dt >= 3)'
+        q, out, tgt = self._frame_inputs(points_query, implicit_output, target_rows)
         col = INSTANCE_COLUMNS.get(data_kind) if col_inst is None else int(col_inst)
         assert col is not None and 0 <= col < tgt.shape[1], 'no instance column: data_kind = %r, col_inst = %r, Dt = %d' % (data_kind, col_inst, tgt.shape[1])
         track = inference.get_track_idx(color_mode)
@@ -219,24 +247,15 @@ class InstanceStats:
         else:
             pred_id = self._tensor(pred_id)
             assert pred_id.shape == (q.shape[0],), 'pred_id must be (N,)'
-        grp = None if inst_group is None else self._tensor(np.asarray(inst_group) if not torch.is_tensor(inst_group) else inst_group,
-                                                          torch.int32).contiguous()
-        if q.shape[0] == 0:
+        found = self._frame_search(q, tgt, nn, inst_group)
+        if found is None:
             return self
-        if nn is None:
-            idx, dist = ops.knn(q[:, :3], tgt[:, :3], 1, metric=1, return_dist=True)
-            nn = (idx[:, 0], dist[:, 0])
-        idx, dist = self._tensor(nn[0], torch.int32), self._tensor(nn[1])
+        idx, dist, grp = found
         if pred_id is not None:               # the solid rows carry the track channel, not this labelling: split it alongside
-            q4 = q if q.shape[1] == 4 else torch.nn.functional.pad(q, (0, 1))
-            both = torch.cat([out[:, :1], pred_id[:, None]], dim=1)
-            solid = ops.split_solid_air(q4.contiguous(), both, density_threshold)[0]
+            solid = self._split_solid(q, torch.cat([out[:, :1], pred_id[:, None]], dim=1), density_threshold)
             solid_ids, pred_col = solid[:, 5], pred_id
         else:
-            if solid is None:
-                q4 = q if q.shape[1] == 4 else torch.nn.functional.pad(q, (0, 1))
-                solid = ops.split_solid_air(q4.contiguous(), out, density_threshold)[0]
-            solid = self._tensor(solid)
+            solid = self._tensor(self._split_solid(q, out, density_threshold) if solid is None else solid)
             solid_ids, pred_col = solid[:, 4 + track], out[:, track]
         self.frame.zero_()
         ops.inst_confusion(out[:, 0], pred_col, idx, dist, tgt[:, col], self.frame, n_ids=self.n_ids,
@@ -244,38 +263,6 @@ class InstanceStats:
         ops.inst_points(solid, solid_ids, self.frame, n_ids=self.n_ids, side=_IC['SIDE_PRED'])
         ops.inst_points(tgt, tgt[:, col], self.frame, n_ids=self.n_ids, side=_IC['SIDE_GT'])
         ops.inst_fold(self.frame, self.counts, self.sums, n_ids=self.n_ids, n_groups=self.n_groups, inst_group=grp)
-        return self
-
-    def _same_layout(self, other):
-        assert isinstance(other, InstanceStats) and other.n_groups == self.n_groups, 'InstanceStats of different n_groups do not add'
-
-    def merge(self, other):
-        self._same_layout(other)
-        self.counts += other.counts.to(self.device)
-        self.sums += other.sums.to(self.device)
-        return self
-
-    __iadd__ = merge
-
-    def all_reduce(self, group=None):
-        """torch.distributed SUM over both arrays (the same layout on every rank)."""
-        import torch.distributed as dist
-        dist.all_reduce(self.counts, op=dist.ReduceOp.SUM, group=group)
-        dist.all_reduce(self.sums, op=dist.ReduceOp.SUM, group=group)
-        return self
-
-    def state(self):
-        """The accumulators as numpy (copies: a later add does not change them); from_state() is the way back.  The frame
-        table is not part of the state."""
-        return dict(n_ids=self.n_ids, n_groups=self.n_groups, counts=self.counts.cpu().numpy().copy(), sums=self.sums.cpu().numpy().copy())
-
-    @classmethod
-    def from_state(cls, state, device=None):
-        self = cls(int(state['n_ids']), int(state['n_groups']), device)
-        counts, sums = np.asarray(state['counts'], np.int64), np.asarray(state['sums'], np.float64)
-        assert counts.shape == tuple(self.counts.shape) and sums.shape == tuple(self.sums.shape)
-        self.counts.copy_(torch.from_numpy(counts))
-        self.sums.copy_(torch.from_numpy(sums))
         return self
 
     def frame_tables(self):
@@ -302,8 +289,7 @@ class InstanceStats:
         solid queries and that of its target points).  'counts': the raw counts by name ((n_groups,) int64 each), 'bad_rows'.
         Raises ValueError when rows or ids were skipped (bad_rows > 0)."""
         G = self.n_groups
-        both = torch.cat([self.counts.view(torch.float64), self.sums]).cpu()           # (bit reinterpretation: ONE transfer)
-        counts, sums = both[:self.counts.numel()].view(torch.int64).numpy(), both[self.counts.numel():].numpy()
+        counts, sums = self._read()
         bad = int(counts[_IC['BAD_ROWS']])
         if bad > 0:
             raise ValueError('InstanceStats: %d rows or ids were skipped (nn_idx outside the target, an id that is no integer in '

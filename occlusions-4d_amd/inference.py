@@ -180,35 +180,39 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                       density_threshold=0.5, data_kind='', cube_mode=4, compress_air=False,
                       encoded=None, return_encoded=False, neighbour_lists=None, stats=None, stats_target=None,
                       stats_group=None, track_merge='device', inst_stats=None, inst_group=None, refine=None):
-    """One encode of the input point-cloud video + decode of all query points of one output
-    frame.  Returns dict(output_solid, output_air, pcl_abstract, features_global,
-    implicit_output, points_query) of float32 numpy arrays.
-    Extensions (keyword only, default = the reference's behaviour): `encoded` = the (pcl_abstract, features_global)
-    device tensors of an earlier call on the same input cloud (the reference's eval loop re-encodes the clip for every
-    output frame, eval/test.py:67-86); `return_encoded` adds them to the result as '_encoded'; `neighbour_lists` =
-    (knn_local (N_q, 8), knn_cross (N_q, 14)) integer arrays: the decoder's neighbour lists of a particular run of the
-    reference for these queries (LocalPclResnetFC.forward's extension; either entry may be None); `stats` = an
-    evaluation.EvalStats this frame is added to, scored on the device against `pcl_target_frame` (or `stats_target` when that
-    is not passed: no gt_solid / gt_air then) with `stats_group` = the group id per target point; the query -> target search
-    and the solid split are shared with the gt branch and the result dict is what it is without `stats`; `inst_stats` = an
-    evaluation.InstanceStats this frame is added to in the same way (the scorer of track_mode 'all': the merged mark_track
-    channel as an instance labelling) with `inst_group` = the group id per instance id; it shares the upload of the target
-    rows, the search and the split with `stats`, and changes neither the result dict nor the one host wait.
-    In track_mode 'all', `encoded` / '_encoded' are dicts {instance id: (pcl_abstract, features_global)}, one entry per rerun.
-    `track_merge`: where the reruns of track_mode 'all' are merged.  'device': a running merge in the library
-    (ops.track_merge_add / track_merge_finish: the squash, the sums and the winner / best update in one pass per rerun), the
-    merged tensor stays on the device for the split and the scoring, and the host blocks once, at the end.  'host': every
-    rerun is copied to the host, multi_track_merge runs in numpy and the merged array is uploaded again.  Same bits.
-    `refine`: a GridRefine, or None = every query is decoded.  point_sample_mode 'grid' only, and not with `neighbour_lists`
-    (ValueError).  Every run decodes one representative per block and then the other points of the active blocks; the
-    dense (N, G) output is rebuilt on the device, so the split, compress_air, `stats`, `inst_stats`, the track merge and the
-    result dict work on it as on a dense decode.  THE CONTRACT, and nothing stronger: every decoded row equals the dense
-    call's row bit for bit; every row that was not decoded is a copy of its block's representative row, whose density is
-    below `low`.  With refine.low <= density_threshold, output_solid is therefore a subset of the dense call's, in the same
-    order, and the same set exactly when no solid query lies in an inactive block.  One device->host read per run (two
-    counts, 8 bytes) sizes the second pass.  The result gains 'refine' = dict(n_queries, n_decoded): host ints, summed over
-    the reruns.  (Bit for bit under the default kernel selection, whose one dependence of a row on its place in the mini-batch
-    decode_refined reproduces; under another kernels.Selection only within the mini-batch-split bound, 1e-5.)"""
+    """One encode of the input point-cloud video + decode of all query points of one output frame.  Returns
+    dict(output_solid, output_air, pcl_abstract, features_global, implicit_output, points_query) of float32 numpy arrays, and
+    gt_solid / gt_air when `pcl_target_frame` is given.  The keywords from `encoded` on are extensions whose defaults give the
+    reference's behaviour.  The host blocks once, at the end; the scorers and `refine` add no wait.
+
+    Encode reuse.  `encoded` = the (pcl_abstract, features_global) device tensors of an earlier call on the same input cloud
+    (the reference re-encodes the clip for every output frame, eval/test.py:67-86); `return_encoded` adds them to the result as
+    '_encoded'.  In track_mode 'all' both are dicts {instance id: (pcl_abstract, features_global)}, one entry per rerun.
+
+    Neighbour lists.  `neighbour_lists` = (knn_local (N_q, 8), knn_cross (N_q, 14)) integer arrays, either may be None: the
+    decoder's neighbour lists of a particular run of the reference for these queries (LocalPclResnetFC.forward's extension).
+
+    Scoring.  `stats` = an evaluation.EvalStats this frame is added to, scored on the device against `pcl_target_frame` (or
+    `stats_target` when that is None: no gt_solid / gt_air then), `stats_group` = the group id per target point.  `inst_stats`
+    = an evaluation.InstanceStats added to in the same way (the scorer of track_mode 'all': the merged mark_track channel as an
+    instance labelling), `inst_group` = the group id per instance id.  The scorers and the gt branch share one upload of the
+    target rows, one query -> target search and the solid split; they change neither the result dict nor the one host wait.
+
+    Track merge.  `track_merge`: where the reruns of track_mode 'all' are merged.  'device': a running merge in the library
+    (ops.track_merge_add / track_merge_finish: squash, sums and the winner / best update in one pass per rerun); the merged
+    tensor stays on the device for the split and the scoring.  'host': every rerun is copied to the host (a second host wait),
+    multi_track_merge runs in numpy and the merged array is uploaded again.  Same bits.
+
+    Refine.  `refine`: a GridRefine (its two passes per run are described there), or None = every query is decoded.
+    point_sample_mode 'grid' only, and not with `neighbour_lists` (ValueError).  The dense (N, G) output is rebuilt on the
+    device: the split, compress_air, the scorers, the track merge and the result dict work on it as on a dense decode.  THE
+    CONTRACT, and nothing stronger: every decoded row equals the dense call's row bit for bit; every other row is a copy of
+    its block's representative row, whose density is below `low`.  With refine.low <= density_threshold, output_solid is
+    therefore a subset of the dense call's, in the same order, and the same set exactly when no solid query lies in an
+    inactive block.  One device->host read per run (two counts, 8 bytes) sizes the second pass.  The result gains 'refine' =
+    dict(n_queries, n_decoded): host ints, summed over the reruns.  (Bit for bit under the default kernel selection, whose one
+    dependence of a row on its place in the mini-batch decode_refined reproduces; under another kernels.Selection only within
+    the mini-batch-split bound, 1e-5.)"""
     assert task == 'if'
     assert sample_implicit
     assert track_merge in ('device', 'host'), track_merge
@@ -247,62 +251,33 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     queries_dev = geometry.sample_implicit_points_blind_device(
         num_sample, min_z, cube_bounds, time_idx, data_kind, cube_mode, point_sample_mode, device)
     copies = _HostCopies(device)
-    single_run = len(track_instance_ids) == 1 and track_instance_ids[0] == -1
-    device_merge = track_merge == 'device' and not single_run and len(track_instance_ids) > 0
+    # (an empty id list goes to the host merge and fails inside multi_track_merge)
+    kind = _SingleRun if track_instance_ids == [-1] else _DeviceMerge if track_merge == 'device' and track_instance_ids else _HostMerge
+    collector = kind(copies, track_instance_ids, output_track_idx, (color_mode, predict_segmentation, track_mode, semantic_classes))
     points_query = copies.fetch(queries_dev)              # (under the encode / decode that follows)
-    all_abstract, all_global, all_output = [], [], []
     encoded_out = {}
     with torch.no_grad():
-        for run, inst_id in enumerate(track_instance_ids):
+        for inst_id in track_instance_ids:
             if inst_id >= 0:                  # mark the instance to follow in the input cloud (:190-193)
                 pcl_input[..., -1] = (pcl_input_sem[..., input_inst_idx] == inst_id)
             res = infer_device(pcl_input, queries_dev, pcl_net, implicit_net, batch_size, color_mode,
                                predict_segmentation, track_mode, semantic_classes,
                                encoded=_encoded_for(encoded, inst_id), neighbour_lists=neighbour_lists,
-                               squash=not device_merge, refine=refine, grid_counts=grid_shape)
+                               squash=collector.squash, refine=refine, grid_counts=grid_shape)
             encoded_out[inst_id] = (res['pcl_abstract'], res['features_global'])
             if refine is not None:
                 for k in refine_stats:
                     refine_stats[k] += res['refine'][k]
-            if device_merge:                  # this rerun onto the running merge: squash, sum, winner / best in one pass
-                raw = res['implicit_output']
-                if run == 0:
-                    merged = _RunningMerge(raw, res['pcl_abstract'], res['features_global'])
-                merged.add(raw, res['pcl_abstract'], res['features_global'], inst_id, output_track_idx,
-                           squash_codes(raw.shape[1], color_mode, predict_segmentation, track_mode, semantic_classes))
-                continue
-            output_dev = res['implicit_output']
-            all_output.append(copies.fetch(output_dev))
-            all_abstract.append(copies.fetch(res['pcl_abstract']))
-            all_global.append(copies.fetch(res['features_global']))
-        if device_merge:
-            output_dev = merged.finish(output_track_idx)
-            merged_h = (copies.fetch(merged.abstract), copies.fetch(merged.features), copies.fetch(output_dev))
-        elif not single_run:                  # the merge of the per-instance reruns is host arithmetic
-            copies.wait()
-            (pcl_abstract, features_global, implicit_output) = multi_track_merge(
-                track_instance_ids, [copies.result(h) for h in all_abstract], [copies.result(h) for h in all_global],
-                [copies.result(h) for h in all_output], output_track_idx)
+            collector.add(res, inst_id)
+        output_dev = collector.finish()            # (N, G), squashed and merged
 
         gt_available = pcl_target_frame is not None
-        nn_dev = target_dev = None
-        if stats is not None or inst_stats is not None:       # one upload of the target rows, one search for all consumers
-            stats_rows = pcl_target_frame if gt_available else stats_target
-            assert stats_rows is not None, 'stats / inst_stats need a target frame: pcl_target_frame or stats_target'
-            target_dev = torch.as_tensor(np.ascontiguousarray(stats_rows, dtype=np.float32) if isinstance(stats_rows, np.ndarray)
-                                         else stats_rows).to(device=device, dtype=torch.float32)
-            nn_dev = nn_target(queries_dev[:, :3], target_dev[:, :3])
+        target_dev, nn_dev, labels = _target_frame(queries_dev[:, :3], pcl_target_frame, point_occupancy_radius, device,
+                                                  stats_target, scored=stats is not None or inst_stats is not None)
         if gt_available:                      # nearest ground-truth point of every query (:270-276)
-            if nn_dev is not None:
-                target_labels, nn_indices = nn_labels(nn_dev[0], nn_dev[1], point_occupancy_radius)
-            else:
-                target_labels, nn_indices = get_1nn_label(queries_dev[:, :3], pcl_target_frame, point_occupancy_radius,
-                                                          device)
-            points_nngt = np.concatenate([target_labels[:, None], pcl_target_frame[nn_indices]], axis=-1)
+            points_nngt = np.concatenate([labels[0][:, None], pcl_target_frame[labels[1]]], axis=-1)
 
         # density-threshold split + compress_air on the device (:279-305): order-preserving compaction
-        if not single_run and not device_merge:       # merged on the host; one upload
-            output_dev = torch.from_numpy(implicit_output).to(device)
         solid, air = ops.split_solid_air(queries_dev, output_dev, density_threshold, compress_air, semantic_classes)
         if stats is not None:
             assert not predict_segmentation or stats.semantic_classes in (0, semantic_classes), \
@@ -322,18 +297,14 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         copies.wait()
         solid, air = copies.result(solid_h), copies.result(air_h)
         points_query = copies.result(points_query)
-        if single_run:
-            (pcl_abstract, features_global, implicit_output) = (copies.result(all_abstract[0]),
-                                                                 copies.result(all_global[0]), copies.result(all_output[0]))
-        elif device_merge:
-            (pcl_abstract, features_global, implicit_output) = (copies.result(h) for h in merged_h)
+        (pcl_abstract, features_global, implicit_output) = collector.host()
     ops.check_pending()                      # cooperative-FPS status words (everything above has completed)
     result = dict(output_solid=solid, output_air=air, pcl_abstract=pcl_abstract,
                   features_global=features_global, implicit_output=implicit_output, points_query=points_query)
     if refine is not None:
         result['refine'] = refine_stats
     if return_encoded:
-        result['_encoded'] = encoded_out[-1] if single_run else encoded_out
+        result['_encoded'] = encoded_out[-1] if -1 in encoded_out else encoded_out     # (a tuple for the one unmarked run)
     if gt_available:
         solid_mask = implicit_output[..., 0] >= density_threshold
         gt_solid, gt_air = points_nngt[solid_mask], points_nngt[~solid_mask]
@@ -350,35 +321,97 @@ def _encoded_for(encoded, inst_id):
     return encoded.get(inst_id) if isinstance(encoded, dict) else None
 
 
-class _RunningMerge:
-    """multi_track_merge as a running merge on the device: one accumulator each for the implicit output (with the winner
-    / best columns of its track channel), the abstract cloud and the global feature.  The latter two go through the same
-    entry point as flat contiguous (n, 1) views without squash or track column; an abstract cloud of None stays None."""
+class _Runs:
+    """The decode runs of one perform_inference call on their way to one result; three collectors fill this in.  `squash`: whether
+    infer_device squashes a run's output; add(res, inst_id) per run; finish() -> the squashed and merged (N, G) device tensor;
+    host(), after the call's last copies.wait() -> the numpy (pcl_abstract, features_global, implicit_output)."""
+    squash = True
 
-    def __init__(self, raw, pcl_abstract, features_global):
-        n = raw.shape[0]
-        self.output = torch.empty((n, raw.shape[1]), dtype=torch.float32, device=raw.device)
-        self.best = torch.empty((n,), dtype=torch.float32, device=raw.device)
-        self.winner = torch.empty((n,), dtype=torch.float32, device=raw.device)
-        self.abstract = None if pcl_abstract is None else torch.empty(pcl_abstract.shape, dtype=torch.float32,
-                                                                      device=pcl_abstract.device)
-        self.features = torch.empty(features_global.shape, dtype=torch.float32, device=features_global.device)
-        self.runs = 0
+    def __init__(self, copies, track_instance_ids, track_col, post_ops):
+        self.copies, self.ids, self.track_col, self.post_ops = copies, track_instance_ids, track_col, post_ops
 
-    def add(self, raw, pcl_abstract, features_global, inst_id, track_col, codes):
+    def host(self):
+        return tuple(self.copies.result(h) for h in self.handles)
+
+
+class _SingleRun(_Runs):
+    """The one unmarked run (track_mode 'none' / 'one'): its tensors are the result."""
+
+    def add(self, res, inst_id):
+        self.output = res['implicit_output']
+        output_h = self.copies.fetch(self.output)
+        self.handles = (self.copies.fetch(res['pcl_abstract']), self.copies.fetch(res['features_global']), output_h)
+
+    def finish(self):
+        return self.output
+
+
+class _DeviceMerge(_Runs):
+    """multi_track_merge as a running merge on the device: one accumulator each for the RAW implicit output (squashed by the
+    add, with the winner / best columns of its track channel), the abstract cloud and the global feature.  The latter two go
+    through the same entry point as flat contiguous (n, 1) views without squash or track column; an abstract of None stays None."""
+    squash = False
+    runs = 0
+
+    def add(self, res, inst_id):
+        raw, pcl_abstract, features_global = res['implicit_output'], res['pcl_abstract'], res['features_global']
         first = self.runs == 0
-        ops.track_merge_add(raw, self.output, self.best, self.winner, inst_id, track_col, codes, first=first)
+        if first:
+            new = lambda like, shape: torch.empty(shape, dtype=torch.float32, device=like.device)
+            self.output, self.best, self.winner = new(raw, tuple(raw.shape)), new(raw, raw.shape[:1]), new(raw, raw.shape[:1])
+            self.abstract = None if pcl_abstract is None else new(pcl_abstract, pcl_abstract.shape)
+            self.features = new(features_global, features_global.shape)
+            self.codes = squash_codes(raw.shape[1], *self.post_ops)
+        ops.track_merge_add(raw, self.output, self.best, self.winner, inst_id, self.track_col, self.codes, first=first)
         for part, acc in ((pcl_abstract, self.abstract), (features_global, self.features)):
             if acc is not None:
                 ops.track_merge_add(part.contiguous().view(-1, 1), acc.view(-1, 1), None, None, inst_id, -1, None, first=first)
         self.runs += 1
 
-    def finish(self, track_col):
-        ops.track_merge_finish(self.output, self.winner, self.runs, track_col)
+    def finish(self):
+        ops.track_merge_finish(self.output, self.winner, self.runs, self.track_col)
         for acc in (self.abstract, self.features):
             if acc is not None:
                 ops.track_merge_finish(acc.view(-1, 1), None, self.runs, -1)
+        self.handles = tuple(self.copies.fetch(t) for t in (self.abstract, self.features, self.output))
         return self.output
+
+
+class _HostMerge(_Runs):
+    """The merge of the reruns as host arithmetic: every run is copied to the host; finish() waits for the copies, merges
+    them with multi_track_merge (the arrays host() hands out) and uploads the merged output for the split and the scoring."""
+
+    def __init__(self, *args):
+        super().__init__(*args)
+        self.output, self.abstract, self.features = [], [], []
+
+    def add(self, res, inst_id):
+        self.output.append(self.copies.fetch(res['implicit_output']))
+        self.abstract.append(self.copies.fetch(res['pcl_abstract']))
+        self.features.append(self.copies.fetch(res['features_global']))
+
+    def finish(self):
+        self.copies.wait()
+        self.handles = multi_track_merge(self.ids, *([self.copies.result(h) for h in part]
+                                                     for part in (self.abstract, self.features, self.output)), self.track_col)
+        return torch.from_numpy(self.handles[2]).to(self.copies.device)
+
+
+def _target_frame(points_query_xyz, pcl_target_frame, thresh, device, stats_target=None, scored=False):
+    """The target frame (`pcl_target_frame`, else `stats_target`) for the scorers and the gt branch -> (target_dev, nn, labels),
+    each None when nobody asks for it.  target_dev: the full-width rows, uploaded only when the frame is `scored` (otherwise the
+    xyz columns alone go up); nn: the ONE query -> target search; labels: get_1nn_label's, when pcl_target_frame is given."""
+    rows = pcl_target_frame if pcl_target_frame is not None else stats_target
+    if not scored and pcl_target_frame is None:
+        return None, None, None
+    target_dev = None
+    if scored:
+        assert rows is not None, 'stats / inst_stats need a target frame: pcl_target_frame or stats_target'
+        target_dev = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float32) if isinstance(rows, np.ndarray)
+                                     else rows).to(device=device, dtype=torch.float32)
+    nn = nn_target(points_query_xyz, target_dev[:, :3] if scored else
+                   torch.from_numpy(np.ascontiguousarray(rows[..., :3], dtype=np.float32)).to(device))
+    return target_dev, nn, None if pcl_target_frame is None else nn_labels(*nn, thresh)
 
 
 def nn_target(points_query_xyz, target_xyz):
@@ -395,8 +428,7 @@ def nn_labels(idx, dist, thresh):
 def get_1nn_label(points_query_xyz, pcl_target_frame, thresh, device):
     """Pseudo label of every query from its nearest target point (utils/geometry.py:444-455, an sklearn
     KDTree there): label = (distance < thresh), plus the neighbour's index.  Streaming k = 1 kernel."""
-    target_xyz = torch.from_numpy(np.ascontiguousarray(pcl_target_frame[..., :3], dtype=np.float32)).to(device)
-    return nn_labels(*nn_target(points_query_xyz, target_xyz), thresh)
+    return _target_frame(points_query_xyz, pcl_target_frame, thresh, device)[2]
 
 
 def multi_track_merge(track_instance_ids, pcl_abstract, features_global, implicit_output, output_track_idx):

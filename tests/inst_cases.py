@@ -477,6 +477,19 @@ def check_merge_and_state(device):
     back = pk.evaluation.InstanceStats.from_state(merged.state(), device)
     assert (back.n_ids, back.n_groups) == (3, 3) and torch.equal(back.counts, merged.counts) and torch.equal(back.sums, merged.sums)
     assert back.counts.dtype == torch.int64 and back.sums.dtype == torch.float64
+    # objects of different n_ids add (the lengths of counts / sums depend on n_groups alone: ops.inst_layout), the left one's n_ids stays
+    wide = pk.evaluation.InstanceStats(5, 3, device)
+    wide.counts += torch.arange(1, wide.counts.numel() + 1, dtype=torch.int64, device=wide.device)
+    wide.sums += 0.5 * torch.arange(1, wide.sums.numel() + 1, dtype=torch.float64, device=wide.device)
+    back += wide
+    assert torch.equal(back.counts, merged.counts + wide.counts) and torch.equal(back.sums, merged.sums + wide.sums)
+    assert not torch.equal(back.counts, merged.counts) and not torch.equal(back.sums, merged.sums)
+    assert pk.evaluation.InstanceStats.from_state(back.state(), device).n_ids == 3
+    # the two scorers do not add to each other, whatever their fields say
+    with pytest.raises(AssertionError, match='do not add'):
+        merged.merge(pk.evaluation.EvalStats(3, 0, device))
+    with pytest.raises(AssertionError, match='do not add'):
+        pk.evaluation.EvalStats(3, 0, device).merge(merged)
     bad = add_hand(new(), h, device, inst_group=np.array([0, 3, 1]))
     with pytest.raises(ValueError, match='1 rows or ids'):
         bad.summary()

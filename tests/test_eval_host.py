@@ -177,6 +177,10 @@ def test_same_frame_twice_doubles_and_merge_adds(twin, cloud):
     assert torch.equal(inplace.counts, merged.counts) and torch.equal(inplace.sums, merged.sums)
     with pytest.raises(AssertionError, match='do not add'):
         merged.merge(pk.evaluation.EvalStats(2, 0, CPU))
+    with pytest.raises(AssertionError, match='do not add'):
+        merged.merge(pk.evaluation.InstanceStats(3, merged.n_groups, CPU))
+    with pytest.raises(AssertionError, match='do not add'):
+        pk.evaluation.InstanceStats(3, merged.n_groups, CPU).merge(merged)
 
 
 def test_state_round_trips(twin, cloud):
