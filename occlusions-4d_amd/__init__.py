@@ -12,6 +12,7 @@ from . import _lib  # noqa: F401
 from . import kernels  # noqa: F401   (`with occlusions4d_amd.kernels(precision='bf16x6'):` -- per-thread kernel selection)
 from . import ops  # noqa: F401
 from . import autograd  # noqa: F401
+from . import surface  # noqa: F401   (the occupancy surface as a quad mesh: Surface, extract, write_ply)
 from . import point_transformer_layer, modules, model, geometry, implicit, inference, distributed, training  # noqa: F401
 from . import evaluation  # noqa: F401
 from . import occlusion  # noqa: F401   (valo ids, live occlusion fractions, track id: the id histogram)
@@ -20,4 +21,4 @@ from . import projection  # noqa: F401   (clouds -> camera views: projection, z-
 from . import cpu_twin  # noqa: F401   (explicit opt-in only: pk.cpu_twin.enable(); never a fallback)
 
 __all__ = ['configs', 'kernels', 'ops', 'point_transformer_layer', 'modules', 'model', 'geometry', 'implicit',
-           'inference', 'distributed', 'autograd', 'training', 'evaluation', 'occlusion', 'frontend', 'projection']
+           'inference', 'distributed', 'autograd', 'training', 'evaluation', 'occlusion', 'frontend', 'projection', 'surface']

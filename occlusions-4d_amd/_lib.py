@@ -21,6 +21,7 @@ FEATURE_HEADERS = {
     'PROJECT': 'occ4d_project.h',       # the camera projection, the z-buffer and the visibility test (projection.py)
     'INST': 'occ4d_inst.h',             # the instance statistics (evaluation.InstanceStats): the layout of the frame table and the two arrays
     'REFINE': 'occ4d_refine.h',         # the coarse-to-fine decode of the query grid (inference.perform_inference(refine=...))
+    'SURFACE': 'occ4d_surface.h',       # the occupancy surface as a quad mesh (surface.py, inference.perform_inference(surface=...))
 }
 
 

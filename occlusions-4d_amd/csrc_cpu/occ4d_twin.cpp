@@ -30,6 +30,7 @@
 #include "occ4d_project.h"
 #include "occ4d_inst.h"
 #include "occ4d_refine.h"
+#include "occ4d_surface.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -38,6 +39,7 @@
 #include "project_math.hpp"
 #include "inst_math.hpp"
 #include "refine_math.hpp"
+#include "surface_math.hpp"
 
 namespace fe = occ4d_frontend;
 namespace ev = occ4d_eval;
@@ -46,6 +48,7 @@ namespace tk = occ4d_track;
 namespace pj = occ4d_project;
 namespace in = occ4d_inst;
 namespace rf = occ4d_refine;
+namespace sf = occ4d_surface;
 
 static thread_local char g_err[512] = "";
 
@@ -667,6 +670,52 @@ int occ4d_refine_expand_f32(const float* key, const int32_t* block_offsets, cons
       rank += selected;
     }
   }
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- surface nets
+// include/occ4d_surface.h: the passes of csrc/surface.hip over csrc/surface_math.hpp, tiles and points in order.  A vertex or face
+// number is its tile's offset + the rank in the tile, as on the device: never a running count over the whole grid.
+int occ4d_surface_count_f32(const float* density, int64_t ld, int nx, int ny, int nz, float level, int32_t* cell_offsets,
+                            int32_t* face_offsets, int32_t* totals, void*) {
+  sf::CountArgs a; bool empty;
+  OCC4D_TRY(sf::check_count(density, ld, nx, ny, nz, level, cell_offsets, face_offsets, totals, empty, a));
+  if (empty) return OCC4D_OK;
+  int32_t cells = 0, quads = 0;
+  float v[8];
+  for (int64_t tile = 0; tile < a.tiles; ++tile) {
+    cell_offsets[tile] = cells;                                           // exclusive prefixes
+    face_offsets[tile] = quads;
+    for (int64_t i = tile * sf::TILE; i < std::min(a.f.grid.points, (tile + 1) * sf::TILE); ++i) {
+      const sf::Item it = sf::item_of(a.f, i, v);
+      cells += sf::crossed(it.mask);
+      quads += sf::quads_of(it.axes);
+    }
+  }
+  totals[0] = cells;
+  totals[1] = quads;
+  return OCC4D_OK;
+}
+int occ4d_surface_write_f32(const float* density, int64_t ld, const float* attrs, int64_t ld_attr, int n_attr, int nx, int ny, int nz,
+                            float level, float x0, float sx, float y0, float sy, float z0, float sz, const int32_t* cell_offsets,
+                            const int32_t* face_offsets, int32_t* work, float* vertices, int64_t ld_v, int vertex_cap,
+                            int32_t* faces, int face_cap, void*) {
+  sf::WriteArgs w; bool empty;
+  OCC4D_TRY(sf::check_write(density, ld, attrs, ld_attr, n_attr, nx, ny, nz, level, x0, sx, y0, sy, z0, sz, cell_offsets, face_offsets,
+                            work, vertices, ld_v, vertex_cap, faces, face_cap, empty, w));
+  if (empty) return OCC4D_OK;
+  float v[8];
+  for (int pass = 0; pass < 2; ++pass)                                    // the vertex pass, then the face pass (it reads work)
+    for (int64_t tile = 0; tile < w.tiles; ++tile) {
+      int64_t cells = 0, quads = 0;
+      for (int64_t i = tile * sf::TILE; i < std::min(w.f.grid.points, (tile + 1) * sf::TILE); ++i) {
+        const sf::Item it = sf::item_of(w.f, i, v);
+        if (pass == 0) sf::vertex_item(w, i, it, v, (int64_t)cell_offsets[tile] + cells);
+        else sf::face_item(w, i, it, (int64_t)face_offsets[tile] + quads);
+        cells += sf::crossed(it.mask);
+        quads += sf::quads_of(it.axes);
+      }
+    }
   return OCC4D_OK;
 }
 

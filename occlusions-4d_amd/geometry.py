@@ -109,6 +109,15 @@ def grid_counts(num_sample, min_z, cube_bounds, data_kind, cube_mode):
     return tuple(_grid_counts(num_sample, [hi - lo for lo, hi in bounds]))
 
 
+def grid_frame(num_sample, min_z, cube_bounds, data_kind, cube_mode):
+    """(counts, mins, spacings) of that grid: the very values point_sample_mode 'grid' hands to ops.grid_points, for whoever
+    has to place something on the grid it generates (surface.extract)."""
+    bounds = _query_bounds(min_z, cube_bounds, data_kind, cube_mode)
+    ext = [hi - lo for lo, hi in bounds]
+    counts = _grid_counts(num_sample, ext)
+    return counts, [lo for lo, _ in bounds], [e / c for e, c in zip(ext, counts)]
+
+
 def sample_implicit_points_blind_device(num_sample, min_z, cube_bounds, time_idx, data_kind, cube_mode,
                                         point_sample_mode, device):
     """sample_implicit_points_blind_numpy with the result resident on `device`: the grid is generated by
@@ -119,10 +128,7 @@ def sample_implicit_points_blind_device(num_sample, min_z, cube_bounds, time_idx
         pts = sample_implicit_points_blind_numpy(num_sample, min_z, cube_bounds, time_idx, data_kind, cube_mode,
                                                  point_sample_mode)
         return torch.from_numpy(pts).to(device)
-    bounds = _query_bounds(min_z, cube_bounds, data_kind, cube_mode)
-    ext = [hi - lo for lo, hi in bounds]
-    counts = _grid_counts(num_sample, ext)
-    return ops.grid_points(counts, [lo for lo, _ in bounds], [e / c for e, c in zip(ext, counts)], time_idx, device)
+    return ops.grid_points(*grid_frame(num_sample, min_z, cube_bounds, data_kind, cube_mode), time_idx, device)
 
 
 def sample_implicit_points_blind_numpy(num_sample, min_z, cube_bounds, time_idx, data_kind,

@@ -19,6 +19,7 @@ from . import implicit
 from . import kernels
 from . import model
 from . import ops
+from . import surface as surface_nets
 
 
 def get_track_idx(color_mode):
@@ -179,7 +180,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                       point_occupancy_radius=0.2, semantic_classes=13,
                       density_threshold=0.5, data_kind='', cube_mode=4, compress_air=False,
                       encoded=None, return_encoded=False, neighbour_lists=None, stats=None, stats_target=None,
-                      stats_group=None, track_merge='device', inst_stats=None, inst_group=None, refine=None):
+                      stats_group=None, track_merge='device', inst_stats=None, inst_group=None, refine=None, surface=None):
     """One encode of the input point-cloud video + decode of all query points of one output frame.  Returns
     dict(output_solid, output_air, pcl_abstract, features_global, implicit_output, points_query) of float32 numpy arrays, and
     gt_solid / gt_air when `pcl_target_frame` is given.  The keywords from `encoded` on are extensions whose defaults give the
@@ -212,7 +213,15 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     inactive block.  One device->host read per run (two counts, 8 bytes) sizes the second pass.  The result gains 'refine' =
     dict(n_queries, n_decoded): host ints, summed over the reruns.  (Bit for bit under the default kernel selection, whose one
     dependence of a row on its place in the mini-batch decode_refined reproduces; under another kernels.Selection only within
-    the mini-batch-split bound, 1e-5.)"""
+    the mini-batch-split bound, 1e-5.)
+
+    Surface.  `surface`: a surface.Surface, or None.  point_sample_mode 'grid' only (ValueError).  The result gains 'surface' =
+    dict(vertices (V, 3 + G) float32, faces (F, 4) int32): the surface density == surface.level (None: density_threshold) of the
+    squashed -- in track_mode 'all' merged, under `refine` expanded -- (N, G) array as a quad mesh, extracted on the device
+    (surface.extract, include/occ4d_surface.h): x, y, z and all G columns per vertex, normals from solid to air, open at the
+    grid's faces.  One 8-byte device->host read sizes it; the two arrays come back with the others, under the one host wait.
+    Under `refine` with refine.low <= level, a cell whose eight corners all lie in inactive blocks is never crossed (their
+    densities are the representatives', below `low`): the mesh exists only where blocks were decoded."""
     assert task == 'if'
     assert sample_implicit
     assert track_merge in ('device', 'host'), track_merge
@@ -225,6 +234,13 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         if neighbour_lists is not None:
             raise ValueError('refine decodes gathered queries: neighbour_lists cannot be given with it')
         grid_shape = geometry.grid_counts(num_sample, min_z, cube_bounds, data_kind, cube_mode)
+    surface_level = None
+    if surface is not None:
+        if not isinstance(surface, surface_nets.Surface):
+            raise ValueError('surface must be a surface.Surface or None, got %r' % (surface,))
+        if point_sample_mode != 'grid':
+            raise ValueError("surface needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
+        surface_level = surface.resolve(density_threshold)
     refine_stats = dict(n_queries=0, n_decoded=0)
     output_track_idx = get_track_idx(color_mode)
     input_inst_idx = 0 if data_kind == 'greater' else 1
@@ -294,6 +310,9 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         # the device, not by a host pass over the array)
         solid_h = copies.fetch(solid)
         air_h = copies.fetch(air, torch.float64 if compress_air else None)
+        if surface is not None:               # the very floats the query grid was generated from
+            mesh_h = [copies.fetch(t) for t in surface_nets.extract(
+                output_dev, *geometry.grid_frame(num_sample, min_z, cube_bounds, data_kind, cube_mode), surface_level)]
         copies.wait()
         solid, air = copies.result(solid_h), copies.result(air_h)
         points_query = copies.result(points_query)
@@ -303,6 +322,8 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                   features_global=features_global, implicit_output=implicit_output, points_query=points_query)
     if refine is not None:
         result['refine'] = refine_stats
+    if surface is not None:
+        result['surface'] = dict(vertices=copies.result(mesh_h[0]), faces=copies.result(mesh_h[1]))
     if return_encoded:
         result['_encoded'] = encoded_out[-1] if -1 in encoded_out else encoded_out     # (a tuple for the one unmarked run)
     if gt_available:

@@ -1211,6 +1211,52 @@ def refine_expand(key, block_offsets, rep_out, fine_out, counts, block, out=None
     return out
 
 
+def surface_capacity(counts):
+    """(cells, interior edges) of the (nx, ny, nz) grid: the most vertices and the most quads a surface-nets mesh on it has."""
+    nx, ny, nz = (int(c) for c in counts)
+    cx, cy, cz = max(nx - 1, 0), max(ny - 1, 0), max(nz - 1, 0)
+    ix, iy, iz = max(nx - 2, 0), max(ny - 2, 0), max(nz - 2, 0)
+    return cx * cy * cz, cx * iy * iz + ix * cy * iz + ix * iy * cz
+
+
+def surface_nets(values, counts, level, mins, spacings, attrs=None, sync=True):
+    """The surface values == level of the (nx, ny, nz) = `counts` grid as a quad mesh (naive surface nets: occ4d_surface_count_f32 /
+    occ4d_surface_write_f32, the rules in include/occ4d_surface.h).  values (n,): one value per grid point, x slowest, z fastest
+    (a strided column view is taken as it is); inside = values >= level.  mins / spacings: the three floats each that
+    ops.grid_points took for this grid.  attrs (n, A) with A <= 32, or None: columns interpolated onto the vertices.
+    -> (vertices (V, 3 + A) float32: x, y, z and the attributes; faces (F, 4) int32: vertex numbers, normals from inside to
+    outside), on the device; one 8-byte device->host read (V and F) sizes them.  sync=False: no read: -> (buffer (cells, 3 + A)
+    whose first V rows are the vertices, buffer (interior edges, 4) whose first F rows are the faces, (2,) int32 ON THE DEVICE:
+    V and F); the rest of the buffers is uninitialised."""
+    nx, ny, nz = (int(c) for c in counts)
+    n = nx * ny * nz
+    v = _dev(values, name='values')
+    assert v.dim() == 1 and v.shape[0] == n, 'values must be (%d,), got %s' % (n, tuple(v.shape))
+    a, ld_attr, n_attr = None, 0, 0
+    if attrs is not None:
+        a, ld_attr = _merge_rows(attrs, 'attrs')
+        assert a.shape[0] == n, 'attrs must hold %d rows, got %d' % (n, a.shape[0])
+        n_attr = a.shape[1]
+    width = 3 + n_attr
+    nb = (n + 255) // 256
+    # (an empty grid is a no-op of the library: its totals are the zeros put here)
+    scratch = (torch.empty if n else torch.zeros)(2 * nb + 2, dtype=torch.int32, device=v.device)
+    cell_offsets, face_offsets, totals = scratch[:nb], scratch[nb:2 * nb], scratch[2 * nb:]
+    st = _stream()
+    ld = v.stride(0) if n > 1 else 1
+    _lib.check(_lib.lib().occ4d_surface_count_f32(_ptr(v), ld, nx, ny, nz, float(level), _ptr(cell_offsets), _ptr(face_offsets),
+                                                  _ptr(totals), st))
+    n_vert, n_face = (int(t) for t in totals.tolist()) if sync else surface_capacity((nx, ny, nz))
+    vertices = torch.empty((n_vert, width), dtype=torch.float32, device=v.device)
+    faces = torch.empty((n_face, 4), dtype=torch.int32, device=v.device)
+    work = torch.empty((n,), dtype=torch.int32, device=v.device)
+    _lib.check(_lib.lib().occ4d_surface_write_f32(
+        _ptr(v), ld, _ptr(a), ld_attr, n_attr, nx, ny, nz, float(level), float(mins[0]), float(spacings[0]), float(mins[1]),
+        float(spacings[1]), float(mins[2]), float(spacings[2]), _ptr(cell_offsets), _ptr(face_offsets), _ptr(work), _ptr(vertices),
+        width, n_vert, _ptr(faces), n_face, st))
+    return (vertices, faces) if sync else (vertices, faces, totals)
+
+
 def eval_layout(n_groups, n_classes):
     """(len(counts), len(sums)) of the evaluation statistics arrays (include/occ4d_eval.h) for this many groups / classes."""
     lens = (int(_lib.lib().occ4d_eval_counts_len(int(n_groups), int(n_classes))), int(_lib.lib().occ4d_eval_sums_len(int(n_groups))))
