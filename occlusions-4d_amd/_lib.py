@@ -23,6 +23,13 @@ FEATURE_HEADERS = {
     'REFINE': 'occ4d_refine.h',         # the coarse-to-fine decode of the query grid (inference.perform_inference(refine=...))
     'SURFACE': 'occ4d_surface.h',       # the occupancy surface as a quad mesh (surface.py, inference.perform_inference(surface=...))
 }
+# FEATURE_HEADERS is a closed list: the suite pins it as the occ4d*.h files of include/ itself, its number of rows, and
+# ALL_SIGNATURES as the sum of its tables.  Headers that came after it live in include/ext/ and are rows here: the same
+# conventions, the same parser, the same two libraries, the same <PREFIX>_HEADER_PATH / _SIGNATURES / _CONSTANTS attributes; their
+# symbols are EXTENSION_SIGNATURES, which bind() covers beside ALL_SIGNATURES.
+EXTENSION_HEADERS = {
+    'RAYCAST': 'ext/occ4d_raycast.h',   # the decoded field ray-cast into camera views (projection.render_field, perform_inference(views=...))
+}
 
 
 class NativeLibraryError(RuntimeError):
@@ -165,6 +172,19 @@ for _prefix, _name in FEATURE_HEADERS.items():
     globals().update({_prefix + '_HEADER_PATH': _path, _prefix + '_SIGNATURES': _table,
                       _prefix + '_CONSTANTS': {k[len(_prefix) + 1:]: v for k, v in parse_constants(_text).items()}})
 
+# ... and the extension headers' symbols, in a table of their own
+EXTENSION_SIGNATURES = {}
+for _prefix, _name in EXTENSION_HEADERS.items():
+    _path = os.path.join(INCLUDE, *_name.split('/'))
+    _text = _read_header(_path)
+    _table = parse_prototypes(_text, {})
+    _twice = sorted(set(_table) & (set(ALL_SIGNATURES) | set(EXTENSION_SIGNATURES)))
+    if _twice or _prefix in FEATURE_HEADERS:
+        raise NativeLibraryError('include/%s declares %s, which another header declares too' % (_name, ', '.join(_twice) or _prefix))
+    EXTENSION_SIGNATURES.update(_table)
+    globals().update({_prefix + '_HEADER_PATH': _path, _prefix + '_SIGNATURES': _table,
+                      _prefix + '_CONSTANTS': {k[len(_prefix) + 1:]: v for k, v in parse_constants(_text).items()}})
+
 _lib = None
 _twin = False            # True only after an explicit load_cpu_twin(): host pointers, no streams (cpu_twin.py)
 
@@ -174,9 +194,9 @@ def is_twin():
 
 
 def bind(handle, missing=None):
-    """Sets restype / argtypes of every symbol of ALL_SIGNATURES on a loaded library and returns it.  A symbol the library does
+    """Sets restype / argtypes of every symbol of ALL_SIGNATURES and EXTENSION_SIGNATURES on a loaded library and returns it.  A symbol the library does
     not export is a stale library (NativeLibraryError) unless `missing` is given: then missing(name) stands in for it."""
-    for name, (res, args) in ALL_SIGNATURES.items():
+    for name, (res, args) in list(ALL_SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError:

@@ -47,6 +47,7 @@ def build(force=False, verbose=True):
     os.makedirs(OBJDIR, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hpp')]
     headers += [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.startswith('occ4d') and f.endswith('.h')]
+    headers += [os.path.join(INCLUDE, 'ext', f) for f in os.listdir(os.path.join(INCLUDE, 'ext')) if f.endswith('.h')]
     jobs = []
     objs = []
     for src in sources():

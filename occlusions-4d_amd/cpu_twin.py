@@ -33,6 +33,7 @@ FLAGS = ['-O3', '-std=c++17', '-fopenmp', '-fPIC', '-shared', '-ffp-contract=off
 
 def build(force=False):
     deps = [SRC] + [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.startswith('occ4d') and f.endswith('.h')]
+    deps += [os.path.join(INCLUDE, 'ext', f) for f in os.listdir(os.path.join(INCLUDE, 'ext')) if f.endswith('.h')]
     deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hpp')]
     if force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         gxx = shutil.which('g++')

@@ -31,6 +31,7 @@
 #include "occ4d_inst.h"
 #include "occ4d_refine.h"
 #include "occ4d_surface.h"
+#include "ext/occ4d_raycast.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -40,6 +41,7 @@
 #include "inst_math.hpp"
 #include "refine_math.hpp"
 #include "surface_math.hpp"
+#include "raycast_math.hpp"
 
 namespace fe = occ4d_frontend;
 namespace ev = occ4d_eval;
@@ -49,6 +51,7 @@ namespace pj = occ4d_project;
 namespace in = occ4d_inst;
 namespace rf = occ4d_refine;
 namespace sf = occ4d_surface;
+namespace ry = occ4d_raycast;
 
 static thread_local char g_err[512] = "";
 
@@ -716,6 +719,23 @@ int occ4d_surface_write_f32(const float* density, int64_t ld, const float* attrs
         quads += sf::quads_of(it.axes);
       }
     }
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- ray cast
+// include/ext/occ4d_raycast.h: the item body of csrc/raycast.hip over csrc/raycast_math.hpp, pixels in order.
+int occ4d_raycast_grid_f32(const float* field, int64_t ld, int nx, int ny, int nz, float x0, float sx, float y0, float sy, float z0,
+                           float sz, float level, const float* k_inv, const float* rt_inv, int V, int H, int W, float near_depth,
+                           float step, int n_steps, const float* attrs, int64_t ld_attr, int d, const int32_t* cols_host, int C,
+                           float depth_background, float feat_background, float* depth, int32_t* cell, float* feat, void*) {
+  ry::Args a; bool empty;
+  OCC4D_TRY(ry::check_raycast(field, ld, nx, ny, nz, x0, sx, y0, sy, z0, sz, level, k_inv, rt_inv, V, H, W, near_depth, step, n_steps,
+                              attrs, ld_attr, d, cols_host, C, depth_background, feat_background, depth, cell, feat, empty, a));
+  if (empty || (!a.depth && !a.cell && !a.feat)) return OCC4D_OK;
+#pragma omp parallel for collapse(2) schedule(dynamic, 4)
+  for (int v = 0; v < V; ++v)
+    for (int py = 0; py < H; ++py)
+      for (int px = 0; px < W; ++px) ry::pixel_item(a, v, px, py);
   return OCC4D_OK;
 }
 

@@ -325,7 +325,7 @@ def occlusion_groups(live_occl_row, valo_ids_pad, num_valo_ids, n_ids, edges=(0.
 
 def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt=False, reuse_encode=True, stats=None,
                   stats_group_fn=None, stats_occlusion=None, inst_stats=None, inst_group_fn=None, refine=None, surface=None,
-                  meshes=None):
+                  meshes=None, views=None, images=None):
     """batch: dict with 'pcl_input' (1,N,8), 'pcl_input_sem' (1,N,1-3), 'pcl_target' list of (1,T,9-11) tensors and
     batch['meta_data']['pcl_target_size'] (list of (1,) tensors), as the reference's test data loader yields them
     (data/data_greater.py:593-606, data/data_carla.py:651-661).  args: namespace with the test_args fields used
@@ -340,7 +340,11 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
     refine: an inference.GridRefine handed to every perform_inference call (the coarse-to-fine decode of the query grid), or None.
     surface: a surface.Surface handed to every perform_inference call, or None; `meshes`: the list every output frame's
     result['surface'] = dict(vertices, faces) is appended to (the tuples of pcl_all keep their contract).  A surface without
-    such a list is a ValueError."""
+    such a list is a ValueError.
+    views: a projection.FieldViews handed to every perform_inference call, or None; `images`: the list every output frame's
+    result['views'] = dict(depth, cell, features) is appended to, in the same way."""
+    if views is not None and not isinstance(images, list):
+        raise ValueError('evaluate_clip(views=...) needs images=<a list>: one dict of images per output frame is appended to it')
     if surface is not None and not isinstance(meshes, list):
         raise ValueError('evaluate_clip(surface=...) needs meshes=<a list>: one mesh per output frame is appended to it')
     assert stats_group_fn is None or stats_occlusion is None, 'stats_group_fn and stats_occlusion exclude each other'
@@ -381,13 +385,16 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
             predict_segmentation=args.segmentation_lw > 0.0, track_mode=args.track_mode,
             point_occupancy_radius=args.point_occupancy_radius, semantic_classes=args.semantic_classes,
             density_threshold=args.density_threshold, data_kind=data_kind, cube_mode=args.cube_mode, compress_air=True,
-            encoded=encoded if reuse_encode else None, return_encoded=reuse_encode, refine=refine, surface=surface, **stats_kw)
+            encoded=encoded if reuse_encode else None, return_encoded=reuse_encode, refine=refine, surface=surface, views=views,
+            **stats_kw)
         if reuse_encode:                  # (track_mode 'all': a dict with one encode per tracked instance)
             encoded = res.pop('_encoded')
         else:
             res.pop('_encoded', None)
         if surface is not None:
             meshes.append(res['surface'])
+        if views is not None:
+            images.append(res['views'])
         item = (pcl_input_numpy, res['pcl_abstract'], res['output_solid'], frame, res['output_air'])
         if save_gt:
             item = item + (pcl_input_sem_numpy, res['points_query'])

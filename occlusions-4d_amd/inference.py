@@ -19,6 +19,7 @@ from . import implicit
 from . import kernels
 from . import model
 from . import ops
+from . import projection
 from . import surface as surface_nets
 
 
@@ -180,7 +181,8 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                       point_occupancy_radius=0.2, semantic_classes=13,
                       density_threshold=0.5, data_kind='', cube_mode=4, compress_air=False,
                       encoded=None, return_encoded=False, neighbour_lists=None, stats=None, stats_target=None,
-                      stats_group=None, track_merge='device', inst_stats=None, inst_group=None, refine=None, surface=None):
+                      stats_group=None, track_merge='device', inst_stats=None, inst_group=None, refine=None, surface=None,
+                      views=None):
     """One encode of the input point-cloud video + decode of all query points of one output frame.  Returns
     dict(output_solid, output_air, pcl_abstract, features_global, implicit_output, points_query) of float32 numpy arrays, and
     gt_solid / gt_air when `pcl_target_frame` is given.  The keywords from `encoded` on are extensions whose defaults give the
@@ -221,7 +223,14 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     (surface.extract, include/occ4d_surface.h): x, y, z and all G columns per vertex, normals from solid to air, open at the
     grid's faces.  One 8-byte device->host read sizes it; the two arrays come back with the others, under the one host wait.
     Under `refine` with refine.low <= level, a cell whose eight corners all lie in inactive blocks is never crossed (their
-    densities are the representatives', below `low`): the mesh exists only where blocks were decoded."""
+    densities are the representatives', below `low`): the mesh exists only where blocks were decoded.
+
+    Views.  `views`: a projection.FieldViews (cameras, image size, level, channels, select, step), or None.  point_sample_mode
+    'grid' only (ValueError).  The result gains 'views' = dict(depth (V, H, W) float32, cell (V, H, W) int32, features
+    (V, H, W, C) float32): the same squashed (N, G) array -- merged, expanded -- ray-cast into the cameras on the device
+    (projection.render_field, include/ext/occ4d_raycast.h): per pixel the first crossing of density == views.level (None:
+    density_threshold), 0 / -1 / 0 where a ray meets none.  No device value is read; the three arrays come back with the others,
+    under the one host wait."""
     assert task == 'if'
     assert sample_implicit
     assert track_merge in ('device', 'host'), track_merge
@@ -241,6 +250,13 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         if point_sample_mode != 'grid':
             raise ValueError("surface needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
         surface_level = surface.resolve(density_threshold)
+    views_level = None
+    if views is not None:
+        if not isinstance(views, projection.FieldViews):
+            raise ValueError('views must be a projection.FieldViews or None, got %r' % (views,))
+        if point_sample_mode != 'grid':
+            raise ValueError("views needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
+        views_level = views.resolve(density_threshold)
     refine_stats = dict(n_queries=0, n_decoded=0)
     output_track_idx = get_track_idx(color_mode)
     input_inst_idx = 0 if data_kind == 'greater' else 1
@@ -313,6 +329,9 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         if surface is not None:               # the very floats the query grid was generated from
             mesh_h = [copies.fetch(t) for t in surface_nets.extract(
                 output_dev, *geometry.grid_frame(num_sample, min_z, cube_bounds, data_kind, cube_mode), surface_level)]
+        if views is not None:
+            views_h = [copies.fetch(t) for t in views.render(
+                output_dev, *geometry.grid_frame(num_sample, min_z, cube_bounds, data_kind, cube_mode), views_level)]
         copies.wait()
         solid, air = copies.result(solid_h), copies.result(air_h)
         points_query = copies.result(points_query)
@@ -324,6 +343,8 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         result['refine'] = refine_stats
     if surface is not None:
         result['surface'] = dict(vertices=copies.result(mesh_h[0]), faces=copies.result(mesh_h[1]))
+    if views is not None:
+        result['views'] = dict(zip(('depth', 'cell', 'features'), (copies.result(h) for h in views_h)))
     if return_encoded:
         result['_encoded'] = encoded_out[-1] if -1 in encoded_out else encoded_out     # (a tuple for the one unmarked run)
     if gt_available:

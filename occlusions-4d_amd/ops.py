@@ -98,8 +98,19 @@ def _rows(t, name='tensor'):
     return t, (t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0)))
 
 
+class _TensorPointer(C.c_void_p):
+    """A void pointer that owns a reference to the tensor it points into: the memory stays allocated for as long as the pointer
+    object lives, so a caller may build an argument list out of _ptr(<temporary tensor>) without the library reading or writing
+    freed memory (on the host that is heap corruption; the device's caching allocator merely hides it)."""
+    __slots__ = ('tensor',)
+
+
 def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    if t is None:
+        return C.c_void_p(0)
+    ptr = _TensorPointer(t.data_ptr())
+    ptr.tensor = t
+    return ptr
 
 
 def _aligned_rows(t, name, k_pad=None):
@@ -1501,6 +1512,46 @@ def zbuffer_resolve(keys, rows, channels=(), background=0.0, feature_background=
     _lib.check(_lib.lib().occ4d_zbuffer_resolve_f32(_ptr(kk), V, H, W, _ptr(r), max(ld, d), n, d, float(background), _ptr(depth),
                                                     _ptr(index), arr, n_ch, float(fbg), _ptr(feat) if n_ch else None, _stream()))
     return depth, index, feat
+
+
+def raycast_grid(values, counts, mins, spacings, level, rt_inv, k_inv, height, width, near, step, n_steps, attrs=None, channels=(),
+                 background=0.0, feature_background=None):
+    """The field `values` on the (nx, ny, nz) = `counts` grid ray-cast into V views (occ4d_raycast_grid_f32, the rules in
+    include/ext/occ4d_raycast.h): per pixel the first of the n_steps samples at depths near + i * step whose trilinear value is
+    >= level, refined against the sample before it.  values (n,): one value per grid point, x slowest, z fastest (a strided
+    column view is read in place); mins / spacings: the three floats each that ops.grid_points took for this grid; rt_inv,
+    k_inv (V, 16) or (V, 4, 4): the INVERSES of the expanded camera matrices.  attrs (n, d) and `channels`: the columns
+    sampled at the hit.  -> (depth (V, H, W) fp32, `background` where nothing is hit; cell (V, H, W) int32, the flat index of
+    the hit cell's low corner or -1; features (V, H, W, C), `feature_background` (default: `background`) where nothing is hit),
+    on the device.  No host read."""
+    nx, ny, nz = (int(c) for c in counts)
+    n = nx * ny * nz
+    v = _dev(values, name='values')
+    assert v.dim() == 1 and v.shape[0] == n, 'values must be (%d,), got %s' % (n, tuple(v.shape))
+    rt, k = _dev(rt_inv, name='rt_inv'), _dev(k_inv, name='k_inv')
+    V = rt.shape[0] if rt.dim() else -1
+    assert rt.dim() in (2, 3) and rt.numel() == V * 16 and tuple(k.shape) == tuple(rt.shape), \
+        'rt_inv / k_inv must both be (V, 16) or (V, 4, 4), got %s and %s' % (tuple(rt.shape), tuple(k.shape))
+    rt, k = rt.contiguous(), k.contiguous()
+    H, W = int(height), int(width)
+    cols = [int(c) for c in channels]
+    n_ch = len(cols)
+    a, ld_attr, d = None, 0, 0
+    if n_ch:
+        assert attrs is not None, 'channels need attrs'
+        a, ld_attr = _merge_rows(attrs, 'attrs')
+        assert a.shape[0] == n, 'attrs must hold %d rows, got %d' % (n, a.shape[0])
+        d = a.shape[1]
+    depth = torch.empty((V, H, W), dtype=torch.float32, device=v.device)
+    cell = torch.empty((V, H, W), dtype=torch.int32, device=v.device)
+    feat = torch.empty((V, H, W, n_ch), dtype=torch.float32, device=v.device)
+    arr = (C.c_int32 * n_ch)(*cols) if n_ch else None
+    fbg = background if feature_background is None else feature_background
+    _lib.check(_lib.lib().occ4d_raycast_grid_f32(
+        _ptr(v), v.stride(0) if n > 1 else 1, nx, ny, nz, float(mins[0]), float(spacings[0]), float(mins[1]), float(spacings[1]),
+        float(mins[2]), float(spacings[2]), float(level), _ptr(k), _ptr(rt), V, H, W, float(near), float(step), int(n_steps), _ptr(a),
+        max(ld_attr, d), d, arr, n_ch, float(background), float(fbg), _ptr(depth), _ptr(cell), _ptr(feat) if n_ch else None, _stream()))
+    return depth, cell, feat
 
 
 def visibility(rows, rt, k, depth, margin):

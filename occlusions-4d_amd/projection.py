@@ -8,8 +8,13 @@ points the model is scored on: VISIBLE from a camera, OCCLUDED from it, or OUTSI
 stats_occlusion=...)`` feeds it to ``EvalStats`` as the group of every target point.  Where a data set has no depth image (CARLA),
 ``render_views`` of the forward sweep gives one.
 
-Everything runs in the four kernels of csrc/project.hip; clouds, cameras and images stay on the device and no function here
-reads a device value on the host.  The arithmetic equals the reference's numpy results bit for bit (tests/golden/project_*.npz).
+``render_field`` shows the decoded field itself instead of a cloud: the dense (N, G) output of a grid decode ray-cast into the
+cameras (include/ext/occ4d_raycast.h, csrc/raycast.hip) -- the depth of the surface density == level, the mask of what was hit, and
+output columns sampled at the hit; ``FieldViews`` is its option object for ``perform_inference(views=...)``.
+
+The cloud functions run in the four kernels of csrc/project.hip; clouds, cameras and images stay on the device and none of them
+reads a device value on the host (render_field inverts its cameras on the host: cameras given as device tensors are read once).
+The arithmetic equals the reference's numpy results bit for bit (tests/golden/project_*.npz).
 """
 import numpy as np
 import torch
@@ -94,3 +99,116 @@ def visibility(points, depth, cam_RT, cam_K, margin):
     if dep.dim() == 2:
         dep = dep[None]
     return ops.visibility(rows, rt, k, dep, margin)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the decoded field
+MAX_STEPS = _lib.RAYCAST_CONSTANTS['MAX_STEPS']        # the header's limit on n_steps (include/ext/occ4d_raycast.h)
+
+
+def invert_cameras(cam_RT, cam_K):
+    """The inverses of the expanded 4 x 4 matrices of V cameras, (rt_inv, k_inv), both (V, 4, 4) float32 numpy: inverted on the
+    HOST in float64 and rounded once -- 2 V 16 numbers that are known before any decode; nothing here depends on a device solver
+    library.  Also returns the float64 expanded rt (V, 4, 4) (the depth of a world point is its row 2).  Device tensors are read
+    to the host: one small read."""
+    def host(a):
+        return np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+    RT, K = host(cam_RT), host(cam_K)
+    if RT.ndim == 2:
+        RT = RT[None]
+    assert RT.ndim == 3 and RT.shape[1:] == (3, 4), 'cam_RT must be (V, 3, 4) or (3, 4), got %s' % (RT.shape,)
+    V = RT.shape[0]
+    if K.ndim == 2:
+        K = np.broadcast_to(K[None], (V, 3, 3))
+    assert K.shape == (V, 3, 3), 'cam_K must be (3, 3) or (V = %d, 3, 3), got %s' % (V, K.shape)
+    rt, k = np.tile(np.eye(4), (V, 1, 1)), np.tile(np.eye(4), (V, 1, 1))
+    rt[:, :3, :], k[:, :3, :3] = RT, K
+    return np.linalg.inv(rt).astype(np.float32), np.linalg.inv(k).astype(np.float32), rt
+
+
+def march_range(counts, mins, spacings, rt64, near=None, far=None, step=None):
+    """(near, step, n_steps) of a ray cast of the (nx, ny, nz) grid under the cameras rt64 (V, 4, 4) float64.  Defaults: step =
+    half the smallest spacing; near / far = the smallest / largest depth of the eight corners of the hull of the grid's points
+    under any of the cameras, near not below step; n_steps = ceil((far - near) / step) + 1.  ValueError when that exceeds the
+    header's limit (or the range is not finite)."""
+    counts, mins, spacings = [int(c) for c in counts], [float(m) for m in mins], [float(s) for s in spacings]
+    if step is None:
+        step = 0.5 * min(spacings)
+    step = float(step)
+    if not (step > 0.0 and np.isfinite(step)):
+        raise ValueError('render_field: step = %r must be finite and > 0' % (step,))
+    lo = [m + 0.5 * s for m, s in zip(mins, spacings)]
+    hi = [m + (c - 0.5) * s for m, s, c in zip(mins, spacings, counts)]
+    corners = np.array([[x, y, z, 1.0] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])])
+    depths = np.einsum('vj,cj->vc', rt64[:, 2, :], corners) if len(rt64) else np.zeros((1, 1))
+    near = max(float(depths.min()), step) if near is None else float(near)
+    far = float(depths.max()) if far is None else float(far)
+    if not (np.isfinite(near) and np.isfinite(far)):
+        raise ValueError('render_field: near = %r, far = %r must be finite' % (near, far))
+    n_steps = int(np.ceil(max(far - near, 0.0) / step)) + 1
+    if n_steps > MAX_STEPS:
+        raise ValueError('render_field: n_steps = %d exceeds %d: (far - near) / step = (%g - %g) / %g' % (n_steps, MAX_STEPS, far, near, step))
+    return near, step, n_steps
+
+
+class FieldViews:
+    """The option object of perform_inference(views=...) / evaluate_clip(views=...): the cameras cam_RT (V, 3, 4), cam_K (3, 3) or
+    (V, 3, 3) and the image size the decoded field is ray-cast into (render_field).  level: the density of the surface shown,
+    None = the call's density_threshold; channels: the output columns sampled at the hit; select = (column, threshold) or None;
+    step: the march's step in depth, None = half the smallest grid spacing.  The cameras are inverted here, once, on the host."""
+
+    def __init__(self, cam_RT, cam_K, height, width, level=None, channels=(), select=None, step=None):
+        if level is not None:
+            level = float(level)
+            if level != level:
+                raise ValueError('FieldViews: level is NaN')
+        self.rt_inv, self.k_inv, self.rt64 = invert_cameras(cam_RT, cam_K)
+        self.height, self.width = int(height), int(width)
+        if self.height < 0 or self.width < 0:
+            raise ValueError('FieldViews: height = %r, width = %r' % (height, width))
+        self.level, self.channels, self.step = level, tuple(int(c) for c in channels), step
+        self.select = None if select is None else (int(select[0]), float(select[1]))
+
+    def resolve(self, density_threshold):
+        level = float(density_threshold) if self.level is None else self.level
+        if level != level:
+            raise ValueError('FieldViews: level is NaN')
+        return level
+
+    def render(self, implicit_output, counts, mins, spacings, level, channel=0, near=None, far=None, background=0.0):
+        """-> (depth, cell, features) of implicit_output (N, G) on its device."""
+        out = implicit_output
+        assert out.dim() == 2 and 0 <= channel < out.shape[1], 'channel = %r' % (channel,)
+        field = out[:, channel]
+        if self.select is not None:
+            column, threshold = self.select
+            assert 0 <= column < out.shape[1], 'select column = %r' % (column,)
+            field = torch.where(out[:, column] >= threshold, field, torch.zeros((), dtype=out.dtype, device=out.device))
+        near, step, n_steps = march_range(counts, mins, spacings, self.rt64, near, far, self.step)
+        rt_inv, k_inv = (torch.from_numpy(m).to(out.device) for m in (self.rt_inv, self.k_inv))
+        return ops.raycast_grid(field, counts, mins, spacings, level, rt_inv, k_inv, self.height, self.width, near, step, n_steps,
+                                attrs=out, channels=self.channels, background=background)
+
+    def __repr__(self):
+        return 'FieldViews(V=%d, height=%d, width=%d, level=%r, channels=%r, select=%r, step=%r)' % (
+            len(self.rt_inv), self.height, self.width, self.level, self.channels, self.select, self.step)
+
+
+def render_field(implicit_output, counts, mins, spacings, cam_RT, cam_K, height, width, level, channel=0, channels=(), select=None,
+                 near=None, far=None, step=None, background=0.0):
+    """The decoded field itself in V camera views (include/ext/occ4d_raycast.h): per pixel the first crossing of
+    implicit_output[:, channel] == level along the pixel's ray through the (nx, ny, nz) = `counts` grid whose points
+    ops.grid_points made from `mins` / `spacings` (geometry.grid_frame).  -> dict of device tensors: 'depth' (V, H, W) fp32
+    (`background` where the ray meets no surface), 'cell' (V, H, W) int32 (the flat index of the hit cell's low corner, -1 =
+    none: cell >= 0 is the mask) and 'features' (V, H, W, C): the columns `channels` of implicit_output, trilinear at the hit.
+    select = (column, threshold): the field is where(implicit_output[:, column] >= threshold, implicit_output[:, channel], 0);
+    with column = the track channel it shows the tracked object alone: its amodal depth and mask.
+    The march: samples at depths near + i * step; defaults in march_range.  The cameras are inverted on the host in float64
+    (invert_cameras); cameras given as device tensors cost one small device->host read, nothing else is read."""
+    level = float(level)
+    if level != level:
+        raise ValueError('render_field: level is NaN')
+    device = _device(implicit_output)
+    views = FieldViews(cam_RT, cam_K, height, width, level, channels, select, step)
+    depth, cell, feat = views.render(_tensor(implicit_output, device, 'implicit_output'), counts, mins, spacings, level, channel, near,
+                                     far, background)
+    return dict(depth=depth, cell=cell, features=feat)
