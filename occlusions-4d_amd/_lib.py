@@ -30,6 +30,12 @@ FEATURE_HEADERS = {
 EXTENSION_HEADERS = {
     'RAYCAST': 'ext/occ4d_raycast.h',   # the decoded field ray-cast into camera views (projection.render_field, perform_inference(views=...))
 }
+# EXTENSION_SIGNATURES is pinned by the suite as well (as the ray-cast's table).  Headers of include/ext/ whose prototypes take the
+# structs of occ4d.h are rows here: parsed with those structs, <PREFIX>_HEADER_PATH / _SIGNATURES attributes as above, their symbols
+# in STRUCT_EXTENSION_SIGNATURES, which bind() covers too.
+STRUCT_EXTENSION_HEADERS = {
+    'PRELUDE': 'ext/occ4d_prelude.h',   # the decoder's query prelude (inference.QueryPrelude, LocalPclResnetFC.query_prelude)
+}
 
 
 class NativeLibraryError(RuntimeError):
@@ -156,8 +162,9 @@ class DecoderWeights(C.Structure):
 
 
 # name -> (restype, argtypes): every symbol include/occ4d.h declares
-SIGNATURES = parse_prototypes(_HEADER, {'occ4d_linear_args': LinearArgs, 'occ4d_pt_layer_weights': PtLayerWeights,
-                                        'occ4d_launch_events': LaunchEvents, 'occ4d_decoder_weights': DecoderWeights})
+_STRUCTS = {'occ4d_linear_args': LinearArgs, 'occ4d_pt_layer_weights': PtLayerWeights, 'occ4d_launch_events': LaunchEvents,
+            'occ4d_decoder_weights': DecoderWeights}
+SIGNATURES = parse_prototypes(_HEADER, _STRUCTS)
 
 # ... and every symbol any header declares; two headers that declare the same one are an error
 ALL_SIGNATURES = dict(SIGNATURES)
@@ -185,6 +192,17 @@ for _prefix, _name in EXTENSION_HEADERS.items():
     globals().update({_prefix + '_HEADER_PATH': _path, _prefix + '_SIGNATURES': _table,
                       _prefix + '_CONSTANTS': {k[len(_prefix) + 1:]: v for k, v in parse_constants(_text).items()}})
 
+# ... and those of the extension headers that use occ4d.h's structs
+STRUCT_EXTENSION_SIGNATURES = {}
+for _prefix, _name in STRUCT_EXTENSION_HEADERS.items():
+    _path = os.path.join(INCLUDE, *_name.split('/'))
+    _table = parse_prototypes(_read_header(_path), _STRUCTS)
+    _twice = sorted(set(_table) & (set(ALL_SIGNATURES) | set(EXTENSION_SIGNATURES) | set(STRUCT_EXTENSION_SIGNATURES)))
+    if _twice or _prefix in FEATURE_HEADERS or _prefix in EXTENSION_HEADERS:
+        raise NativeLibraryError('include/%s declares %s, which another header declares too' % (_name, ', '.join(_twice) or _prefix))
+    STRUCT_EXTENSION_SIGNATURES.update(_table)
+    globals().update({_prefix + '_HEADER_PATH': _path, _prefix + '_SIGNATURES': _table})
+
 _lib = None
 _twin = False            # True only after an explicit load_cpu_twin(): host pointers, no streams (cpu_twin.py)
 
@@ -194,9 +212,10 @@ def is_twin():
 
 
 def bind(handle, missing=None):
-    """Sets restype / argtypes of every symbol of ALL_SIGNATURES and EXTENSION_SIGNATURES on a loaded library and returns it.  A symbol the library does
+    """Sets restype / argtypes of every symbol of ALL_SIGNATURES and the two extension tables on a loaded library and returns it.  A symbol the library does
     not export is a stale library (NativeLibraryError) unless `missing` is given: then missing(name) stands in for it."""
-    for name, (res, args) in list(ALL_SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()):
+    for name, (res, args) in (list(ALL_SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items())
+                              + list(STRUCT_EXTENSION_SIGNATURES.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError:

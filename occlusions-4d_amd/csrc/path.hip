@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "decoder_math.hpp"
 
 namespace {
 
@@ -696,10 +697,54 @@ int clamp_indices(const int32_t* src, int64_t n, int m, int32_t* dst, hipStream_
   return occ4d::check_launch("occ4d_decoder_query_fwd_f32 (neighbour lists)");
 }
 
+// The decoder's query front end (D2 + D3, the cross layers' lists, D5 + lin_in): the part of a decode that needs only the
+// abstract cloud's COORDINATES and the raw weights -- no per-scene table, no prepared buffer.  decoder_forward runs it per
+// chunk; occ4d_decoder_query_prelude_f32 runs it once over all the queries of a step, beside the encoder.
+int query_lists(const occ4d_decoder_weights& w, const float* xyz, int m, const float* q, int64_t qs, int c,
+                const int32_t* knn_local, const int32_t* knn_cross, int32_t* idx8, float* w8, int32_t* idx_att,
+                hipStream_t st) {
+  // D2 + D3 (model/implicit.py:328-342): 8 nearest abstract points by Euclidean norm, inverse-distance weights
+  // (caller-supplied lists: the reference's own tie order; distances recomputed with the search's expression)
+  if (knn_local) {
+    TRY(clamp_indices(knn_local, (int64_t)c * w.k_local, m, idx8, st));
+    TRY(occ4d_knn_dists_f32(q, qs, c, xyz, 3, m, idx8, w.k_local, 1, w8, st));
+  } else {
+    TRY(occ4d_knn_f32(q, qs, c, xyz, 3, m, w.k_local, 1, idx8, 0, w8, st));
+  }
+  TRY(occ4d_interp_weights_f32(w8, c, w.k_local, w8, st));
+  // one kNN_torch (model/point_transformer_layer.py:167) serves every cross-attention layer: same xyz, same K
+  if (w.n_cross && knn_cross) TRY(clamp_indices(knn_cross, (int64_t)c * w.k_cross, m, idx_att, st));
+  else if (w.n_cross) TRY(occ4d_knn_f32(q, qs, c, xyz, 3, m, w.k_cross, 0, idx_att, 0, nullptr, st));
+  return OCC4D_OK;
+}
+// D5 + lin_in (:405-408): x = lin_in(posenc(q)); pe: c rows of lin_in_ld floats
+int query_embed(const occ4d_decoder_weights& w, const float* q, int64_t qs, int c, float* pe, float* x, int64_t ldx,
+                hipStream_t st) {
+  const int P = w.d_in * (2 * w.n_freq + 1), P4 = w.lin_in_ld;
+  if (w.n_freq > 0) {
+    if (P4 != P) TRY(occ4d::zero_rows(pe, P4, c, P4, st));
+    TRY(occ4d_posenc_f32(q, qs, c, w.d_in, w.n_freq, (double)w.base_frequency, pe, P4, st));
+  } else {
+    TRY(occ4d::zero_rows(pe, P4, c, P4, st));
+    TRY(occ4d::copy_rows(pe, P4, q, qs, c, w.d_in, st));
+  }
+  return lin(pe, P4, w.lin_in_w, w.lin_in_ld, w.lin_in_b, x, ldx, c, P4, w.d_hidden, 0, 0, nullptr, 0, st);
+}
+
+// What occ4d_decoder_query_prelude_f32 left for the rows of a forward call: the lists and weights, and optionally lin_in's
+// output, which then IS the trunk's x buffer.
+struct QueryPrelude {
+  const int32_t* idx_local;
+  const float* w_local;
+  const int32_t* idx_cross;
+  float* x0;
+  int64_t ld_x0;
+};
+
 int decoder_forward(const occ4d_decoder_weights& w, const DecoderLayout& L, const float* prep, const float* scene, int m,
                     const float* queries, int64_t qs, int n, const int32_t* knn_local, const int32_t* knn_cross, float* out,
                     int64_t ld_out, float* penult, int64_t ld_pen, Bump& ws, int flags, const Events& E, hipStream_t st,
-                    bool dry) {
+                    bool dry, const QueryPrelude* pre = nullptr) {
   const int H = L.H;
   const DecoderScene S = decoder_scene_layout(w, m);
   const float* xyz = scene ? scene + S.xyz : nullptr;
@@ -709,39 +754,23 @@ int decoder_forward(const occ4d_decoder_weights& w, const DecoderLayout& L, cons
     const int c = std::min(step, n - lo);
     const int64_t mark = ws.mark();
     const float* q = queries + (int64_t)lo * qs;
-    float* x = penult ? penult + (int64_t)lo * ld_pen : ws.take((int64_t)c * H);
-    const int64_t ldx = penult ? ld_pen : H;
-    int32_t* idx8 = reinterpret_cast<int32_t*>(ws.take((int64_t)c * w.k_local));
-    float* w8 = ws.take((int64_t)c * w.k_local);
-    int32_t* idx_att = L.nC ? reinterpret_cast<int32_t*>(ws.take((int64_t)c * w.k_cross)) : nullptr;
-    float* pe = ws.take((int64_t)c * L.P4);
+    const bool x_given = pre && pre->x0 && !penult;        // the prelude's rows serve in place; with penult they are copied there
+    float* x = penult ? penult + (int64_t)lo * ld_pen : x_given ? pre->x0 + (int64_t)lo * pre->ld_x0 : ws.take((int64_t)c * H);
+    const int64_t ldx = penult ? ld_pen : x_given ? pre->ld_x0 : H;
+    int32_t* idx8 = pre ? const_cast<int32_t*>(pre->idx_local + (int64_t)lo * w.k_local)
+                        : reinterpret_cast<int32_t*>(ws.take((int64_t)c * w.k_local));
+    float* w8 = pre ? const_cast<float*>(pre->w_local + (int64_t)lo * w.k_local) : ws.take((int64_t)c * w.k_local);
+    int32_t* idx_att = !L.nC ? nullptr
+                       : pre ? const_cast<int32_t*>(pre->idx_cross + (int64_t)lo * w.k_cross)
+                             : reinterpret_cast<int32_t*>(ws.take((int64_t)c * w.k_cross));
+    float* pe = pre && pre->x0 ? nullptr : ws.take((int64_t)c * L.P4);
     float* hbuf = (L.resblock && (!L.x6trunk || L.f16block)) ? nullptr : ws.take((int64_t)c * H);
     if (!dry) {
-      // D2 + D3 (model/implicit.py:328-342): 8 nearest abstract points by Euclidean norm, inverse-distance weights
-      // (caller-supplied lists: the reference's own tie order; distances recomputed with the search's expression)
-      if (knn_local) {
-        TRY(clamp_indices(knn_local + (int64_t)lo * w.k_local, (int64_t)c * w.k_local, m, idx8, st));
-        TRY(occ4d_knn_dists_f32(q, qs, c, xyz, 3, m, idx8, w.k_local, 1, w8, st));
-      } else {
-        TRY(occ4d_knn_f32(q, qs, c, xyz, 3, m, w.k_local, 1, idx8, 0, w8, st));
-      }
-      TRY(occ4d_interp_weights_f32(w8, c, w.k_local, w8, st));
-      // one kNN_torch (model/point_transformer_layer.py:167) serves every cross-attention layer: same xyz, same K
-      if (L.nC && knn_cross) TRY(clamp_indices(knn_cross + (int64_t)lo * w.k_cross, (int64_t)c * w.k_cross, m, idx_att, st));
-      else if (L.nC) TRY(occ4d_knn_f32(q, qs, c, xyz, 3, m, w.k_cross, 0, idx_att, 0, nullptr, st));
-      // D5 + lin_in (:405-408)
-      const float* emb = q;
-      int64_t ld_emb = qs;
-      if (w.n_freq > 0) {
-        if (L.P4 != L.P) TRY(occ4d::zero_rows(pe, L.P4, c, L.P4, st));
-        TRY(occ4d_posenc_f32(q, qs, c, w.d_in, w.n_freq, (double)w.base_frequency, pe, L.P4, st));
-        emb = pe; ld_emb = L.P4;
-      } else {
-        TRY(occ4d::zero_rows(pe, L.P4, c, L.P4, st));
-        TRY(occ4d::copy_rows(pe, L.P4, q, qs, c, w.d_in, st));
-        emb = pe; ld_emb = L.P4;
-      }
-      TRY(lin(emb, ld_emb, w.lin_in_w, w.lin_in_ld, w.lin_in_b, x, ldx, c, L.P4, H, 0, 0, nullptr, 0, st));
+      if (!pre)
+        TRY(query_lists(w, xyz, m, q, qs, c, knn_local ? knn_local + (int64_t)lo * w.k_local : nullptr,
+                        knn_cross ? knn_cross + (int64_t)lo * w.k_cross : nullptr, idx8, w8, idx_att, st));
+      if (pe) TRY(query_embed(w, q, qs, c, pe, x, ldx, st));
+      else if (!x_given) TRY(occ4d::copy_rows(x, ldx, pre->x0 + (int64_t)lo * pre->ld_x0, pre->ld_x0, c, H, st));
     }
     int next_cross = 0;
     for (int i = 0; i < L.nB; ++i) {
@@ -1085,4 +1114,48 @@ extern "C" int occ4d_decoder_query_fwd_f32(const occ4d_decoder_weights* w, const
   const Events E{ev, (hipStream_t)stream};
   return decoder_forward(*w, decoder_layout(*w, flags), prepared, scene, m, queries, q_stride, n, knn_local, knn_cross, out,
                          ld_out, penult, ld_pen, ws, flags, E, (hipStream_t)stream, false);
+}
+
+// ---- the query prelude: the front end of ALL the queries of a step in one pass, from coordinates and raw weights alone
+extern "C" int64_t occ4d_decoder_query_prelude_workspace_floats(const occ4d_decoder_weights* w, int n, int with_x0) {
+  if (check_decoder(w, "occ4d_decoder_query_prelude_workspace_floats") || n < 0) return -1;
+  Bump ws(nullptr);
+  if (with_x0) ws.take((int64_t)std::min(n, occ4d_decoder::PRELUDE_ROWS) * w->lin_in_ld);
+  return ws.peak + ALIGN;
+}
+extern "C" int occ4d_decoder_query_prelude_f32(const occ4d_decoder_weights* w, const float* xyz, int m, const float* queries,
+                                               int64_t q_stride, int n, int32_t* idx_local, float* w_local,
+                                               int32_t* idx_cross, float* x0, int64_t ld_x0, float* workspace, void* stream) {
+  TRY(check_decoder(w, "occ4d_decoder_query_prelude_f32"));
+  bool empty = false;
+  TRY(occ4d_decoder::check_query_prelude(w, xyz, m, queries, q_stride, n, idx_local, w_local, idx_cross, x0, ld_x0, workspace,
+                                         &empty));
+  if (empty) return OCC4D_OK;
+  hipStream_t st = (hipStream_t)stream;
+  for (int lo = 0; lo < n; lo += occ4d_decoder::PRELUDE_ROWS) {
+    const int c = std::min(occ4d_decoder::PRELUDE_ROWS, n - lo);
+    const float* q = queries + (int64_t)lo * q_stride;
+    TRY(query_lists(*w, xyz, m, q, q_stride, c, nullptr, nullptr, idx_local + (int64_t)lo * w->k_local,
+                    w_local + (int64_t)lo * w->k_local, w->n_cross ? idx_cross + (int64_t)lo * w->k_cross : nullptr, st));
+    if (x0) TRY(query_embed(*w, q, q_stride, c, workspace, x0 + (int64_t)lo * ld_x0, ld_x0, st));
+  }
+  return OCC4D_OK;
+}
+extern "C" int occ4d_decoder_query_fwd_prelude_f32(const occ4d_decoder_weights* w, const float* prepared, const float* scene,
+                                                   int m, const float* queries, int64_t q_stride, int n,
+                                                   const int32_t* idx_local, const float* w_local, const int32_t* idx_cross,
+                                                   float* x0, int64_t ld_x0, float* out, int64_t ld_out, float* penult,
+                                                   int64_t ld_pen, float* workspace, int flags, occ4d_launch_events* ev,
+                                                   void* stream) {
+  TRY(check_decoder(w, "occ4d_decoder_query_fwd_prelude_f32"));
+  if (ev) ev->used = 0;
+  bool empty = false;
+  TRY(occ4d_decoder::check_query_fwd_prelude(w, prepared, scene, m, queries, q_stride, n, idx_local, w_local, idx_cross, x0,
+                                             ld_x0, out, ld_out, penult, ld_pen, workspace, &empty));
+  if (empty) return OCC4D_OK;
+  Bump ws(workspace);
+  const Events E{ev, (hipStream_t)stream};
+  const QueryPrelude pre{idx_local, w_local, idx_cross, x0, ld_x0};
+  return decoder_forward(*w, decoder_layout(*w, flags), prepared, scene, m, queries, q_stride, n, nullptr, nullptr, out, ld_out,
+                         penult, ld_pen, ws, flags, E, (hipStream_t)stream, false, &pre);
 }

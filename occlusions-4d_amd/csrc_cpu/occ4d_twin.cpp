@@ -42,6 +42,7 @@
 #include "refine_math.hpp"
 #include "surface_math.hpp"
 #include "raycast_math.hpp"
+#include "decoder_math.hpp"
 
 namespace fe = occ4d_frontend;
 namespace ev = occ4d_eval;
@@ -969,13 +970,43 @@ int occ4d_decoder_prepare_scene_f32(const occ4d_decoder_weights* w, const float*
 }
 int64_t occ4d_decoder_query_workspace_floats(const occ4d_decoder_weights* w, int, int, int) { return w ? 64 : -1; }
 
-int occ4d_decoder_query_fwd_f32(const occ4d_decoder_weights* w, const float*, const float* scene, int m, const float* queries,
-                                int64_t qs, int n, const int32_t* knn_local, const int32_t* knn_cross, float* out, int64_t ld_out,
-                                float* penult, int64_t ld_pen, float*, int, occ4d_launch_events* ev, void*) {
-  const char* who = "occ4d_decoder_query_fwd_f32";
-  OCC4D_TRY(check_decoder(w, who));
-  OCC4D_REQUIRE(scene && queries && out && n >= 0 && m >= w->k_local && (w->n_cross == 0 || m >= w->k_cross), "%s: bad arguments", who);
-  if (ev) ev->used = 0;
+// The prelude's rows of the queries of a forward call (occ4d_decoder_query_fwd_prelude_f32), or none
+struct QueryPrelude {
+  const int32_t* idx_local;
+  const float* w_local;
+  const int32_t* idx_cross;
+  const float* x0;
+  int64_t ld_x0;
+};
+
+// D2 + D3 of one query: the k_local nearest abstract points by Euclidean norm (or the caller's list, clamped) and their
+// normalised inverse-distance weights, in occ4d_interp_weights_f32's expressions
+static void local_list_one(const float* qi, const float* xyz, int m, int kl, const int32_t* given, int32_t* i8, float* w8) {
+  float d8[16];
+  if (given) {
+    for (int j = 0; j < kl; ++j) {
+      i8[j] = std::min(std::max(given[j], 0), m - 1);
+      d8[j] = dist_metric(qi, xyz + 3 * (int64_t)i8[j], 1);
+    }
+  } else {
+    knn_one(qi, xyz, 3, m, kl, 1, i8, d8);
+  }
+  float ws = 0.f;
+  for (int j = 0; j < kl; ++j) { w8[j] = 1.f / (d8[j] + 1e-4f); ws += std::fabs(w8[j]); }
+  ws = std::max(ws, 1e-12f);
+  for (int j = 0; j < kl; ++j) w8[j] /= ws;
+}
+// D5 + lin_in of one query (:405-408); pe: d_in (2 n_freq + 1) floats of scratch
+static void embed_one(const occ4d_decoder_weights* w, const float* qi, int64_t qs, float* pe, float* x) {
+  const int P = w->d_in * (2 * w->n_freq + 1);
+  if (w->n_freq > 0) occ4d_posenc_f32(qi, qs, 1, w->d_in, w->n_freq, (double)w->base_frequency, pe, P, nullptr);
+  else std::copy(qi, qi + w->d_in, pe);
+  matvec(w->lin_in_w, w->lin_in_ld, w->lin_in_b, pe, w->d_hidden, P, x);
+}
+
+static int decoder_rows(const occ4d_decoder_weights* w, const float* scene, int m, const float* queries, int64_t qs, int n,
+                        const int32_t* knn_local, const int32_t* knn_cross, const QueryPrelude* pre, float* out, int64_t ld_out,
+                        float* penult, int64_t ld_pen) {
   const DecScene S = dec_scene(*w, m);
   const float *xyz = scene + S.xyz, *feats = scene + S.feats, *fglobal = scene + S.fglobal;
   const int H = w->d_hidden, E = w->d_latent_local, dg = w->d_latent - E, DL = w->d_latent;
@@ -994,33 +1025,28 @@ int occ4d_decoder_query_fwd_f32(const occ4d_decoder_weights* w, const float*, co
       const float* qi = queries + (int64_t)i * qs;
       // D2 + D3: 8 nearest abstract points by Euclidean norm, inverse-distance interpolation (model/implicit.py:328-342)
       int32_t i8[16], ia[16];
-      float d8[16], w8[16];
-      if (knn_local) {
-        for (int j = 0; j < kl; ++j) {
-          i8[j] = std::min(std::max(knn_local[(int64_t)i * kl + j], 0), m - 1);
-          d8[j] = dist_metric(qi, xyz + 3 * (int64_t)i8[j], 1);
-        }
+      float w8[16];
+      if (pre) {
+        std::copy(pre->idx_local + (int64_t)i * kl, pre->idx_local + (int64_t)(i + 1) * kl, i8);
+        std::copy(pre->w_local + (int64_t)i * kl, pre->w_local + (int64_t)(i + 1) * kl, w8);
       } else {
-        knn_one(qi, xyz, 3, m, kl, 1, i8, d8);
+        local_list_one(qi, xyz, m, kl, knn_local ? knn_local + (int64_t)i * kl : nullptr, i8, w8);
       }
-      float ws = 0.f;
-      for (int j = 0; j < kl; ++j) { w8[j] = 1.f / (d8[j] + 1e-4f); ws += std::fabs(w8[j]); }
-      ws = std::max(ws, 1e-12f);
       for (int c = 0; c < dg; ++c) fq[c] = fglobal[c];                     // [global | local]                (:342)
       for (int c = 0; c < E; ++c) {
         float s = 0.f;
-        for (int j = 0; j < kl; ++j) s += (w8[j] / ws) * feats[(int64_t)i8[j] * E + c];
+        for (int j = 0; j < kl; ++j) s += w8[j] * feats[(int64_t)i8[j] * E + c];
         fq[dg + c] = s;
       }
       // one kNN_torch serves every cross layer (same coordinates, same K)   (model/point_transformer_layer.py:167)
       if (w->n_cross) {
-        if (knn_cross) for (int j = 0; j < kc; ++j) ia[j] = std::min(std::max(knn_cross[(int64_t)i * kc + j], 0), m - 1);
+        if (pre) std::copy(pre->idx_cross + (int64_t)i * kc, pre->idx_cross + (int64_t)(i + 1) * kc, ia);
+        else if (knn_cross) for (int j = 0; j < kc; ++j) ia[j] = std::min(std::max(knn_cross[(int64_t)i * kc + j], 0), m - 1);
         else knn_one(qi, xyz, 3, m, kc, 0, ia, nullptr);
       }
       // D5 + lin_in (:405-408)
-      if (w->n_freq > 0) occ4d_posenc_f32(qi, qs, 1, w->d_in, w->n_freq, (double)w->base_frequency, pe.data(), P, nullptr);
-      else std::copy(qi, qi + w->d_in, pe.begin());
-      matvec(w->lin_in_w, w->lin_in_ld, w->lin_in_b, pe.data(), H, P, x.data());
+      if (pre && pre->x0) std::copy(pre->x0 + (int64_t)i * pre->ld_x0, pre->x0 + (int64_t)i * pre->ld_x0 + H, x.begin());
+      else embed_one(w, qi, qs, pe.data(), x.data());
       int next_cross = 0;
       for (int bl = 0; bl < w->n_blocks; ++bl) {
         matvec(w->lin_z_w[bl], DL, w->lin_z_b[bl], fq.data(), H, DL, t.data());                    // x += lin_z[i](features_query)   (:416-417)
@@ -1048,6 +1074,53 @@ int occ4d_decoder_query_fwd_f32(const occ4d_decoder_weights* w, const float*, co
     }
   }
   return OCC4D_OK;
+}
+
+int occ4d_decoder_query_fwd_f32(const occ4d_decoder_weights* w, const float*, const float* scene, int m, const float* queries,
+                                int64_t qs, int n, const int32_t* knn_local, const int32_t* knn_cross, float* out, int64_t ld_out,
+                                float* penult, int64_t ld_pen, float*, int, occ4d_launch_events* ev, void*) {
+  const char* who = "occ4d_decoder_query_fwd_f32";
+  OCC4D_TRY(check_decoder(w, who));
+  OCC4D_REQUIRE(scene && queries && out && n >= 0 && m >= w->k_local && (w->n_cross == 0 || m >= w->k_cross), "%s: bad arguments", who);
+  if (ev) ev->used = 0;
+  return decoder_rows(w, scene, m, queries, qs, n, knn_local, knn_cross, nullptr, out, ld_out, penult, ld_pen);
+}
+
+// ---- the query prelude (csrc/path.hip; argument contracts shared through csrc/decoder_math.hpp)
+int64_t occ4d_decoder_query_prelude_workspace_floats(const occ4d_decoder_weights* w, int n, int) { return w && n >= 0 ? 64 : -1; }
+int occ4d_decoder_query_prelude_f32(const occ4d_decoder_weights* w, const float* xyz, int m, const float* queries, int64_t qs, int n,
+                                    int32_t* idx_local, float* w_local, int32_t* idx_cross, float* x0, int64_t ld_x0,
+                                    float* workspace, void*) {
+  OCC4D_TRY(check_decoder(w, "occ4d_decoder_query_prelude_f32"));
+  bool empty = false;
+  OCC4D_TRY(occ4d_decoder::check_query_prelude(w, xyz, m, queries, qs, n, idx_local, w_local, idx_cross, x0, ld_x0, workspace, &empty));
+  if (empty) return OCC4D_OK;
+  const int kl = w->k_local, kc = w->k_cross;
+#pragma omp parallel
+  {
+    std::vector<float> pe((size_t)std::max(w->d_in * (2 * w->n_freq + 1), 1));
+#pragma omp for schedule(dynamic, 64)
+    for (int i = 0; i < n; ++i) {
+      const float* qi = queries + (int64_t)i * qs;
+      local_list_one(qi, xyz, m, kl, nullptr, idx_local + (int64_t)i * kl, w_local + (int64_t)i * kl);
+      if (w->n_cross) knn_one(qi, xyz, 3, m, kc, 0, idx_cross + (int64_t)i * kc, nullptr);
+      if (x0) embed_one(w, qi, qs, pe.data(), x0 + (int64_t)i * ld_x0);
+    }
+  }
+  return OCC4D_OK;
+}
+int occ4d_decoder_query_fwd_prelude_f32(const occ4d_decoder_weights* w, const float* prepared, const float* scene, int m,
+                                        const float* queries, int64_t qs, int n, const int32_t* idx_local, const float* w_local,
+                                        const int32_t* idx_cross, float* x0, int64_t ld_x0, float* out, int64_t ld_out,
+                                        float* penult, int64_t ld_pen, float* workspace, int, occ4d_launch_events* ev, void*) {
+  OCC4D_TRY(check_decoder(w, "occ4d_decoder_query_fwd_prelude_f32"));
+  if (ev) ev->used = 0;
+  bool empty = false;
+  OCC4D_TRY(occ4d_decoder::check_query_fwd_prelude(w, prepared, scene, m, queries, qs, n, idx_local, w_local, idx_cross, x0, ld_x0,
+                                                   out, ld_out, penult, ld_pen, workspace, &empty));
+  if (empty) return OCC4D_OK;
+  const QueryPrelude pre{idx_local, w_local, idx_cross, x0, ld_x0};
+  return decoder_rows(w, scene, m, queries, qs, n, nullptr, nullptr, &pre, out, ld_out, penult, ld_pen);
 }
 
 }  // extern "C"

@@ -92,16 +92,20 @@ def sharded_inference(pcl_input, points_query, pcl_net, implicit_net, batch_size
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     device = points_query.device
+    lo, hi = shard_bounds(points_query.shape[0], rank, world)
+    prelude = None
     if encoded is None:
+        if world == 1:        # one GPU: the decode's query front end goes out first, beside the encoder's sampling chain
+            prelude = inference.QueryPrelude.start(pcl_input, points_query, lo, hi, pcl_net, implicit_net)
         shape = abstract_shape(pcl_net, pcl_input.shape[1])
         pcl_abstract, features_global = encode_and_share(pcl_input, pcl_net, shape, pcl_net.global_dim, device,
                                                          timing=timing)
     else:
         pcl_abstract, features_global = encoded
-    lo, hi = shard_bounds(points_query.shape[0], rank, world)
     out = torch.empty((hi - lo, implicit_net.d_out), dtype=torch.float32, device=device)
     if points_query.is_cuda:
-        inference.decode_batches(implicit_net, points_query, lo, hi, batch_size, pcl_abstract, features_global, out)
+        inference.decode_batches(implicit_net, points_query, lo, hi, batch_size, pcl_abstract, features_global, out,
+                                 prelude=prelude)
     else:   # CPU stand-ins (gloo test of the sharding logic): plain loop, no streams
         for b in range(lo, hi, batch_size):
             e = min(hi, b + batch_size)

@@ -12,6 +12,8 @@ per-scene constant (global half + bias) plus the inverse-distance interpolation 
 per-abstract-point table W_z^local f_j, because the interpolation is linear; per-scene
 tables are computed once per abstract cloud, not once per call.
 """
+import os
+
 import torch
 
 from . import geometry  # noqa: F401  (same module graph as the reference)
@@ -33,6 +35,10 @@ def positional_encode(points, base_frequency, num_powers):
 
 
 ACTIVATIONS = {'relu': 1, 'swish': 2}       # act_in codes of occ4d_linear_f32 (0 = none); swish = x * sigmoid(x) (:46-64)
+
+# LocalPclResnetFC.query_prelude keeps lin_in's output of ALL queries (n * d_hidden * 4 bytes) only up to this many bytes;
+# above, the prelude leaves the lists and weights and every mini-batch embeds its own rows.  4 GiB: the 2.1 M-query grid (3.5 GB)
+PRELUDE_X0_MAX = int(os.environ.get('OCC4D_PRELUDE_X0_MAX', str(4 << 30)))
 
 
 def _check_activation(name):
@@ -333,18 +339,60 @@ class LocalPclResnetFC(ResnetFC, kernels.HasKernelSelection):
         return (output, penult)
 
     def forward_output_only(self, points_query, points_abstract, features_global, features_abstract, out,
-                            knn_local=None, knn_cross=None):
+                            knn_local=None, knn_cross=None, prelude=None):
         """Extension for the device-resident driver (inference.decode_batches): the raw outputs of one mini-batch
         written straight into `out` (a row slice of the caller's result tensor); the penultimate activation, which
-        perform_inference discards (eval/inference.py:211), is not materialised for the caller."""
+        perform_inference discards (eval/inference.py:211), is not materialised for the caller.  `prelude`: (buffers of
+        query_prelude over a query tensor, first row, end row) -- points_query is that tensor's [first:end] slice and the
+        searches, the weights and the embedding of these rows are taken from the buffers (x0's rows are consumed)."""
         assert not needs_grad(self, points_abstract, features_global, features_abstract)
         assert self.num_local_features > 0 and self._library_path_ok() and points_query.dim() == 2
         with kernels.use(kernels.current(self)):
             sc = self.prepare_scene(points_abstract, features_global, features_abstract)
             w, prepared, flags = self.path_weights()
+            if prelude is not None:
+                assert knn_local is None and knn_cross is None
+                buf, b, e = prelude
+                assert buf['m'] == sc['m'] and e - b == points_query.shape[0]
+                ops.decoder_query_fwd_prelude(w, prepared, sc['scene'], sc['m'], points_query, buf['idx_local'][b:e],
+                                              buf['w_local'][b:e], None if buf['idx_cross'] is None else buf['idx_cross'][b:e],
+                                              None if buf['x0'] is None else buf['x0'][b:e], flags, out=out, want_penult=False)
+                return out
             ops.decoder_query_fwd(w, prepared, sc['scene'], sc['m'], points_query, flags, out=out, want_penult=False,
                                   knn_local=knn_local, knn_cross=knn_cross)
         return out
+
+    def query_prelude(self, points_query, xyz_abstract):
+        """The query front end of a whole decode in one pass (occ4d_decoder_query_prelude_f32): the two neighbour lists and
+        the interpolation weights of points_query (n, d_in) over the abstract coordinates xyz_abstract (m, 3), and lin_in's
+        output x0 while n * d_hidden * 4 bytes <= PRELUDE_X0_MAX.  Needs no encoder feature, so inference.QueryPrelude
+        issues it beside the encoder.  The buffers are this module's, one set per device (replaced when n changes), rewritten
+        by the next call, which waits for buffers['released'] when the reader has left an event there (decode_batches does)."""
+        assert points_query.dim() == 2 and points_query.shape[1] == self.d_in and self._library_path_ok()
+        n, dev = points_query.shape[0], points_query.device
+        with kernels.use(kernels.current(self)):
+            w, _, _ = self.path_weights()
+            cache = self.__dict__.setdefault('_prelude_buffers', {})
+            want_x0 = n * self.d_hidden * 4 <= PRELUDE_X0_MAX
+            buf = cache.get(dev)
+            if buf is not None and buf.get('released') is not None:
+                # (the last decode that read the buffers may have run on another stream than this call's)
+                torch.cuda.current_stream().wait_event(buf['released'])
+            if buf is None or buf['n'] != n or (buf['x0'] is not None) != want_x0:
+                cache.pop(dev, None)          # (dropped first: the old set's blocks are free for the new one)
+                del buf
+                buf = cache[dev] = dict(
+                    n=n,
+                    idx_local=torch.empty((n, w.k_local), dtype=torch.int32, device=dev),
+                    w_local=torch.empty((n, w.k_local), dtype=torch.float32, device=dev),
+                    idx_cross=torch.empty((n, w.k_cross), dtype=torch.int32, device=dev) if w.n_cross else None,
+                    x0=torch.empty((n, self.d_hidden), dtype=torch.float32, device=dev) if want_x0 else None,
+                    workspace=torch.empty((ops.decoder_query_prelude_workspace(w, n),), dtype=torch.float32, device=dev)
+                    if want_x0 else None)
+            buf['m'] = xyz_abstract.shape[0]
+            ops.decoder_query_prelude(w, xyz_abstract, points_query, buf['idx_local'], buf['w_local'], buf['idx_cross'],
+                                      buf['x0'], buf['workspace'])
+        return buf
 
     # -- training path (as-written op order, differentiable kernels) ------------------------
     def _forward_train(self, points_query, points_abstract, features_global, features_abstract, knn_local=None,

@@ -500,14 +500,17 @@ def infer_device(pcl_input, points_query, pcl_net, implicit_net, batch_size, col
     features_global (D)).  squash=False: implicit_output holds the network's RAW outputs (the caller squashes).
     refine: a GridRefine for points_query = the (nx, ny, nz) = `grid_counts` grid: two decode passes and the expansion stand
     in for the dense decode (decode_refined), and the result gains 'refine' = dict(n_queries, n_decoded)."""
+    n = points_query.shape[0]
+    prelude = None
     if encoded is not None:
         (pcl_abstract, features_global) = encoded
     else:
+        if neighbour_lists is None and refine is None:
+            prelude = QueryPrelude.start(pcl_input, points_query, 0, n, pcl_net, implicit_net)
         (pcl_abstract, features_global, _) = pcl_net(pcl_input, False)
         if pcl_abstract is not None:
             pcl_abstract = pcl_abstract.squeeze(0)
         features_global = features_global.squeeze(0)
-    n = points_query.shape[0]
     out = torch.empty((n, implicit_net.d_out), dtype=torch.float32, device=points_query.device)
     lists = None
     if neighbour_lists is not None:
@@ -516,7 +519,8 @@ def infer_device(pcl_input, points_query, pcl_net, implicit_net, batch_size, col
     codes = squash_codes(implicit_net.d_out, color_mode, predict_segmentation, track_mode, semantic_classes)
     res = dict(implicit_output=out, pcl_abstract=pcl_abstract, features_global=features_global)
     if refine is None:
-        decode_batches(implicit_net, points_query, 0, n, batch_size, pcl_abstract, features_global, out, lists=lists)
+        decode_batches(implicit_net, points_query, 0, n, batch_size, pcl_abstract, features_global, out, lists=lists,
+                       prelude=prelude)
     else:
         assert lists is None and grid_counts is not None, 'refine: no neighbour_lists, and the grid counts of points_query'
         res['refine'] = decode_refined(implicit_net, points_query, grid_counts, refine, batch_size, pcl_abstract,
@@ -639,41 +643,87 @@ def decode_chunk(batch_size):
     return batch_size
 
 
-def _decode_into(implicit_net, q, pcl_abstract, features_global, out_rows, lists=None):
+def _decode_into(implicit_net, q, pcl_abstract, features_global, out_rows, lists=None, prelude=None):
     """One mini-batch: the network's raw outputs written into `out_rows`.  The library-backed decoder writes them in
     place and skips the penultimate activation perform_inference discards (eval/inference.py:211); any other module
-    with the reference's forward signature is called as the reference calls it."""
+    with the reference's forward signature is called as the reference calls it.  `prelude`: (buffers, first row, end row)
+    of a QueryPrelude for these very queries."""
     direct = getattr(implicit_net, 'forward_output_only', None)
     kw = {} if lists is None else dict(knn_local=lists[0], knn_cross=lists[1])
     if direct is not None and getattr(implicit_net, 'num_local_features', 0) > 0 and q.dim() == 2 and q.shape[0] > 0:
+        if prelude is not None:
+            kw['prelude'] = prelude
         direct(q, pcl_abstract, features_global, None, out_rows, **kw)
         return
+    assert prelude is None
     (o, _) = implicit_net(q, pcl_abstract, features_global, None, **kw)
     out_rows.copy_(o)
 
 
+class QueryPrelude:
+    """The decode's query front end issued BEFORE the encoder: the searches, the interpolation
+    weights and lin_in of points_query[lo:hi] need the abstract cloud's coordinates only, and those exist a few hundred
+    microseconds into the encoder's sampling chain (PointCompletionNetV3.abstract_xyz_early) -- so one native pass over all
+    rows (LocalPclResnetFC.query_prelude) runs on a side stream while the rest of that single-workgroup chain would leave
+    the device empty.  Order of issue: start() (early coordinates + the pass, both on the side stream), then the encoder,
+    then decode_batches(prelude=...), whose mini-batches wait for `done`.  Ordering is by stream events only.
+    start() returns None wherever the path does not apply (kernels.Selection.query_prelude off, host tensors or the CPU
+    twin, a decoder without the library path, an encoder whose sampling is not the deterministic nested chain); the
+    decode then runs its front end per mini-batch as before."""
+
+    def __init__(self, buffers, lo, hi, done):
+        self.buffers, self.lo, self.hi, self.done = buffers, lo, hi, done
+
+    @classmethod
+    def start(cls, pcl_input, points_query, lo, hi, pcl_net, implicit_net):
+        if not (kernels.scope().query_prelude and hi > lo and torch.is_tensor(pcl_input) and pcl_input.is_cuda
+                and points_query.is_cuda and points_query.dim() == 2 and hasattr(pcl_net, 'abstract_xyz_early')
+                and hasattr(implicit_net, 'query_prelude') and getattr(implicit_net, 'num_local_features', 0) > 0
+                and implicit_net._library_path_ok() and not ops._lib.is_twin()
+                and not implicit.needs_grad(implicit_net) and not implicit.needs_grad(pcl_net, pcl_input)):
+            return None
+        # (the second decode stream: idle until the second mini-batch, and no further hardware queue)
+        side = side_streams(points_query.device, 'decode', 2)[1]
+        early = pcl_net.abstract_xyz_early(pcl_input, stream=side)      # (waits for the work queued on the current stream:
+        if early is None:                                               #  the last decode that read the buffers is among it)
+            return None
+        xyz, _ = early
+        with torch.cuda.stream(side):
+            buffers = implicit_net.query_prelude(points_query[lo:hi], xyz)
+            done = torch.cuda.Event()
+            done.record(side)
+        return cls(buffers, lo, hi, done)
+
+
 def decode_batches(implicit_net, points_query, lo, hi, batch_size, pcl_abstract, features_global, out, out_offset=0,
-                   lists=None):
+                   lists=None, prelude=None):
     """Runs implicit_net on points_query[lo:hi] in mini-batches of `batch_size` (the reference's
     loop, eval/inference.py:204-246) and writes rows into out[out_offset:].  Mini-batches are
     independent, so consecutive ones alternate between `decode_streams` (kernels.Selection) HIP streams: a 32768-query
     batch is exactly one wave of 256 workgroups for the row-tiled kernels, and the next batch's
     kernels fill the tail of the previous one's instead of waiting behind it.  The first batch runs
     on the caller's stream so the per-scene tables are built (and cached) before the side streams
-    start."""
+    start.  `prelude`: the QueryPrelude started for exactly these rows, or None."""
     batch_size = decode_chunk(batch_size)
     starts = list(range(lo, hi, batch_size))
     n_streams = kernels.scope().decode_streams if points_query.is_cuda else 1      # (host tensors: the explicit CPU twin)
     main = torch.cuda.current_stream() if points_query.is_cuda else None
     side = side_streams(points_query.device, 'decode', n_streams) if n_streams > 1 and len(starts) > 2 else []
+    if prelude is not None:
+        assert lists is None and (prelude.lo, prelude.hi) == (lo, hi)
+        main.wait_event(prelude.done)                    # (the side streams wait for `main` behind the first mini-batch)
+
     def rows(b, e):           # the caller's neighbour lists of these queries (rows are indexed like points_query)
         return None if lists is None else tuple(None if a is None else a[b:e] for a in lists)
+
+    def pre(b, e):
+        return None if prelude is None else (prelude.buffers, b - lo, e - lo)
 
     for bi, b in enumerate(starts):
         e = min(hi, b + batch_size)
         if bi == 0 or not side:
             _decode_into(implicit_net, points_query[b:e], pcl_abstract, features_global, out[out_offset + b - lo:out_offset + e - lo],
-                         rows(b, e))
+                         rows(b, e), pre(b, e))
             if bi == 0:
                 for st in side:
                     st.wait_stream(main)
@@ -681,7 +731,9 @@ def decode_batches(implicit_net, points_query, lo, hi, batch_size, pcl_abstract,
         st = side[bi % len(side)]
         with torch.cuda.stream(st):
             _decode_into(implicit_net, points_query[b:e], pcl_abstract, features_global, out[out_offset + b - lo:out_offset + e - lo],
-                         rows(b, e))
+                         rows(b, e), pre(b, e))
     for st in side:
         main.wait_stream(st)
+    if prelude is not None:
+        prelude.buffers['released'] = main.record_event()        # (the next prelude overwrites the buffers behind this)
     return out

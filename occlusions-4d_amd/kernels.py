@@ -54,6 +54,8 @@ class Selection:
                                       # 'none' (backward recomputes a, logits, pe), 'logits' (backward skips GEMM2; + 1.6 GB per
                                       # layer at config 5), 'all' (nothing recomputed; + 6.4 GB per layer)
     decode_streams: int = 2           # inference: HIP streams the decode mini-batches alternate between (1 = the reference's serial loop)
+    query_prelude: bool = True        # inference, one GPU: the decode's query front end (searches, weights, lin_in) for all queries in
+                                      # one pass beside the encoder's sampling chain; False: per mini-batch (A/B)
 
     def __post_init__(self):
         assert self.logit_precision in PRECISIONS, self.logit_precision
@@ -113,7 +115,8 @@ def _from_environment():
         stored_attention_form=os.environ.get('OCC4D_STORED_ATTENTION_FORM', 'merged'),
         checkpoint_chunk=int(os.environ.get('OCC4D_CHECKPOINT_CHUNK', '32768')),
         store_pairs=os.environ.get('OCC4D_STORE_PAIRS', 'all'),
-        decode_streams=int(os.environ.get('OCC4D_DECODE_STREAMS', '2')))
+        decode_streams=int(os.environ.get('OCC4D_DECODE_STREAMS', '2')),
+        query_prelude=_env_flag('OCC4D_QUERY_PRELUDE', '1'))
 
 
 _DEFAULTS = _from_environment()         # immutable; the environment is read once

@@ -143,6 +143,51 @@ class PointCompletionNetV3(torch.nn.Module):
         self._prefetched = (self.geometry_key(pcl), geom, pcl)
         return geom
 
+    def abstract_level_sizes(self, n_points):
+        """Point counts of the levels that enter the abstract cloud, in pcl_abstract's row order (largest first)."""
+        sizes = [n_points]
+        for _ in range(self.down_blocks):
+            sizes.append(-(-sizes[-1] // self.transition_factor))
+        return sizes[len(sizes) - self.abstract_levels:]
+
+    def abstract_xyz_early(self, pcl, stream=None):
+        """The coordinates forward(pcl) will return in pcl_abstract[..., :3], as an (M, 3) tensor, after a SHORT sampling
+        launch instead of the whole chain: -> (xyz, event recorded behind it), or None when they cannot be had early.
+        With the nested levels of DESIGN.md 4 (iv) every level's subset is a prefix of level 0's selection order, so the
+        largest abstract level (531 of 4779 picks for GREATER, 1593 for CARLA's two levels) is what the SAME sampling
+        kernel with the same start index selects when asked for that many samples; the smaller levels follow by
+        modules.NestedFps' index arithmetic and the rows by the library's gather kernel: the chain's own expressions,
+        bit for bit (as long as the picks are distinct points, which the chain's prefix property presumes too).  The
+        launches go to `stream` (default: a stream of this module's own) behind the work queued on the current stream;
+        forward() is not changed and still runs the full chain."""
+        downs = [b for b in self.blocks if isinstance(b, modules.DownTransition)]
+        if (not pcl.is_cuda or pcl.dim() != 3 or pcl.shape[0] != 1 or not modules.NESTED_FPS or not self.output_featurized
+                or any(b.fps_random_start for b in downs) or pcl.shape[1] >= ops.FPS_COOP_MIN_POINTS or pcl.requires_grad
+                or not 1 <= self.abstract_levels <= len(downs)):
+            return None          # (above the single-workgroup sampler's range a second cooperative launch is not worth its spin)
+        sizes = self.abstract_level_sizes(pcl.shape[1])
+        if self._early_stream is None and stream is None:
+            self._early_stream = torch.cuda.Stream()
+        side = stream if stream is not None else self._early_stream
+        main = torch.cuda.current_stream()
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            pos = pcl[0, :, :3].detach()
+            orig, order = ops.fps_auto(pos, sizes[0], start=0, return_order=True)
+            xyz = torch.empty((sum(sizes), 3), dtype=torch.float32, device=pcl.device)
+            at = 0
+            for lv, m in enumerate(sizes):
+                if lv > 0:
+                    _, orig = ops.nested_fps_level(order, orig, m)
+                ops.gather_rows(pos, orig, out=xyz[at:at + m])
+                at += m
+            ev = torch.cuda.Event()
+            ev.record(side)
+        xyz.record_stream(main)
+        return xyz, ev
+
+    _early_stream = None
+
     @staticmethod
     def geometry_key(pcl):
         return (pcl.data_ptr(), pcl._version, tuple(pcl.shape))

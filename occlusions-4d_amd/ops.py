@@ -698,15 +698,15 @@ def nested_fps_level(order, orig, m):
     return pos, nxt
 
 
-def gather_rows(src, idx, cols=None):
-    """out[i, :] = src[idx[i], :cols] (cols None = the whole row)."""
+def gather_rows(src, idx, cols=None, out=None):
+    """out[i, :] = src[idx[i], :cols] (cols None = the whole row).  `out`: a row-strided (n_out, cols) destination."""
     src, lds = _rows(_dev(src, name='src'), 'src')
     idx = _dev(idx, torch.int32, 'idx').contiguous()
     n_out = idx.numel()
     d = src.shape[1] if cols is None else int(cols)
     assert 0 < d <= src.shape[1]
-    out = torch.empty((n_out, d), dtype=torch.float32, device=src.device)
-    _lib.check(_lib.lib().occ4d_gather_rows_f32(_ptr(src), lds, _ptr(idx), n_out, d, _ptr(out), d, _stream()))
+    out, ldo = _out(out, (n_out, d), src.device)
+    _lib.check(_lib.lib().occ4d_gather_rows_f32(_ptr(src), lds, _ptr(idx), n_out, d, _ptr(out), ldo, _stream()))
     return out
 
 
@@ -1050,6 +1050,70 @@ def decoder_query_fwd(w, prepared, scene, m, queries, flags=0, out=None, penult=
     _lib.check(_lib.lib().occ4d_decoder_query_fwd_f32(
         C.byref(w), _ptr(prepared), _ptr(scene), m, _ptr(q), qs, n, _ptr(kl), _ptr(kc), _ptr(o), ldo, _ptr(penult), ldp,
         _ptr(ws), flags, ev, _stream()))
+    finish()
+    return o, penult
+
+
+def _check_prelude_rows(w, n, idx_local, w_local, idx_cross):
+    """The prelude's per-query rows: contiguous (n, k_local) int32 / fp32 and (n, k_cross) int32 (None without cross layers)."""
+    for t, k, dt, name in ((idx_local, w.k_local, torch.int32, 'idx_local'), (w_local, w.k_local, torch.float32, 'w_local'),
+                           (idx_cross, w.k_cross, torch.int32, 'idx_cross')):
+        if t is None:
+            assert name == 'idx_cross' and w.n_cross == 0, name + ' is required'
+            continue
+        assert _dev(t, dt, name).is_contiguous() and tuple(t.shape) == (n, k), '%s must be a contiguous (%d, %d) tensor' % (name, n, k)
+
+
+def decoder_query_prelude(w, xyz, queries, idx_local, w_local, idx_cross, x0=None, workspace=None):
+    """occ4d_decoder_query_prelude_f32: the neighbour lists and interpolation weights of ALL `queries` (n, d_in) against the
+    abstract coordinates xyz (m, 3), and with `x0` (n, d_hidden) lin_in(posenc(queries)), written into the caller's buffers
+    (idx_local (n, k_local) int32, w_local (n, k_local), idx_cross (n, k_cross) int32 or None without cross layers).  Needs
+    neither the prepared weights nor the per-scene tables.  `workspace`: at least decoder_query_prelude_workspace(w, n)
+    floats, only with x0."""
+    q, qs = _rows(_dev(queries, name='points_query'), 'points_query')
+    n = q.shape[0]
+    xyz = _dev(xyz, name='points_abstract')
+    assert xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.is_contiguous(), 'points_abstract must be a packed (m, 3) tensor'
+    _check_prelude_rows(w, n, idx_local, w_local, idx_cross)
+    ld0 = 0
+    if x0 is not None:
+        x0, ld0 = _out(x0, (n, w.d_hidden), q.device, name='x0')
+        assert workspace is not None and workspace.numel() >= decoder_query_prelude_workspace(w, n)
+    _lib.check(_lib.lib().occ4d_decoder_query_prelude_f32(
+        C.byref(w), _ptr(xyz), xyz.shape[0], _ptr(q), qs, n, _ptr(idx_local), _ptr(w_local), _ptr(idx_cross), _ptr(x0), ld0,
+        _ptr(workspace if x0 is not None else None), _stream()))
+
+
+def decoder_query_prelude_workspace(w, n, with_x0=True):
+    count = int(_lib.lib().occ4d_decoder_query_prelude_workspace_floats(C.byref(w), int(n), 1 if with_x0 else 0))
+    if count < 0:
+        _lib.check(_lib.EINVAL)
+    return count
+
+
+def decoder_query_fwd_prelude(w, prepared, scene, m, queries, idx_local, w_local, idx_cross, x0=None, flags=0, out=None,
+                              penult=None, want_penult=True):
+    """occ4d_decoder_query_fwd_prelude_f32 on one mini-batch: decoder_query_fwd with the prelude's rows of these queries
+    (decoder_query_prelude) in place of the searches, the weights and -- with x0 -- the embedding.  x0's rows are consumed."""
+    q, qs = _rows(_dev(queries, name='points_query'), 'points_query')
+    n = q.shape[0]
+    _check_prelude_rows(w, n, idx_local, w_local, idx_cross)
+    ld0 = 0
+    if x0 is not None:
+        x0, ld0 = _out(x0, (n, w.d_hidden), q.device, name='x0')
+    o, ldo = _out(out, (n, w.d_out), q.device)
+    ldp = 0
+    if penult is not None or want_penult:
+        penult, ldp = _out(penult, (n, w.d_hidden), q.device, name='penult')
+    ws = _sized(_lib.lib().occ4d_decoder_query_workspace_floats, C.byref(w), n, m, flags, device=q.device)
+    d, k = w.d_hidden, w.k_cross
+    fused = (w.n_cross > 0 and d in FUSED_ATTN_DIMS and k <= FUSED_ATTN_MAX_K and w.cross[0].pos_hidden == 32
+             and not (flags & _lib.PATH_UNFUSED))
+    attn = [('cross_attn', dict(k=k, d=d), lambda c: _attn_flops(c, k, d), w.n_cross)] if fused else []
+    ev, finish = _path_events(n, attn + [('resblock', {}, lambda c: 4.0 * c * d * d, w.n_blocks)])
+    _lib.check(_lib.lib().occ4d_decoder_query_fwd_prelude_f32(
+        C.byref(w), _ptr(prepared), _ptr(scene), m, _ptr(q), qs, n, _ptr(idx_local), _ptr(w_local), _ptr(idx_cross), _ptr(x0),
+        ld0, _ptr(o), ldo, _ptr(penult), ldp, _ptr(ws), flags, ev, _stream()))
     finish()
     return o, penult
 
