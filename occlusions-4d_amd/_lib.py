@@ -36,6 +36,13 @@ EXTENSION_HEADERS = {
 STRUCT_EXTENSION_HEADERS = {
     'PRELUDE': 'ext/occ4d_prelude.h',   # the decoder's query prelude (inference.QueryPrelude, LocalPclResnetFC.query_prelude)
 }
+# The three tables above are pinned by the suite row for row.  ADDON_HEADERS is OPEN BY DESIGN: every later header of include/ext/
+# is a row here (parsed with occ4d.h's structs, so a prototype may use them or not): the same <PREFIX>_HEADER_PATH / _SIGNATURES /
+# _CONSTANTS attributes, its symbols in ADDON_SIGNATURES, which bind() covers too.  A test of a header checks that its symbols are
+# IN the table and in none of the other three, never that the table equals them.
+ADDON_HEADERS = {
+    'COMPONENTS': 'ext/occ4d_components.h',     # the connected components of the solid set (components.py, perform_inference(components=...))
+}
 
 
 class NativeLibraryError(RuntimeError):
@@ -203,6 +210,19 @@ for _prefix, _name in STRUCT_EXTENSION_HEADERS.items():
     STRUCT_EXTENSION_SIGNATURES.update(_table)
     globals().update({_prefix + '_HEADER_PATH': _path, _prefix + '_SIGNATURES': _table})
 
+# ... and the open table
+ADDON_SIGNATURES = {}
+for _prefix, _name in ADDON_HEADERS.items():
+    _path = os.path.join(INCLUDE, *_name.split('/'))
+    _text = _read_header(_path)
+    _table = parse_prototypes(_text, _STRUCTS)
+    _twice = sorted(set(_table) & (set(ALL_SIGNATURES) | set(EXTENSION_SIGNATURES) | set(STRUCT_EXTENSION_SIGNATURES) | set(ADDON_SIGNATURES)))
+    if _twice or _prefix in FEATURE_HEADERS or _prefix in EXTENSION_HEADERS or _prefix in STRUCT_EXTENSION_HEADERS:
+        raise NativeLibraryError('include/%s declares %s, which another header declares too' % (_name, ', '.join(_twice) or _prefix))
+    ADDON_SIGNATURES.update(_table)
+    globals().update({_prefix + '_HEADER_PATH': _path, _prefix + '_SIGNATURES': _table,
+                      _prefix + '_CONSTANTS': {k[len(_prefix) + 1:]: v for k, v in parse_constants(_text).items()}})
+
 _lib = None
 _twin = False            # True only after an explicit load_cpu_twin(): host pointers, no streams (cpu_twin.py)
 
@@ -212,10 +232,10 @@ def is_twin():
 
 
 def bind(handle, missing=None):
-    """Sets restype / argtypes of every symbol of ALL_SIGNATURES and the two extension tables on a loaded library and returns it.  A symbol the library does
+    """Sets restype / argtypes of every symbol of ALL_SIGNATURES, the two extension tables and ADDON_SIGNATURES on a loaded library and returns it.  A symbol the library does
     not export is a stale library (NativeLibraryError) unless `missing` is given: then missing(name) stands in for it."""
     for name, (res, args) in (list(ALL_SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items())
-                              + list(STRUCT_EXTENSION_SIGNATURES.items())):
+                              + list(STRUCT_EXTENSION_SIGNATURES.items()) + list(ADDON_SIGNATURES.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError:

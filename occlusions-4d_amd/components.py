@@ -1,0 +1,92 @@
+"""The connected components of the decoded occupancy on the dense query grid, on the device (include/ext/occ4d_components.h):
+how many separate objects the predicted solid set holds and where each one is, from ONE decode.
+
+perform_inference(components=Components()) adds result['components'] = dict(labels (N,) int32, table (K, 12) int64): per query
+the number of its component (-1: air, or a component smaller than min_size), per component its size, root (lowest flat index),
+class, and the sums, minima and maxima of its integer grid coordinates.  Components are numbered in the order of their roots; with
+connectivity 6 / 18 / 26, min_size 1 and no classes that is scipy.ndimage.label's numbering minus one.
+
+    res = perform_inference(..., point_sample_mode='grid', components=Components(min_size=20))
+    frame = geometry.grid_frame(num_sample, min_z, cube_bounds, data_kind, cube_mode)        # counts, mins, spacings
+    objects = boxes_and_centroids(res['components']['table'], frame[1], frame[2])
+
+The table holds integers only, so it is the same bit for bit under any scheduling; world-space centroids and boxes are made from
+it on the host in float64 (boxes_and_centroids)."""
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+CONNECTIVITIES = (6, 18, 26)
+
+
+class Components:
+    """The option object of perform_inference(components=...) / evaluate_clip(components=...).  level: the density from which a
+    query is solid (density >= level, the comparison of the solid split), None = the call's density_threshold; connectivity: 6, 18
+    or 26; select = (column, threshold) or None: members also need implicit_output[:, column] >= threshold (with the track
+    channel: the tracked object alone); by_class: neighbours must share their semantic class (the argmax of the semantic columns,
+    first maximum wins; needs predict_segmentation); min_size: components of fewer points are dropped."""
+
+    def __init__(self, level=None, connectivity=6, select=None, by_class=False, min_size=1):
+        if level is not None:
+            level = float(level)
+            if level != level:
+                raise ValueError('Components: level is NaN')
+        if isinstance(connectivity, bool) or connectivity not in CONNECTIVITIES:
+            raise ValueError('Components: connectivity = %r must be 6, 18 or 26' % (connectivity,))
+        if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)) or not 1 <= min_size <= 2 ** 31 - 1:
+            raise ValueError('Components: min_size = %r must be an integer >= 1' % (min_size,))
+        self.level, self.connectivity, self.min_size, self.by_class = level, int(connectivity), int(min_size), bool(by_class)
+        self.select = None if select is None else (int(select[0]), float(select[1]))
+
+    def resolve(self, density_threshold):
+        level = float(density_threshold) if self.level is None else self.level
+        if level != level:
+            raise ValueError('Components: level is NaN')
+        return level
+
+    def __repr__(self):
+        return 'Components(level=%r, connectivity=%d, select=%r, by_class=%r, min_size=%d)' % (
+            self.level, self.connectivity, self.select, self.by_class, self.min_size)
+
+
+def label(implicit_output, counts, level, connectivity=6, select=None, klass=None, min_size=1, channel=0):
+    """The components of column `channel` of a dense (N, G) output on the (nx, ny, nz) = `counts` grid at `level`.  select =
+    (column, threshold): the mask column; klass (N,) int32 or None.  -> (labels (N,) int32, table (K, 12) int64) on the device; one
+    12-byte device->host read (the totals) sizes the table."""
+    level = float(level)
+    if level != level:
+        raise ValueError('components.label: level is NaN')
+    out = implicit_output
+    assert out.dim() == 2 and 0 <= channel < out.shape[1], 'channel = %r' % (channel,)
+    mask, mask_level = None, 0.0
+    if select is not None:
+        column, mask_level = int(select[0]), float(select[1])
+        assert 0 <= column < out.shape[1], 'select column = %r' % (column,)
+        mask = out[:, column]
+    labels, _, table = ops.grid_components(out[:, channel], counts, level, connectivity, min_size, mask, mask_level, klass)
+    return labels, table
+
+
+def semantic_class(implicit_output, first, n_classes):
+    """(N,) int32: the argmax of columns first .. first + n_classes - 1, the first maximum wins (the rule of compress_air)."""
+    assert 0 <= first and first + n_classes <= implicit_output.shape[1] and n_classes >= 1, \
+        'semantic columns %d .. %d of %d' % (first, first + n_classes - 1, implicit_output.shape[1])
+    return torch.argmax(implicit_output[:, first:first + n_classes], dim=1).to(torch.int32)
+
+
+def boxes_and_centroids(table, mins, spacings):
+    """World-space summary of a component table (K, 12), on the host in float64: dict(size (K,) int64, klass (K,) int64, centroid
+    (K, 3), box_min (K, 3), box_max (K, 3): the centres of the box's corner points).  Point i of axis a lies at (i + 0.5) *
+    spacing_a + origin_a, so the centroid is (sum_a / size + 0.5) * spacing_a + origin_a."""
+    t = np.asarray(table.cpu() if hasattr(table, 'cpu') else table)
+    assert t.ndim == 2 and t.shape[1] == _lib.COMPONENTS_CONSTANTS['COLS'], 'table must be (K, 12), got %s' % (t.shape,)
+    t = t.astype(np.int64, copy=False)
+    origin, spacing = np.asarray(mins, np.float64).reshape(3), np.asarray(spacings, np.float64).reshape(3)
+    size = t[:, 0]
+
+    def world(index):
+        return (index + 0.5) * spacing + origin
+
+    return dict(size=size.copy(), klass=t[:, 2].copy(), centroid=world(t[:, 3:6].astype(np.float64) / size[:, None].astype(np.float64)),
+                box_min=world(t[:, 6:9].astype(np.float64)), box_max=world(t[:, 9:12].astype(np.float64)))

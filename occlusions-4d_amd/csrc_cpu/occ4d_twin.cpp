@@ -32,6 +32,7 @@
 #include "occ4d_refine.h"
 #include "occ4d_surface.h"
 #include "ext/occ4d_raycast.h"
+#include "ext/occ4d_components.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -42,6 +43,7 @@
 #include "refine_math.hpp"
 #include "surface_math.hpp"
 #include "raycast_math.hpp"
+#include "components_math.hpp"
 #include "decoder_math.hpp"
 
 namespace fe = occ4d_frontend;
@@ -53,6 +55,7 @@ namespace in = occ4d_inst;
 namespace rf = occ4d_refine;
 namespace sf = occ4d_surface;
 namespace ry = occ4d_raycast;
+namespace cc = occ4d_components;
 
 static thread_local char g_err[512] = "";
 
@@ -737,6 +740,55 @@ int occ4d_raycast_grid_f32(const float* field, int64_t ld, int nx, int ny, int n
   for (int v = 0; v < V; ++v)
     for (int py = 0; py < H; ++py)
       for (int px = 0; px < W; ++px) ry::pixel_item(a, v, px, py);
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- components
+// include/ext/occ4d_components.h: the passes of csrc/components.hip over csrc/components_math.hpp, tiles and points in order, the
+// atomics spelled as plain memory operations (one thread).  A kept root's number is its tile's prefix + its rank in the tile.
+int occ4d_components_label_f32(const float* field, int64_t ld, float level, const float* mask, int64_t ld_mask, float mask_level,
+                               const int32_t* klass, int nx, int ny, int nz, int connectivity, int min_size, int32_t* work,
+                               int32_t* labels, int32_t* totals, void*) {
+  cc::LabelArgs a; bool empty;
+  OCC4D_TRY(cc::check_label(field, ld, level, mask, ld_mask, mask_level, klass, nx, ny, nz, connectivity, min_size, work, labels, totals,
+                            empty, a));
+  if (empty) return OCC4D_OK;
+  const cc::Grid& g = a.grid;
+  int32_t s_parent[256], s_key[256];
+  for (int64_t tile = 0; tile < g.local_tiles; ++tile) {                  // pass 1: its three steps, a barrier = the end of a loop
+    for (int t = 0; t < 256; ++t) cc::local_init(a, cc::local_point(g, tile, t), t, s_parent, s_key);
+    for (int t = 0; t < 256; ++t) cc::local_link<cc::Plain>(a, cc::local_point(g, tile, t), t, s_parent, s_key);
+    for (int t = 0; t < 256; ++t) cc::local_write<cc::Plain>(a, g, tile, cc::local_point(g, tile, t), t, s_parent);
+  }
+  for (int64_t p = 0; p < g.points; ++p) cc::border_item<cc::Plain>(a, p);                    // pass 2
+  for (int64_t p = 0; p < g.points; ++p) {                                                    // pass 3
+    const int r = cc::flatten_item(a, p);
+    if (r >= 0) a.size[r] += 1;
+  }
+  int32_t sums[3] = {0, 0, 0};
+  for (int64_t tile = 0; tile < g.number_tiles; ++tile) {                 // passes 4 to 6: counts, exclusive prefixes, numbers
+    a.kept_roots[tile] = sums[0];
+    a.kept_points[tile] = sums[1];
+    a.all_roots[tile] = sums[2];
+    for (int64_t p = tile * cc::TILE; p < std::min(g.points, (tile + 1) * cc::TILE); ++p) {
+      if (cc::is_kept_root(a, p)) a.parent[p] = sums[0]++;               // (parent[p] is read by no test of this loop)
+      sums[1] += cc::is_kept_point(a, p);
+      sums[2] += cc::is_root(a, p);
+    }
+  }
+  for (int c = 0; c < 3; ++c) totals[c] = sums[c];
+  for (int64_t p = 0; p < g.points; ++p) cc::label_item(a, p);                                // pass 7
+  return OCC4D_OK;
+}
+int occ4d_components_table_i64(const int32_t* labels, const int32_t* klass, int nx, int ny, int nz, const int32_t* totals,
+                               int64_t* table, int cap, void*) {
+  cc::TableArgs a; bool empty;
+  OCC4D_TRY(cc::check_table(labels, klass, nx, ny, nz, totals, table, cap, empty, a));
+  if (empty) return OCC4D_OK;
+  const int rows = cc::table_rows(a);
+  for (int k = 0; k < rows; ++k) cc::table_init_row(a, k);
+  for (int64_t p = 0; p < a.grid.points; ++p)                             // one contribution per point: a run of one
+    if (labels[p] >= 0) cc::table_add<cc::PlainTable>(a, labels[p], rows, cc::contribution_of(a, p));
   return OCC4D_OK;
 }
 

@@ -325,7 +325,7 @@ def occlusion_groups(live_occl_row, valo_ids_pad, num_valo_ids, n_ids, edges=(0.
 
 def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt=False, reuse_encode=True, stats=None,
                   stats_group_fn=None, stats_occlusion=None, inst_stats=None, inst_group_fn=None, refine=None, surface=None,
-                  meshes=None, views=None, images=None):
+                  meshes=None, views=None, images=None, components=None, objects=None):
     """batch: dict with 'pcl_input' (1,N,8), 'pcl_input_sem' (1,N,1-3), 'pcl_target' list of (1,T,9-11) tensors and
     batch['meta_data']['pcl_target_size'] (list of (1,) tensors), as the reference's test data loader yields them
     (data/data_greater.py:593-606, data/data_carla.py:651-661).  args: namespace with the test_args fields used
@@ -342,7 +342,11 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
     result['surface'] = dict(vertices, faces) is appended to (the tuples of pcl_all keep their contract).  A surface without
     such a list is a ValueError.
     views: a projection.FieldViews handed to every perform_inference call, or None; `images`: the list every output frame's
-    result['views'] = dict(depth, cell, features) is appended to, in the same way."""
+    result['views'] = dict(depth, cell, features) is appended to, in the same way.
+    components: a components.Components handed to every perform_inference call, or None; `objects`: the list every output frame's
+    result['components'] = dict(labels, table) is appended to, in the same way."""
+    if components is not None and not isinstance(objects, list):
+        raise ValueError('evaluate_clip(components=...) needs objects=<a list>: one dict of labels and table per output frame is appended to it')
     if views is not None and not isinstance(images, list):
         raise ValueError('evaluate_clip(views=...) needs images=<a list>: one dict of images per output frame is appended to it')
     if surface is not None and not isinstance(meshes, list):
@@ -386,7 +390,7 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
             point_occupancy_radius=args.point_occupancy_radius, semantic_classes=args.semantic_classes,
             density_threshold=args.density_threshold, data_kind=data_kind, cube_mode=args.cube_mode, compress_air=True,
             encoded=encoded if reuse_encode else None, return_encoded=reuse_encode, refine=refine, surface=surface, views=views,
-            **stats_kw)
+            components=components, **stats_kw)
         if reuse_encode:                  # (track_mode 'all': a dict with one encode per tracked instance)
             encoded = res.pop('_encoded')
         else:
@@ -395,6 +399,8 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
             meshes.append(res['surface'])
         if views is not None:
             images.append(res['views'])
+        if components is not None:
+            objects.append(res['components'])
         item = (pcl_input_numpy, res['pcl_abstract'], res['output_solid'], frame, res['output_air'])
         if save_gt:
             item = item + (pcl_input_sem_numpy, res['points_query'])

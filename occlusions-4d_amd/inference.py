@@ -21,6 +21,7 @@ from . import model
 from . import ops
 from . import projection
 from . import surface as surface_nets
+from . import components as components_mod
 
 
 def get_track_idx(color_mode):
@@ -182,7 +183,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                       density_threshold=0.5, data_kind='', cube_mode=4, compress_air=False,
                       encoded=None, return_encoded=False, neighbour_lists=None, stats=None, stats_target=None,
                       stats_group=None, track_merge='device', inst_stats=None, inst_group=None, refine=None, surface=None,
-                      views=None):
+                      views=None, components=None):
     """One encode of the input point-cloud video + decode of all query points of one output frame.  Returns
     dict(output_solid, output_air, pcl_abstract, features_global, implicit_output, points_query) of float32 numpy arrays, and
     gt_solid / gt_air when `pcl_target_frame` is given.  The keywords from `encoded` on are extensions whose defaults give the
@@ -230,7 +231,15 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     (V, H, W, C) float32): the same squashed (N, G) array -- merged, expanded -- ray-cast into the cameras on the device
     (projection.render_field, include/ext/occ4d_raycast.h): per pixel the first crossing of density == views.level (None:
     density_threshold), 0 / -1 / 0 where a ray meets none.  No device value is read; the three arrays come back with the others,
-    under the one host wait."""
+    under the one host wait.
+
+    Components.  `components`: a components.Components (level, connectivity, select, by_class, min_size), or None.
+    point_sample_mode 'grid' only (ValueError); by_class needs predict_segmentation (ValueError).  The result gains 'components' =
+    dict(labels (N,) int32, table (K, 12) int64): the connected components of density >= components.level (None:
+    density_threshold) of the same squashed (N, G) array -- merged, expanded --, labelled on the device (components.label,
+    include/ext/occ4d_components.h): per query its component's number or -1, per component size, root, class, coordinate sums,
+    minima and maxima (components.boxes_and_centroids turns them into world-space boxes).  One 12-byte device->host read sizes
+    the table; the two arrays come back with the others, under the one host wait."""
     assert task == 'if'
     assert sample_implicit
     assert track_merge in ('device', 'host'), track_merge
@@ -257,6 +266,15 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         if point_sample_mode != 'grid':
             raise ValueError("views needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
         views_level = views.resolve(density_threshold)
+    components_level = None
+    if components is not None:
+        if not isinstance(components, components_mod.Components):
+            raise ValueError('components must be a components.Components or None, got %r' % (components,))
+        if point_sample_mode != 'grid':
+            raise ValueError("components needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
+        if components.by_class and not predict_segmentation:
+            raise ValueError('components with by_class=True needs predict_segmentation=True')
+        components_level = components.resolve(density_threshold)
     refine_stats = dict(n_queries=0, n_decoded=0)
     output_track_idx = get_track_idx(color_mode)
     input_inst_idx = 0 if data_kind == 'greater' else 1
@@ -332,6 +350,13 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         if views is not None:
             views_h = [copies.fetch(t) for t in views.render(
                 output_dev, *geometry.grid_frame(num_sample, min_z, cube_bounds, data_kind, cube_mode), views_level)]
+        if components is not None:
+            klass = None
+            if components.by_class:
+                klass = components_mod.semantic_class(output_dev, output_dev.shape[1] - semantic_classes, semantic_classes)
+            components_h = [copies.fetch(t) for t in components_mod.label(
+                output_dev, geometry.grid_counts(num_sample, min_z, cube_bounds, data_kind, cube_mode), components_level,
+                components.connectivity, components.select, klass, components.min_size)]
         copies.wait()
         solid, air = copies.result(solid_h), copies.result(air_h)
         points_query = copies.result(points_query)
@@ -345,6 +370,8 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         result['surface'] = dict(vertices=copies.result(mesh_h[0]), faces=copies.result(mesh_h[1]))
     if views is not None:
         result['views'] = dict(zip(('depth', 'cell', 'features'), (copies.result(h) for h in views_h)))
+    if components is not None:
+        result['components'] = dict(labels=copies.result(components_h[0]), table=copies.result(components_h[1]))
     if return_encoded:
         result['_encoded'] = encoded_out[-1] if -1 in encoded_out else encoded_out     # (a tuple for the one unmarked run)
     if gt_available:

@@ -1618,6 +1618,54 @@ def raycast_grid(values, counts, mins, spacings, level, rt_inv, k_inv, height, w
     return depth, cell, feat
 
 
+def components_work_len(n):
+    """Elements of the int32 work array of occ4d_components_label_f32 for n grid points (the formula of the header)."""
+    tile = _lib.COMPONENTS_CONSTANTS['TILE']
+    return 3 * n + 3 * ((n + tile - 1) // tile)
+
+
+def grid_components(values, counts, level, connectivity=6, min_size=1, mask=None, mask_level=0.0, klass=None, cap=None, table=None):
+    """The connected components of the set values >= level of the (nx, ny, nz) = `counts` grid (occ4d_components_label_f32 /
+    occ4d_components_table_i64, the rules in include/ext/occ4d_components.h).  values (n,): one value per grid point, x slowest,
+    z fastest (a strided column view is read in place); mask (n,) with mask_level: a second such column, members also need
+    mask >= mask_level; klass (n,) int32: members need klass >= 0 and neighbours equal classes.  Components of fewer than min_size
+    points are dropped, the others numbered in the order of their lowest flat index.
+    -> (labels (n,) int32, -1 = none; totals (3,) int32: kept components, kept points, all components; table (K, 12) int64, one row
+    per kept component), on the device.  cap=None: one 12-byte device->host read of totals sizes the table, K = totals[0].  cap = an
+    int: no read, K = cap, and only the rows below min(cap, totals[0]) are written.  `table`: a caller's contiguous int64 (>= K, 12)
+    buffer whose first K rows are used (cap required)."""
+    nx, ny, nz = (int(c) for c in counts)
+    n = nx * ny * nz
+    v, ld = _inst_column(values, n, 'values')
+    m, ld_mask = (None, 0) if mask is None else _inst_column(mask, n, 'mask')
+    kl = None
+    if klass is not None:
+        kl = _dev(klass, torch.int32, 'klass')
+        assert tuple(kl.shape) == (n,) and kl.is_contiguous(), 'klass must be a contiguous (%d,) tensor, got %s' % (n, tuple(kl.shape))
+    connectivity, min_size = int(connectivity), int(min_size)
+    # (an empty grid is a no-op of the library: its totals are the zeros put here)
+    scratch = (torch.empty if n else torch.zeros)(components_work_len(n) + 3, dtype=torch.int32, device=v.device)
+    work, totals = scratch[:-3], scratch[-3:]
+    labels = torch.empty((n,), dtype=torch.int32, device=v.device)
+    st = _stream()
+    _lib.check(_lib.lib().occ4d_components_label_f32(_ptr(v), ld, float(level), _ptr(m), ld_mask, float(mask_level), _ptr(kl), nx, ny, nz,
+                                                     connectivity, min_size, _ptr(work), _ptr(labels), _ptr(totals), st))
+    cols = _lib.COMPONENTS_CONSTANTS['COLS']
+    if cap is None:
+        assert table is None, 'a caller\'s table needs cap'
+        cap = int(totals.tolist()[0]) if n else 0
+    cap = int(cap)
+    assert cap >= 0, 'cap = %d must be >= 0' % cap
+    if table is None:
+        table = torch.empty((cap, cols), dtype=torch.int64, device=v.device)
+    else:
+        table = _dev(table, torch.int64, 'table')
+        assert table.dim() == 2 and table.shape[1] == cols and table.shape[0] >= cap and table.is_contiguous(), \
+            'table must be a contiguous (>= %d, %d) tensor, got %s' % (cap, cols, tuple(table.shape))
+    _lib.check(_lib.lib().occ4d_components_table_i64(_ptr(labels), _ptr(kl), nx, ny, nz, _ptr(totals), _ptr(table), cap, st))
+    return labels, totals, table[:cap]
+
+
 def visibility(rows, rt, k, depth, margin):
     """Visibility code of every row under every camera against that camera's depth image (occ4d_visibility_f32): -> (V, n) int32,
     0 visible, 1 occluded (the image holds a depth d > 0 at the row's pixel and depth - d > margin), 2 outside.  depth (V, H, W),
