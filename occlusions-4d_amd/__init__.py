@@ -18,7 +18,7 @@ from . import evaluation  # noqa: F401
 from . import occlusion  # noqa: F401   (valo ids, live occlusion fractions, track id: the id histogram)
 from . import frontend  # noqa: F401   (frames -> clouds on the device: greater_clip / carla_clip)
 from . import projection  # noqa: F401   (clouds -> camera views: projection, z-buffer, visibility codes)
-from . import components  # noqa: F401   (connected components of the decoded occupancy: Components, label, boxes_and_centroids)
+from . import components  # noqa: F401   (connected components of the decoded occupancy: Components, label, boxes_and_centroids; linked across frames: Tracker, tracks)
 from . import cpu_twin  # noqa: F401   (explicit opt-in only: pk.cpu_twin.enable(); never a fallback)
 
 __all__ = ['configs', 'kernels', 'ops', 'point_transformer_layer', 'modules', 'model', 'geometry', 'implicit',

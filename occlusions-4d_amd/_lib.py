@@ -42,6 +42,7 @@ STRUCT_EXTENSION_HEADERS = {
 # IN the table and in none of the other three, never that the table equals them.
 ADDON_HEADERS = {
     'COMPONENTS': 'ext/occ4d_components.h',     # the connected components of the solid set (components.py, perform_inference(components=...))
+    'LINK': 'ext/occ4d_link.h',                 # the components of two frames linked: overlaps, tracks (components.Tracker, perform_inference(tracker=...))
 }
 
 

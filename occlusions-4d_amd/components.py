@@ -75,6 +75,69 @@ def semantic_class(implicit_output, first, n_classes):
     return torch.argmax(implicit_output[:, first:first + n_classes], dim=1).to(torch.int32)
 
 
+class Tracker:
+    """Links the components of consecutive output frames on the device (include/ext/occ4d_link.h): the option object of
+    perform_inference(components=..., tracker=...) / evaluate_clip(..., tracker=...).  Component b of a frame continues component a
+    of the frame before when each is the other's best overlap by intersection over union and that is >= min_iou (a float, or an
+    exact (num, den) pair); it then keeps a's track id, and every other component takes the next free id, in order.
+
+    The previous frame's labels, table and track ids and the id counter stay on the device; add_frame reads nothing back."""
+
+    def __init__(self, min_iou=0.0):
+        num, den = ops._min_iou_fraction(min_iou)
+        if not (1 <= den <= 2 ** 20 and 0 <= num <= den):
+            raise ValueError('Tracker: min_iou = %r must lie in [0, 1]' % (min_iou,))
+        self.min_iou = (num, den)
+        self.reset()
+
+    def reset(self):
+        """Forgets the previous frame and the ids: the next frame numbers its components 0, 1, ..."""
+        self.labels = self.table = self.track = self.next = None
+
+    def add_frame(self, labels, table):
+        """labels (n,) int32, table (K, 12) int64: a frame's components (components.label).  -> link (K, 4) int32 on the device: per
+        component its track id, the component of the previous frame it continues or -1, its best overlap there or -1, and that
+        overlap's number of points."""
+        if self.labels is not None and labels.shape[0] != self.labels.shape[0]:
+            raise ValueError('Tracker.add_frame: labels of %d points after a frame of %d' % (labels.shape[0], self.labels.shape[0]))
+        if self.labels is None:                                               # a first frame: nothing to continue
+            self.labels, self.table = labels, table[:0]
+            self.track = torch.empty((0,), dtype=torch.int32, device=labels.device)
+        if self.next is None:
+            self.next = torch.zeros((1,), dtype=torch.int32, device=labels.device)
+        pairs, totals = ops.components_overlap(self.labels, labels, self.table.shape[0], table.shape[0])
+        link, _, self.next = ops.components_match(pairs, totals, self.table, table, self.track, self.next, self.min_iou)
+        self.labels, self.table, self.track = labels, table, link[:, 0].contiguous()
+        return link
+
+    def n_tracks(self):
+        """The number of track ids handed out so far: the one host read."""
+        return 0 if self.next is None else int(self.next.item())
+
+    def __repr__(self):
+        return 'Tracker(min_iou=(%d, %d))' % self.min_iou
+
+
+def tracks(objects, mins, spacings):
+    """The trajectories, on the host in float64: `objects` is the list evaluate_clip(components=..., objects=[], tracker=...)
+    appended one dict(labels, table, link) per output frame to.  -> {track id: dict(frames (T,) int64, components (T,) int64: the
+    component's number in its frame, size (T,) int64, centroid (T, 3), box_min (T, 3), box_max (T, 3))}, the T frames in order."""
+    rows = {}
+    for t, frame in enumerate(objects):
+        summary = boxes_and_centroids(frame['table'], mins, spacings)
+        link = np.asarray(frame['link'])
+        assert link.ndim == 2 and link.shape == (len(summary['size']), 4), 'link must be (K, 4), got %s' % (link.shape,)
+        for k, track in enumerate(link[:, 0].tolist()):
+            rows.setdefault(track, []).append((t, k, summary['size'][k], summary['centroid'][k], summary['box_min'][k], summary['box_max'][k]))
+    out = {}
+    for track, items in sorted(rows.items()):
+        out[track] = dict(frames=np.array([i[0] for i in items], np.int64), components=np.array([i[1] for i in items], np.int64),
+                          size=np.array([i[2] for i in items], np.int64), centroid=np.array([i[3] for i in items], np.float64).reshape(-1, 3),
+                          box_min=np.array([i[4] for i in items], np.float64).reshape(-1, 3),
+                          box_max=np.array([i[5] for i in items], np.float64).reshape(-1, 3))
+    return out
+
+
 def boxes_and_centroids(table, mins, spacings):
     """World-space summary of a component table (K, 12), on the host in float64: dict(size (K,) int64, klass (K,) int64, centroid
     (K, 3), box_min (K, 3), box_max (K, 3): the centres of the box's corner points).  Point i of axis a lies at (i + 0.5) *

@@ -33,6 +33,7 @@
 #include "occ4d_surface.h"
 #include "ext/occ4d_raycast.h"
 #include "ext/occ4d_components.h"
+#include "ext/occ4d_link.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -44,6 +45,7 @@
 #include "surface_math.hpp"
 #include "raycast_math.hpp"
 #include "components_math.hpp"
+#include "link_math.hpp"
 #include "decoder_math.hpp"
 
 namespace fe = occ4d_frontend;
@@ -56,6 +58,7 @@ namespace rf = occ4d_refine;
 namespace sf = occ4d_surface;
 namespace ry = occ4d_raycast;
 namespace cc = occ4d_components;
+namespace lk = occ4d_link;
 
 static thread_local char g_err[512] = "";
 
@@ -789,6 +792,53 @@ int occ4d_components_table_i64(const int32_t* labels, const int32_t* klass, int 
   for (int k = 0; k < rows; ++k) cc::table_init_row(a, k);
   for (int64_t p = 0; p < a.grid.points; ++p)                             // one contribution per point: a run of one
     if (labels[p] >= 0) cc::table_add<cc::PlainTable>(a, labels[p], rows, cc::contribution_of(a, p));
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- link
+// include/ext/occ4d_link.h: the passes of csrc/link.hip over csrc/link_math.hpp, items in order, the atomics spelled as plain memory
+// operations (one thread); every point is a run of one, and a pair's number is its tile's prefix + its root's rank in the tile.
+int occ4d_link_overlap_i32(const int32_t* labels_a, const int32_t* labels_b, int k_a, int k_b, int64_t n, int32_t* work,
+                           int64_t* pairs, int cap, int32_t* totals, void*) {
+  lk::OverlapArgs a; bool empty;
+  OCC4D_TRY(lk::check_overlap(labels_a, labels_b, k_a, k_b, n, work, pairs, cap, totals, empty, a));
+  if (empty) return OCC4D_OK;
+  for (int64_t i = 0; i < std::max(a.table.slots, n); ++i) lk::clear_item(a, i);              // pass 1
+  int32_t members = 0, numbered = 0;
+  for (int64_t tile = 0; tile < a.tiles; ++tile) {                                            // pass 2
+    a.tile_members[tile] = members;
+    for (int64_t p = tile * lk::TILE; p < std::min(n, (tile + 1) * lk::TILE); ++p) {
+      const int64_t key = lk::key_of(a, p);
+      if (key == lk::EMPTY) continue;
+      lk::insert_item<lk::Plain>(a, key, 1, p);
+      ++members;
+    }
+  }
+  for (int64_t s = 0; s < a.table.slots; ++s) lk::mark_item(a, s);                            // pass 3
+  for (int64_t tile = 0; tile < a.tiles; ++tile) {                                            // passes 4 to 6
+    a.tile_pairs[tile] = numbered;
+    for (int64_t p = tile * lk::TILE; p < std::min(n, (tile + 1) * lk::TILE); ++p)
+      if (lk::is_pair_root(a, p)) lk::pair_write(a, p, numbered++);
+  }
+  totals[0] = numbered;
+  totals[1] = members;
+  return OCC4D_OK;
+}
+int occ4d_link_match_i32(const int64_t* pairs, const int32_t* totals, int cap, const int64_t* table_a, int64_t ld_a,
+                         const int64_t* table_b, int64_t ld_b, int k_a, int k_b, const int32_t* track_a, int iou_num, int iou_den,
+                         const int32_t* next_in, int32_t* link, int32_t* best_a, int32_t* next_out, void*) {
+  lk::MatchArgs m;
+  OCC4D_TRY(lk::check_match(pairs, totals, cap, table_a, ld_a, table_b, ld_b, k_a, k_b, track_a, iou_num, iou_den, next_in, link, best_a,
+                            next_out, m));
+  const int rows = lk::pair_rows(m);
+  for (int64_t k = 0; k < std::max(k_a, k_b); ++k) lk::init_item(m, k);                       // pass 1
+  for (int i = 0; i < rows; ++i) lk::best_item<lk::Plain>(m, rows, i);                        // pass 2
+  for (int64_t b = 0; b < k_b; ++b) lk::resolve_item(m, rows, b);                             // pass 3
+  for (int64_t ka = 0; ka < k_a; ++ka) lk::finish_item(m, rows, ka);                          // pass 4
+  int32_t next = next_in[0];                                                                  // pass 5
+  for (int64_t b = 0; b < k_b; ++b)
+    if (lk::is_new(m, b)) lk::new_id(m, b, next++);
+  next_out[0] = next;
   return OCC4D_OK;
 }
 

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import components as components_mod
 from . import inference
 from . import ops
 from . import projection
@@ -325,7 +326,7 @@ def occlusion_groups(live_occl_row, valo_ids_pad, num_valo_ids, n_ids, edges=(0.
 
 def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt=False, reuse_encode=True, stats=None,
                   stats_group_fn=None, stats_occlusion=None, inst_stats=None, inst_group_fn=None, refine=None, surface=None,
-                  meshes=None, views=None, images=None, components=None, objects=None):
+                  meshes=None, views=None, images=None, components=None, objects=None, tracker=None):
     """batch: dict with 'pcl_input' (1,N,8), 'pcl_input_sem' (1,N,1-3), 'pcl_target' list of (1,T,9-11) tensors and
     batch['meta_data']['pcl_target_size'] (list of (1,) tensors), as the reference's test data loader yields them
     (data/data_greater.py:593-606, data/data_carla.py:651-661).  args: namespace with the test_args fields used
@@ -344,7 +345,16 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
     views: a projection.FieldViews handed to every perform_inference call, or None; `images`: the list every output frame's
     result['views'] = dict(depth, cell, features) is appended to, in the same way.
     components: a components.Components handed to every perform_inference call, or None; `objects`: the list every output frame's
-    result['components'] = dict(labels, table) is appended to, in the same way."""
+    result['components'] = dict(labels, table) is appended to, in the same way.
+    tracker: a components.Tracker, or None (needs `components`): reset here, then handed to every perform_inference call, so that
+    every dict of `objects` gains 'link' (K, 4), the frame's components linked to those of the output frame before
+    (components.tracks turns the list into trajectories)."""
+    if tracker is not None:
+        if not isinstance(tracker, components_mod.Tracker):
+            raise ValueError('tracker must be a components.Tracker or None, got %r' % (tracker,))
+        if components is None:
+            raise ValueError('tracker needs components=<a components.Components>: it links the components of consecutive frames')
+        tracker.reset()
     if components is not None and not isinstance(objects, list):
         raise ValueError('evaluate_clip(components=...) needs objects=<a list>: one dict of labels and table per output frame is appended to it')
     if views is not None and not isinstance(images, list):
@@ -390,7 +400,7 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
             point_occupancy_radius=args.point_occupancy_radius, semantic_classes=args.semantic_classes,
             density_threshold=args.density_threshold, data_kind=data_kind, cube_mode=args.cube_mode, compress_air=True,
             encoded=encoded if reuse_encode else None, return_encoded=reuse_encode, refine=refine, surface=surface, views=views,
-            components=components, **stats_kw)
+            components=components, tracker=tracker, **stats_kw)
         if reuse_encode:                  # (track_mode 'all': a dict with one encode per tracked instance)
             encoded = res.pop('_encoded')
         else:

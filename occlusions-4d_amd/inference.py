@@ -183,7 +183,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                       density_threshold=0.5, data_kind='', cube_mode=4, compress_air=False,
                       encoded=None, return_encoded=False, neighbour_lists=None, stats=None, stats_target=None,
                       stats_group=None, track_merge='device', inst_stats=None, inst_group=None, refine=None, surface=None,
-                      views=None, components=None):
+                      views=None, components=None, tracker=None):
     """One encode of the input point-cloud video + decode of all query points of one output frame.  Returns
     dict(output_solid, output_air, pcl_abstract, features_global, implicit_output, points_query) of float32 numpy arrays, and
     gt_solid / gt_air when `pcl_target_frame` is given.  The keywords from `encoded` on are extensions whose defaults give the
@@ -239,7 +239,12 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     density_threshold) of the same squashed (N, G) array -- merged, expanded --, labelled on the device (components.label,
     include/ext/occ4d_components.h): per query its component's number or -1, per component size, root, class, coordinate sums,
     minima and maxima (components.boxes_and_centroids turns them into world-space boxes).  One 12-byte device->host read sizes
-    the table; the two arrays come back with the others, under the one host wait."""
+    the table; the two arrays come back with the others, under the one host wait.
+
+    Tracker.  `tracker`: a components.Tracker, or None; needs `components` (ValueError).  result['components'] gains 'link' (K, 4)
+    int32: per component its track id, the component of the tracker's previous frame it continues or -1, its best overlap there
+    or -1 and that overlap's points (include/ext/occ4d_link.h), made on the device from the labels and the table above and
+    fetched under the same host wait: no extra read.  The tracker then holds this frame."""
     assert task == 'if'
     assert sample_implicit
     assert track_merge in ('device', 'host'), track_merge
@@ -275,6 +280,11 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         if components.by_class and not predict_segmentation:
             raise ValueError('components with by_class=True needs predict_segmentation=True')
         components_level = components.resolve(density_threshold)
+    if tracker is not None:
+        if not isinstance(tracker, components_mod.Tracker):
+            raise ValueError('tracker must be a components.Tracker or None, got %r' % (tracker,))
+        if components is None:
+            raise ValueError('tracker needs components=<a components.Components>: it links the components of consecutive frames')
     refine_stats = dict(n_queries=0, n_decoded=0)
     output_track_idx = get_track_idx(color_mode)
     input_inst_idx = 0 if data_kind == 'greater' else 1
@@ -354,9 +364,12 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
             klass = None
             if components.by_class:
                 klass = components_mod.semantic_class(output_dev, output_dev.shape[1] - semantic_classes, semantic_classes)
-            components_h = [copies.fetch(t) for t in components_mod.label(
+            components_dev = components_mod.label(
                 output_dev, geometry.grid_counts(num_sample, min_z, cube_bounds, data_kind, cube_mode), components_level,
-                components.connectivity, components.select, klass, components.min_size)]
+                components.connectivity, components.select, klass, components.min_size)
+            components_h = [copies.fetch(t) for t in components_dev]
+            if tracker is not None:
+                components_h.append(copies.fetch(tracker.add_frame(*components_dev)))
         copies.wait()
         solid, air = copies.result(solid_h), copies.result(air_h)
         points_query = copies.result(points_query)
@@ -372,6 +385,8 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         result['views'] = dict(zip(('depth', 'cell', 'features'), (copies.result(h) for h in views_h)))
     if components is not None:
         result['components'] = dict(labels=copies.result(components_h[0]), table=copies.result(components_h[1]))
+        if tracker is not None:
+            result['components']['link'] = copies.result(components_h[2])
     if return_encoded:
         result['_encoded'] = encoded_out[-1] if -1 in encoded_out else encoded_out     # (a tuple for the one unmarked run)
     if gt_available:

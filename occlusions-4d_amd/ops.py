@@ -1666,6 +1666,91 @@ def grid_components(values, counts, level, connectivity=6, min_size=1, mask=None
     return labels, totals, table[:cap]
 
 
+def link_work_len(n, cap):
+    """Elements of the int32 work array of occ4d_link_overlap_i32 for n grid points and `cap` pair rows (the formula of the
+    header): 4 * slots + n + 2 * tiles with slots the smallest power of two >= max(2 * min(cap, n), MIN_SLOTS), at most 2^31."""
+    k = _lib.LINK_CONSTANTS
+    slots = k['MIN_SLOTS']
+    while slots < 2 * min(cap, n) and slots < 2 ** 31:
+        slots *= 2
+    return 4 * slots + n + 2 * ((n + k['TILE'] - 1) // k['TILE'])
+
+
+def components_overlap(labels_a, labels_b, k_a, k_b, cap=None, trim=False, pairs=None):
+    """The overlaps of two label volumes of the same grid (occ4d_link_overlap_i32, the rules in include/ext/occ4d_link.h):
+    labels_a, labels_b (n,) int32 as ops.grid_components returns them, k_a / k_b their numbers of components.  A point counts when
+    0 <= labels_a[p] < k_a and 0 <= labels_b[p] < k_b.  -> (pairs (cap, 4) int64: a, b, count, root per distinct (a, b), numbered
+    in the order of their lowest flat index, written below min(cap, totals[0]) only; totals (3,) int32: pairs, member points,
+    1 if the work table overflowed), on the device.  cap=None: min(n, k_a * k_b), which holds every pair.  No host read unless
+    trim=True: one 12-byte read, and pairs[:totals[0]] comes back.  `pairs`: a caller's contiguous int64 (>= cap, 4) buffer."""
+    a = _dev(labels_a, torch.int32, 'labels_a')
+    b = _dev(labels_b, torch.int32, 'labels_b')
+    n = a.shape[0] if a.dim() == 1 else -1
+    assert a.dim() == 1 and tuple(b.shape) == (n,) and a.is_contiguous() and b.is_contiguous(), \
+        'labels_a and labels_b must be contiguous (n,) tensors of one length, got %s and %s' % (tuple(a.shape), tuple(b.shape))
+    k_a, k_b = int(k_a), int(k_b)
+    cap = min(n, k_a * k_b) if cap is None else int(cap)
+    assert cap >= 0, 'cap = %d must be >= 0' % cap
+    cols = _lib.LINK_CONSTANTS['PAIR_COLS']
+    if pairs is None:
+        pairs = torch.empty((cap, cols), dtype=torch.int64, device=a.device)
+    else:
+        pairs = _dev(pairs, torch.int64, 'pairs')
+        assert pairs.dim() == 2 and pairs.shape[1] == cols and pairs.shape[0] >= cap and pairs.is_contiguous(), \
+            'pairs must be a contiguous (>= %d, %d) tensor, got %s' % (cap, cols, tuple(pairs.shape))
+    # (an empty grid is a no-op of the library: its totals are the zeros put here; the work array starts 16 bytes in: 8-byte aligned)
+    scratch = (torch.empty if n else torch.zeros)(link_work_len(n, cap) + 4, dtype=torch.int32, device=a.device)
+    totals, work = scratch[:3], scratch[4:]
+    _lib.check(_lib.lib().occ4d_link_overlap_i32(_ptr(a), _ptr(b), k_a, k_b, n, _ptr(work), _ptr(pairs) if cap else None, cap,
+                                                 _ptr(totals), _stream()))
+    if trim:
+        return pairs[:min(cap, int(totals.tolist()[0]))], totals
+    return pairs[:cap], totals
+
+
+def _min_iou_fraction(min_iou):
+    if isinstance(min_iou, (tuple, list)):
+        num, den = (int(v) for v in min_iou)
+        return num, den
+    from fractions import Fraction
+    f = Fraction(min_iou).limit_denominator(2 ** 20)
+    return f.numerator, f.denominator
+
+
+def components_match(pairs, totals, table_a, table_b, track_a, next_id, min_iou=0.0):
+    """The components of the later frame matched with those of the earlier one (occ4d_link_match_i32): pairs, totals as
+    ops.components_overlap returns them (pairs at full cap), table_a (k_a, 12), table_b (k_b, 12) int64 the two component tables
+    (column 0, the size, is read), track_a (k_a,) int32 the earlier frame's track ids, next_id (1,) int32 the first free track id,
+    on the device.  b continues a when each is the other's best overlap by intersection over union and that is >= min_iou: a float,
+    taken as Fraction(min_iou).limit_denominator(2 ** 20), or a (num, den) pair taken as it is.
+    -> (link (k_b, 4) int32: track id, linked a or -1, best a or -1, its count; best_a (k_a, 2) int32: best b or -1, its count;
+    next_out (1,) int32), on the device.  No host read."""
+    num, den = _min_iou_fraction(min_iou)
+    p = _dev(pairs, torch.int64, 'pairs')
+    assert p.dim() == 2 and p.shape[1] == _lib.LINK_CONSTANTS['PAIR_COLS'] and p.is_contiguous(), \
+        'pairs must be a contiguous (cap, 4) tensor, got %s' % (tuple(p.shape),)
+    cap = p.shape[0]
+    t = _dev(totals, torch.int32, 'totals')
+    assert tuple(t.shape) == (3,) and t.is_contiguous(), 'totals must be a contiguous (3,) tensor, got %s' % (tuple(t.shape),)
+    ta, lda = _rows(_dev(table_a, torch.int64, 'table_a'), 'table_a')
+    tb, ldb = _rows(_dev(table_b, torch.int64, 'table_b'), 'table_b')
+    assert ta.shape[1] >= 1 and tb.shape[1] >= 1, 'the tables need their size column'
+    k_a, k_b = ta.shape[0], tb.shape[0]
+    tr = _dev(track_a, torch.int32, 'track_a')
+    assert tuple(tr.shape) == (k_a,) and tr.is_contiguous(), 'track_a must be a contiguous (%d,) tensor, got %s' % (k_a, tuple(tr.shape))
+    nx = _dev(next_id, torch.int32, 'next_id')
+    assert nx.numel() == 1, 'next_id must hold one element, got %s' % (tuple(nx.shape),)
+    link = torch.empty((k_b, 4), dtype=torch.int32, device=p.device)
+    best_a = torch.empty((k_a, 2), dtype=torch.int32, device=p.device)
+    next_out = torch.empty((1,), dtype=torch.int32, device=p.device)
+    used = k_a > 0 and k_b > 0 and cap > 0
+    _lib.check(_lib.lib().occ4d_link_match_i32(_ptr(p) if used else None, _ptr(t), cap, _ptr(ta) if k_a else None, max(lda, 1),
+                                               _ptr(tb) if k_b else None, max(ldb, 1), k_a, k_b, _ptr(tr) if k_a else None, num, den,
+                                               _ptr(nx), _ptr(link) if k_b else None, _ptr(best_a) if k_a else None, _ptr(next_out),
+                                               _stream()))
+    return link, best_a, next_out
+
+
 def visibility(rows, rt, k, depth, margin):
     """Visibility code of every row under every camera against that camera's depth image (occ4d_visibility_f32): -> (V, n) int32,
     0 visible, 1 occluded (the image holds a depth d > 0 at the row's pixel and depth - d > margin), 2 outside.  depth (V, H, W),
