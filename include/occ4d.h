@@ -798,7 +798,8 @@ typedef struct occ4d_decoder_weights {
 int64_t occ4d_decoder_prepared_floats(const occ4d_decoder_weights* w, int flags);
 int occ4d_decoder_prepare_f32(const occ4d_decoder_weights* w, float* prepared, int flags, void* stream);
 /* Per abstract cloud (model/implicit.py:286-290 split of pcl_abstract; D7 hoisting; refactoring (ii) of DESIGN.md 4):
- * xyz (m, >= 3) stride xyz_stride, feats (m, d_latent_local) ld_feats, fglobal (d_latent - d_latent_local). */
+ * xyz (m, >= 3) stride xyz_stride, feats (m, d_latent_local) ld_feats, fglobal (d_latent - d_latent_local); a decoder
+ * without a global part (d_latent == d_latent_local) takes fglobal = NULL. */
 int64_t occ4d_decoder_scene_floats(const occ4d_decoder_weights* w, int m);
 int occ4d_decoder_prepare_scene_f32(const occ4d_decoder_weights* w, const float* prepared, const float* xyz,
                                     int64_t xyz_stride, const float* feats, int64_t ld_feats, const float* fglobal,

@@ -777,8 +777,9 @@ int decoder_forward(const occ4d_decoder_weights& w, const DecoderLayout& L, cons
       if (!dry) {
         // x += lin_z[i](features_query) in the exact-in-R form.  OCC4D_PATH_FUSED_INTERP (A/B only,
         // measured slower: DESIGN.md 6e): the term of block i + 1 is added in block i's epilogue instead, wherever no
-        // cross-attention layer sits between the two blocks.
-        const bool fuse_ok = (flags & OCC4D_PATH_FUSED_INTERP) && L.resblock && !L.trunk4;
+        // cross-attention layer sits between the two blocks.  Only the fp32 fused block has that epilogue: where the
+        // split-precision trunk takes the block (L.x6trunk, L.f16block included) every term is added here.
+        const bool fuse_ok = (flags & OCC4D_PATH_FUSED_INTERP) && L.resblock && !L.trunk4 && !L.x6trunk;
         const bool cross_behind = next_cross < L.nC && w.cross_after[next_cross] == i;
         const bool cross_before = i > 0 && next_cross > 0 && w.cross_after[next_cross - 1] == i - 1;
         const bool had_it = fuse_ok && i > 0 && !cross_before;           // block i - 1's epilogue added this block's term

@@ -1061,11 +1061,12 @@ int occ4d_decoder_prepare_scene_f32(const occ4d_decoder_weights* w, const float*
                                     const float* feats, int64_t ld_feats, const float* fglobal, int m, float* scene, int, void* st) {
   const char* who = "occ4d_decoder_prepare_scene_f32";
   OCC4D_TRY(check_decoder(w, who));
-  OCC4D_REQUIRE(xyz && feats && fglobal && scene && m >= 1, "%s: bad arguments", who);
+  const int dg = w->d_latent - w->d_latent_local;                            // 0: a decoder without a global part takes no fglobal
+  OCC4D_REQUIRE(xyz && feats && scene && m >= 1 && dg >= 0 && (dg == 0 || fglobal), "%s: bad arguments", who);
   const DecScene S = dec_scene(*w, m);
   OCC4D_TRY(occ4d_copy_rows_f32(scene + S.xyz, 3, xyz, xyz_stride, m, 3, st));
   OCC4D_TRY(occ4d_copy_rows_f32(scene + S.feats, w->d_latent_local, feats, ld_feats, m, w->d_latent_local, st));
-  std::memcpy(scene + S.fglobal, fglobal, sizeof(float) * (w->d_latent - w->d_latent_local));
+  if (dg > 0) std::memcpy(scene + S.fglobal, fglobal, sizeof(float) * dg);
   for (int j = 0; j < w->n_cross; ++j)      // to_k / to_v rows of the abstract cloud: once per scene instead of once per call (D7)
     layer_tables(w->cross[j], scene + S.feats, w->d_latent_local, m, scene + S.layer[j], scene + S.layer[j] + (int64_t)m * w->cross[j].dim);
   return OCC4D_OK;

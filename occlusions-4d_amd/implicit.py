@@ -210,13 +210,18 @@ class LocalPclResnetFC(ResnetFC, kernels.HasKernelSelection):
         buffer for them (occ4d_decoder_prepare_f32: stage-packed residual blocks, merged + packed cross-attention
         layers).  Cached while the parameters (storage, version, weights epoch) and the kernel flags are unchanged."""
         flags = ptl.path_flags(self)
-        key = (flags, weights_epoch()) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        # use_pt_inds {block: layer} is the reference's map (model/implicit.py:264-268) and, as there, what decides which
+        # layer runs where: two layers the constructor's formula puts behind ONE block share a key, the later one
+        # shadows the earlier (whose parameters stay in the state dict and are never run)
+        live = tuple(sorted(self.use_pt_inds.items())) if self.local_mode == 'attention' else ()
+        key = (flags, weights_epoch(), live) + tuple((p.data_ptr(), p._version) for p in self.parameters())
         cache = self.__dict__.setdefault('_path', {})       # one entry per flag value (threads under different selections)
         hit = cache.get(flags)
         if hit is not None and hit[0] == key:
             return hit[1], hit[2], flags
         L = ops._lib
-        assert self.n_blocks <= L.MAX_BLOCKS and len(getattr(self, 'pt_blocks', [])) <= L.MAX_CROSS
+        assert self.n_blocks <= L.MAX_BLOCKS and len(live) <= L.MAX_CROSS
+        assert all(0 <= i < self.n_blocks and 0 <= j < len(self.pt_blocks) for i, j in live), live
         keep = []
 
         def dp(t):
@@ -232,7 +237,7 @@ class LocalPclResnetFC(ResnetFC, kernels.HasKernelSelection):
             w_in = torch.nn.functional.pad(w_in, (0, 4 - p_in % 4))
         w = L.DecoderWeights(d_in=self.d_in, n_freq=self.pos_encoding_freqs, d_hidden=self.d_hidden, d_out=self.d_out,
                              d_latent=self.d_latent, d_latent_local=self.d_latent_local, n_blocks=self.n_blocks,
-                             n_cross=len(self.pt_blocks) if self.local_mode == 'attention' else 0,
+                             n_cross=len(live),
                              k_local=self.num_local_features, k_cross=self.cross_attn_neighbors,
                              activation=ACTIVATIONS[self.activation] - 1, lin_in_ld=w_in.shape[1], base_frequency=0.1)
         w.lin_in_w, w.lin_in_b = dp(w_in), dp(self.lin_in.bias)
@@ -241,14 +246,12 @@ class LocalPclResnetFC(ResnetFC, kernels.HasKernelSelection):
             w.lin_z_w[i], w.lin_z_b[i] = dp(self.lin_z[i].weight), dp(self.lin_z[i].bias)
             w.fc0_w[i], w.fc0_b[i] = dp(self.blocks[i].fc_0.weight), dp(self.blocks[i].fc_0.bias)
             w.fc1_w[i], w.fc1_b[i] = dp(self.blocks[i].fc_1.weight), dp(self.blocks[i].fc_1.bias)
-        if self.local_mode == 'attention':
-            after = sorted(self.use_pt_inds)
-            for j, blk in enumerate(self.pt_blocks):
-                lw, _, _ = blk.layer2.path_weights(cross=True, pre=blk.layer1, post=blk.layer3, flags=flags)
-                w.cross[j] = lw
-                keep.append(lw)
-                w.cross_after[j] = after[j]
-                assert self.use_pt_inds[after[j]] == j
+        for j, (after, layer) in enumerate(live):          # cross[j]: the layer that runs behind the j-th position, ascending
+            blk = self.pt_blocks[layer]
+            lw, _, _ = blk.layer2.path_weights(cross=True, pre=blk.layer1, post=blk.layer3, flags=flags)
+            w.cross[j] = lw
+            keep.append(lw)
+            w.cross_after[j] = after
         w._keep = keep
         prepared = ops.decoder_prepare(w, flags, self.lin_out.weight.device)
         cache[flags] = (key, w, prepared)

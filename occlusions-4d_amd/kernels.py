@@ -43,7 +43,8 @@ class Selection:
     attn16: bool = True               # d = 416: csrc/crossattn16p.hip; False: csrc/crossattn.hip (OCC4D_PATH_FIRST_GEN)
     trunk_kernels: bool = True        # row-resident trunk kernels; False: the generic Linear kernel
     trunk4: bool = False              # half-CU trunk kernels (csrc/trunk4.hip): measured slower at the decode chunk
-    fused_interp: bool = False        # A/B only: lin_z table term of block i + 1 in block i's epilogue
+    fused_interp: bool = False        # A/B only: lin_z table term of block i + 1 in block i's epilogue (the fp32 fused
+                                      # block's; without effect under trunk4 or a split trunk_precision)
     logit_precision: str = 'f32'      # the d = 416 attention layers' GEMMs
     trunk_precision: str = 'f32'      # the decoder's 416-input Linear layers (residual blocks, query projection, layer3)
     train_precision: str = 'f32'      # training path: forward Linears, data gradients, pair-tensor recompute ('f32' | 'bf16x6')
