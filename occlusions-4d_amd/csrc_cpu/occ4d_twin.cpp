@@ -34,6 +34,7 @@
 #include "ext/occ4d_raycast.h"
 #include "ext/occ4d_components.h"
 #include "ext/occ4d_link.h"
+#include "ext/occ4d_distance.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -46,6 +47,7 @@
 #include "raycast_math.hpp"
 #include "components_math.hpp"
 #include "link_math.hpp"
+#include "distance_math.hpp"
 #include "decoder_math.hpp"
 
 namespace fe = occ4d_frontend;
@@ -59,6 +61,7 @@ namespace sf = occ4d_surface;
 namespace ry = occ4d_raycast;
 namespace cc = occ4d_components;
 namespace lk = occ4d_link;
+namespace dm = occ4d_distance;
 
 static thread_local char g_err[512] = "";
 
@@ -839,6 +842,27 @@ int occ4d_link_match_i32(const int64_t* pairs, const int32_t* totals, int cap, c
   for (int64_t b = 0; b < k_b; ++b)
     if (lk::is_new(m, b)) lk::new_id(m, b, next++);
   next_out[0] = next;
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- distance
+// include/ext/occ4d_distance.h: the three stages of csrc/distance.hip over csrc/distance_math.hpp, LINE BY LINE (a tile of width 1):
+// the line's pairs staged, then each of its points' minimum written in place.
+int occ4d_distance_grid_f32(const float* field, int64_t ld, float level, const float* mask, int64_t ld_mask, float mask_level,
+                            int target, int nx, int ny, int nz, int wx, int wy, int wz, int32_t* dist2, int32_t* nearest, void*) {
+  dm::Args a; bool empty;
+  OCC4D_TRY(dm::check_distance(field, ld, level, mask, ld_mask, mask_level, target, nx, ny, nz, wx, wy, wz, dist2, nearest, empty, a));
+  if (empty) return OCC4D_OK;
+  std::vector<int32_t> s_cost(dm::MAX_AXIS), s_site(dm::MAX_AXIS);
+  for (int stage = 0; stage < 3; ++stage) {
+    const dm::Pass ps = dm::pass_of(a, stage, 1);
+    const int slots = dm::tile_slots(ps);
+    for (int64_t b = 0; b < ps.tiles; ++b) {
+      const dm::Tile t = dm::tile_of(ps, b);
+      for (int s = 0; s < slots; ++s) dm::stage_item(a, ps, t, s, s_cost.data(), nearest ? s_site.data() : nullptr);
+      for (int s = 0; s < slots; ++s) dm::min_item(a, ps, t, s, s_cost.data(), nearest ? s_site.data() : nullptr);
+    }
+  }
   return OCC4D_OK;
 }
 

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from . import components as components_mod
+from . import distance as distance_mod
 from . import inference
 from . import ops
 from . import projection
@@ -326,7 +327,8 @@ def occlusion_groups(live_occl_row, valo_ids_pad, num_valo_ids, n_ids, edges=(0.
 
 def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt=False, reuse_encode=True, stats=None,
                   stats_group_fn=None, stats_occlusion=None, inst_stats=None, inst_group_fn=None, refine=None, surface=None,
-                  meshes=None, views=None, images=None, components=None, objects=None, tracker=None):
+                  meshes=None, views=None, images=None, components=None, objects=None, tracker=None, clearance=None,
+                  clearances=None):
     """batch: dict with 'pcl_input' (1,N,8), 'pcl_input_sem' (1,N,1-3), 'pcl_target' list of (1,T,9-11) tensors and
     batch['meta_data']['pcl_target_size'] (list of (1,) tensors), as the reference's test data loader yields them
     (data/data_greater.py:593-606, data/data_carla.py:651-661).  args: namespace with the test_args fields used
@@ -348,7 +350,14 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
     result['components'] = dict(labels, table) is appended to, in the same way.
     tracker: a components.Tracker, or None (needs `components`): reset here, then handed to every perform_inference call, so that
     every dict of `objects` gains 'link' (K, 4), the frame's components linked to those of the output frame before
-    (components.tracks turns the list into trajectories)."""
+    (components.tracks turns the list into trajectories).
+    clearance: a distance.Clearance handed to every perform_inference call, or None; `clearances`: the list every output frame's
+    result['clearance'] = dict(dist2[, nearest][, inside2]) is appended to, in the same way."""
+    if clearance is not None:
+        if not isinstance(clearance, distance_mod.Clearance):
+            raise ValueError('clearance must be a distance.Clearance or None, got %r' % (clearance,))
+        if not isinstance(clearances, list):
+            raise ValueError('evaluate_clip(clearance=...) needs clearances=<a list>: one dict of distances per output frame is appended to it')
     if tracker is not None:
         if not isinstance(tracker, components_mod.Tracker):
             raise ValueError('tracker must be a components.Tracker or None, got %r' % (tracker,))
@@ -400,7 +409,7 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
             point_occupancy_radius=args.point_occupancy_radius, semantic_classes=args.semantic_classes,
             density_threshold=args.density_threshold, data_kind=data_kind, cube_mode=args.cube_mode, compress_air=True,
             encoded=encoded if reuse_encode else None, return_encoded=reuse_encode, refine=refine, surface=surface, views=views,
-            components=components, tracker=tracker, **stats_kw)
+            components=components, tracker=tracker, clearance=clearance, **stats_kw)
         if reuse_encode:                  # (track_mode 'all': a dict with one encode per tracked instance)
             encoded = res.pop('_encoded')
         else:
@@ -411,6 +420,8 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
             images.append(res['views'])
         if components is not None:
             objects.append(res['components'])
+        if clearance is not None:
+            clearances.append(res['clearance'])
         item = (pcl_input_numpy, res['pcl_abstract'], res['output_solid'], frame, res['output_air'])
         if save_gt:
             item = item + (pcl_input_sem_numpy, res['points_query'])

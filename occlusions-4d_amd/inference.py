@@ -22,6 +22,7 @@ from . import ops
 from . import projection
 from . import surface as surface_nets
 from . import components as components_mod
+from . import distance as distance_mod
 
 
 def get_track_idx(color_mode):
@@ -183,7 +184,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                       density_threshold=0.5, data_kind='', cube_mode=4, compress_air=False,
                       encoded=None, return_encoded=False, neighbour_lists=None, stats=None, stats_target=None,
                       stats_group=None, track_merge='device', inst_stats=None, inst_group=None, refine=None, surface=None,
-                      views=None, components=None, tracker=None):
+                      views=None, components=None, tracker=None, clearance=None):
     """One encode of the input point-cloud video + decode of all query points of one output frame.  Returns
     dict(output_solid, output_air, pcl_abstract, features_global, implicit_output, points_query) of float32 numpy arrays, and
     gt_solid / gt_air when `pcl_target_frame` is given.  The keywords from `encoded` on are extensions whose defaults give the
@@ -244,7 +245,14 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     Tracker.  `tracker`: a components.Tracker, or None; needs `components` (ValueError).  result['components'] gains 'link' (K, 4)
     int32: per component its track id, the component of the tracker's previous frame it continues or -1, its best overlap there
     or -1 and that overlap's points (include/ext/occ4d_link.h), made on the device from the labels and the table above and
-    fetched under the same host wait: no extra read.  The tracker then holds this frame."""
+    fetched under the same host wait: no extra read.  The tracker then holds this frame.
+
+    Clearance.  `clearance`: a distance.Clearance (level, select, weights, nearest, inside), or None.  point_sample_mode 'grid'
+    only (ValueError).  The result gains 'clearance' = dict(dist2 (N,) int32[, nearest (N,) int32][, inside2 (N,) int32]): the exact
+    distance transform of density >= clearance.level (None: density_threshold) of the same squashed (N, G) array -- merged,
+    expanded --, on the device (distance.transform, include/ext/occ4d_distance.h): per query the squared distance, in weighted grid
+    steps, to the nearest solid query (2^31 - 1: there is none), the flat index of that query, and the squared distance to the
+    nearest query that is not solid.  No device value is read; the arrays come back with the others, under the one host wait."""
     assert task == 'if'
     assert sample_implicit
     assert track_merge in ('device', 'host'), track_merge
@@ -285,6 +293,13 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
             raise ValueError('tracker must be a components.Tracker or None, got %r' % (tracker,))
         if components is None:
             raise ValueError('tracker needs components=<a components.Components>: it links the components of consecutive frames')
+    clearance_level = None
+    if clearance is not None:
+        if not isinstance(clearance, distance_mod.Clearance):
+            raise ValueError('clearance must be a distance.Clearance or None, got %r' % (clearance,))
+        if point_sample_mode != 'grid':
+            raise ValueError("clearance needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
+        clearance_level = clearance.resolve(density_threshold)
     refine_stats = dict(n_queries=0, n_decoded=0)
     output_track_idx = get_track_idx(color_mode)
     input_inst_idx = 0 if data_kind == 'greater' else 1
@@ -370,6 +385,10 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
             components_h = [copies.fetch(t) for t in components_dev]
             if tracker is not None:
                 components_h.append(copies.fetch(tracker.add_frame(*components_dev)))
+        if clearance is not None:
+            clearance_h = {k: copies.fetch(t) for k, t in distance_mod.transform(
+                output_dev, geometry.grid_counts(num_sample, min_z, cube_bounds, data_kind, cube_mode), clearance_level,
+                clearance.select, clearance.weights, clearance.nearest, clearance.inside).items()}
         copies.wait()
         solid, air = copies.result(solid_h), copies.result(air_h)
         points_query = copies.result(points_query)
@@ -387,6 +406,8 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         result['components'] = dict(labels=copies.result(components_h[0]), table=copies.result(components_h[1]))
         if tracker is not None:
             result['components']['link'] = copies.result(components_h[2])
+    if clearance is not None:
+        result['clearance'] = {k: copies.result(h) for k, h in clearance_h.items()}
     if return_encoded:
         result['_encoded'] = encoded_out[-1] if -1 in encoded_out else encoded_out     # (a tuple for the one unmarked run)
     if gt_available:

@@ -1666,6 +1666,50 @@ def grid_components(values, counts, level, connectivity=6, min_size=1, mask=None
     return labels, totals, table[:cap]
 
 
+def distance_tile_width(length, stage=1):
+    """Lines of a workgroup's tile in the launcher of occ4d_distance_grid_f32 for lines of `length` points (the formulas of the
+    header's constants): stage 0 (z) max(1, RUN_POINTS // length) consecutive lines; stages 1, 2 (y, x) TILE_WIDTH halved until
+    length * width <= TILE_POINTS."""
+    k = _lib.DISTANCE_CONSTANTS
+    if stage == 0:
+        return max(1, k['RUN_POINTS'] // length)
+    width = k['TILE_WIDTH']
+    while width > 1 and width * length > k['TILE_POINTS']:
+        width //= 2
+    return width
+
+
+def grid_distance(values, counts, level, weights=(1, 1, 1), target=0, mask=None, mask_level=0.0, nearest=False, out=None):
+    """The exact squared Euclidean distance of every point of the (nx, ny, nz) = `counts` grid to the nearest SITE
+    (occ4d_distance_grid_f32, the rules in include/ext/occ4d_distance.h).  values (n,): one value per grid point, x slowest, z
+    fastest (a strided column view is read in place); the members are values >= level, with mask (n,) also mask >= mask_level.
+    target 0: the members are the sites; 1: the non-members.  weights = (wx, wy, wz): integers >= 1, the cost of a step along each
+    axis is its weight times the squared number of points.  nearest: also the flat index of the site.
+    `out` = (dist2, nearest or None): the caller's contiguous int32 buffers of >= n elements, whose first n are used.
+    -> (dist2 (n,) int32, DISTANCE_CONSTANTS['NONE'] where there is no site; nearest (n,) int32, -1 there, or None), on the device.
+    No host read."""
+    nx, ny, nz = (int(c) for c in counts)
+    n = nx * ny * nz
+    v, ld = _inst_column(values, n, 'values')
+    m, ld_mask = (None, 0) if mask is None else _inst_column(mask, n, 'mask')
+    wx, wy, wz = (int(w) for w in weights)
+    bufs = []
+    for i, (name, wanted) in enumerate((('dist2', True), ('nearest', bool(nearest)))):
+        buf = None if out is None else out[i]
+        if not wanted:
+            assert buf is None, 'out holds a nearest buffer without nearest=True'
+        elif buf is None:
+            buf = torch.empty((max(n, 0),), dtype=torch.int32, device=v.device)
+        else:
+            buf = _dev(buf, torch.int32, 'out ' + name)
+            assert buf.dim() == 1 and buf.shape[0] >= n and buf.is_contiguous(), \
+                'out %s must be a contiguous (>= %d,) tensor, got %s' % (name, n, tuple(buf.shape))
+        bufs.append(buf)
+    _lib.check(_lib.lib().occ4d_distance_grid_f32(_ptr(v), ld, float(level), _ptr(m), ld_mask, float(mask_level), int(target), nx, ny, nz,
+                                                  wx, wy, wz, _ptr(bufs[0]), _ptr(bufs[1]), _stream()))
+    return bufs[0][:max(n, 0)], None if bufs[1] is None else bufs[1][:max(n, 0)]
+
+
 def link_work_len(n, cap):
     """Elements of the int32 work array of occ4d_link_overlap_i32 for n grid points and `cap` pair rows (the formula of the
     header): 4 * slots + n + 2 * tiles with slots the smallest power of two >= max(2 * min(cap, n), MIN_SLOTS), at most 2^31."""
