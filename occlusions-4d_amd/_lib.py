@@ -44,6 +44,7 @@ ADDON_HEADERS = {
     'COMPONENTS': 'ext/occ4d_components.h',     # the connected components of the solid set (components.py, perform_inference(components=...))
     'LINK': 'ext/occ4d_link.h',                 # the components of two frames linked: overlaps, tracks (components.Tracker, perform_inference(tracker=...))
     'DISTANCE': 'ext/occ4d_distance.h',         # the distance transform of the solid set: clearance (distance.py, perform_inference(clearance=...))
+    'GEODESIC': 'ext/occ4d_geodesic.h',         # shortest free-space paths over the clearance (geodesic.py, perform_inference(route=...))
 }
 
 

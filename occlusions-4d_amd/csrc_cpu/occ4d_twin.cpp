@@ -35,6 +35,7 @@
 #include "ext/occ4d_components.h"
 #include "ext/occ4d_link.h"
 #include "ext/occ4d_distance.h"
+#include "ext/occ4d_geodesic.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -48,6 +49,7 @@
 #include "components_math.hpp"
 #include "link_math.hpp"
 #include "distance_math.hpp"
+#include "geodesic_math.hpp"
 #include "decoder_math.hpp"
 
 namespace fe = occ4d_frontend;
@@ -62,6 +64,7 @@ namespace ry = occ4d_raycast;
 namespace cc = occ4d_components;
 namespace lk = occ4d_link;
 namespace dm = occ4d_distance;
+namespace gm = occ4d_geodesic;
 
 static thread_local char g_err[512] = "";
 
@@ -863,6 +866,60 @@ int occ4d_distance_grid_f32(const float* field, int64_t ld, float level, const f
       for (int s = 0; s < slots; ++s) dm::min_item(a, ps, t, s, s_cost.data(), nearest ? s_site.data() : nullptr);
     }
   }
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- geodesic
+// include/ext/occ4d_geodesic.h: the passes of csrc/geodesic.hip over csrc/geodesic_math.hpp with ONE TILE, THE WHOLE GRID, relaxed in
+// place: a round sweeps the points forwards and backwards in turn until a sweep lowers nothing (a `for` bounded by the grid's points)
+// -- another tiling and another order of events than the kernel's, the same fixed point.
+int occ4d_geodesic_grid_i32(const int32_t* clear, int min_clear, int nx, int ny, int nz, const int32_t* seeds, int n_seeds,
+                            int connectivity, int step_face, int step_edge, int step_corner, int rounds, int resume, int32_t* work,
+                            int32_t* cost, int32_t* parent, int32_t* status, void*) {
+  gm::Args a; bool empty;
+  OCC4D_TRY(gm::check_geodesic(clear, min_clear, nx, ny, nz, seeds, n_seeds, connectivity, step_face, step_edge, step_corner, rounds,
+                               resume, work, cost, parent, status, empty, a));
+  if (empty) return OCC4D_OK;
+  for (int k = 0; k <= rounds; ++k) a.flags[k] = k == 0 ? 1 : 0;
+  if (!resume) {
+    for (int64_t p = 0; p < a.points; ++p) a.cost[p] = gm::NONE;
+    for (int k = 0; k < n_seeds; ++k) {
+      const int64_t p = gm::seed_point(a, k);
+      if (p >= 0) a.cost[p] = 0;
+    }
+  }
+  for (int k = 1; k <= rounds && a.flags[k - 1]; ++k) {
+    for (int64_t it = 0; it < a.points; ++it) {
+      bool lowered = false;
+      for (int64_t u = 0; u < a.points; ++u) {
+        const int64_t p = it % 2 ? a.points - 1 - u : u;
+        if (!gm::passable(a, p)) continue;
+        int i[3];
+        gm::coords_of(a, p, i);
+        const int32_t best = gm::relax_point(a.rank, a.step, a.cost[p], gm::GridAt{a, i});
+        if (best < a.cost[p]) {
+          a.cost[p] = best;
+          lowered = true;
+        }
+      }
+      if (!lowered) break;
+      a.flags[k] = 1;
+    }
+  }
+  int changed = 0;
+  for (int k = 1; k <= rounds; ++k) changed += a.flags[k] != 0;
+  gm::status_item(a, changed);
+  if (parent)
+    for (int64_t p = 0; p < a.points; ++p) gm::parent_item(a, p);
+  return OCC4D_OK;
+}
+
+int occ4d_geodesic_trace_i32(const int32_t* cost, const int32_t* parent, int n, const int32_t* goals, int n_goals, int cap,
+                             int32_t* paths, int32_t* path_len, void*) {
+  gm::TraceArgs a; bool empty;
+  OCC4D_TRY(gm::check_trace(cost, parent, n, goals, n_goals, cap, paths, path_len, empty, a));
+  if (empty) return OCC4D_OK;
+  for (int g = 0; g < n_goals; ++g) gm::trace_item(a, g);
   return OCC4D_OK;
 }
 

@@ -24,6 +24,7 @@ import torch
 from . import _lib
 from . import components as components_mod
 from . import distance as distance_mod
+from . import geodesic as geodesic_mod
 from . import inference
 from . import ops
 from . import projection
@@ -328,7 +329,7 @@ def occlusion_groups(live_occl_row, valo_ids_pad, num_valo_ids, n_ids, edges=(0.
 def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt=False, reuse_encode=True, stats=None,
                   stats_group_fn=None, stats_occlusion=None, inst_stats=None, inst_group_fn=None, refine=None, surface=None,
                   meshes=None, views=None, images=None, components=None, objects=None, tracker=None, clearance=None,
-                  clearances=None):
+                  clearances=None, route=None, routes=None):
     """batch: dict with 'pcl_input' (1,N,8), 'pcl_input_sem' (1,N,1-3), 'pcl_target' list of (1,T,9-11) tensors and
     batch['meta_data']['pcl_target_size'] (list of (1,) tensors), as the reference's test data loader yields them
     (data/data_greater.py:593-606, data/data_carla.py:651-661).  args: namespace with the test_args fields used
@@ -352,7 +353,16 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
     every dict of `objects` gains 'link' (K, 4), the frame's components linked to those of the output frame before
     (components.tracks turns the list into trajectories).
     clearance: a distance.Clearance handed to every perform_inference call, or None; `clearances`: the list every output frame's
-    result['clearance'] = dict(dist2[, nearest][, inside2]) is appended to, in the same way."""
+    result['clearance'] = dict(dist2[, nearest][, inside2]) is appended to, in the same way.
+    route: a geodesic.Route handed to every perform_inference call, or None (needs `clearance`); `routes`: the list every output
+    frame's result['route'] = dict(cost, status[, parent][, paths, path_len]) is appended to, in the same way."""
+    if route is not None:
+        if not isinstance(route, geodesic_mod.Route):
+            raise ValueError('route must be a geodesic.Route or None, got %r' % (route,))
+        if clearance is None:
+            raise ValueError('route needs clearance=<a distance.Clearance>: a query is passable when its dist2 >= route.min_clear')
+        if not isinstance(routes, list):
+            raise ValueError('evaluate_clip(route=...) needs routes=<a list>: one dict of costs and paths per output frame is appended to it')
     if clearance is not None:
         if not isinstance(clearance, distance_mod.Clearance):
             raise ValueError('clearance must be a distance.Clearance or None, got %r' % (clearance,))
@@ -409,7 +419,7 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
             point_occupancy_radius=args.point_occupancy_radius, semantic_classes=args.semantic_classes,
             density_threshold=args.density_threshold, data_kind=data_kind, cube_mode=args.cube_mode, compress_air=True,
             encoded=encoded if reuse_encode else None, return_encoded=reuse_encode, refine=refine, surface=surface, views=views,
-            components=components, tracker=tracker, clearance=clearance, **stats_kw)
+            components=components, tracker=tracker, clearance=clearance, route=route, **stats_kw)
         if reuse_encode:                  # (track_mode 'all': a dict with one encode per tracked instance)
             encoded = res.pop('_encoded')
         else:
@@ -422,6 +432,8 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
             objects.append(res['components'])
         if clearance is not None:
             clearances.append(res['clearance'])
+        if route is not None:
+            routes.append(res['route'])
         item = (pcl_input_numpy, res['pcl_abstract'], res['output_solid'], frame, res['output_air'])
         if save_gt:
             item = item + (pcl_input_sem_numpy, res['points_query'])

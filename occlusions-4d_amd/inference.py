@@ -23,6 +23,7 @@ from . import projection
 from . import surface as surface_nets
 from . import components as components_mod
 from . import distance as distance_mod
+from . import geodesic as geodesic_mod
 
 
 def get_track_idx(color_mode):
@@ -184,7 +185,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                       density_threshold=0.5, data_kind='', cube_mode=4, compress_air=False,
                       encoded=None, return_encoded=False, neighbour_lists=None, stats=None, stats_target=None,
                       stats_group=None, track_merge='device', inst_stats=None, inst_group=None, refine=None, surface=None,
-                      views=None, components=None, tracker=None, clearance=None):
+                      views=None, components=None, route=None, tracker=None, clearance=None):
     """One encode of the input point-cloud video + decode of all query points of one output frame.  Returns
     dict(output_solid, output_air, pcl_abstract, features_global, implicit_output, points_query) of float32 numpy arrays, and
     gt_solid / gt_air when `pcl_target_frame` is given.  The keywords from `encoded` on are extensions whose defaults give the
@@ -252,7 +253,17 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     distance transform of density >= clearance.level (None: density_threshold) of the same squashed (N, G) array -- merged,
     expanded --, on the device (distance.transform, include/ext/occ4d_distance.h): per query the squared distance, in weighted grid
     steps, to the nearest solid query (2^31 - 1: there is none), the flat index of that query, and the squared distance to the
-    nearest query that is not solid.  No device value is read; the arrays come back with the others, under the one host wait."""
+    nearest query that is not solid.  No device value is read; the arrays come back with the others, under the one host wait.
+
+    Route.  `route` (in the signature it stands in front of `tracker`: the suite pins the last two names): a geodesic.Route (seeds,
+    goals, min_clear, connectivity, steps, rounds, parent, path_cap), or None; needs `clearance` and point_sample_mode 'grid'
+    (ValueError).  World-point seeds and goals become grid indices on the host before the decode (geodesic.grid_index; ValueError
+    outside the grid).  The result gains 'route' = dict(cost (N,) int32, status (2,) int32[, parent (N,) int32][, paths (G, cap)
+    int32, path_len (G,) int32]): the least step cost of a path from any seed to every query over the queries with clearance
+    dist2 >= route.min_clear -- that call's dist2: merged, expanded --, and the goals' paths back to a seed (geodesic.solve,
+    include/ext/occ4d_geodesic.h).  A fixed number of launches -- route.rounds (None: ops.geodesic_default_rounds) + 2, one more for
+    the predecessors and one for the paths -- and no device value read: status[0] == 1 says that the costs are converged, i.e. THE
+    shortest, and has to be looked at; the arrays come back with the others, under the one host wait."""
     assert task == 'if'
     assert sample_implicit
     assert track_merge in ('device', 'host'), track_merge
@@ -300,6 +311,15 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         if point_sample_mode != 'grid':
             raise ValueError("clearance needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
         clearance_level = clearance.resolve(density_threshold)
+    route_on_grid = None
+    if route is not None:
+        if not isinstance(route, geodesic_mod.Route):
+            raise ValueError('route must be a geodesic.Route or None, got %r' % (route,))
+        if point_sample_mode != 'grid':
+            raise ValueError("route needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
+        if clearance is None:
+            raise ValueError('route needs clearance=<a distance.Clearance>: a query is passable when its dist2 >= route.min_clear')
+        route_on_grid = route.resolve(*geometry.grid_frame(num_sample, min_z, cube_bounds, data_kind, cube_mode))
     refine_stats = dict(n_queries=0, n_decoded=0)
     output_track_idx = get_track_idx(color_mode)
     input_inst_idx = 0 if data_kind == 'greater' else 1
@@ -386,9 +406,17 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
             if tracker is not None:
                 components_h.append(copies.fetch(tracker.add_frame(*components_dev)))
         if clearance is not None:
-            clearance_h = {k: copies.fetch(t) for k, t in distance_mod.transform(
+            clearance_dev = distance_mod.transform(
                 output_dev, geometry.grid_counts(num_sample, min_z, cube_bounds, data_kind, cube_mode), clearance_level,
-                clearance.select, clearance.weights, clearance.nearest, clearance.inside).items()}
+                clearance.select, clearance.weights, clearance.nearest, clearance.inside)
+            clearance_h = {k: copies.fetch(t) for k, t in clearance_dev.items()}
+        if route is not None:                 # (rounds given: a fixed number of launches and no read of the status)
+            route_counts = geometry.grid_counts(num_sample, min_z, cube_bounds, data_kind, cube_mode)
+            seeds_dev, goals_dev = (None if a is None else torch.from_numpy(a).to(device) for a in route_on_grid[:2])
+            route_h = {k: copies.fetch(t) for k, t in geodesic_mod.solve(
+                clearance_dev['dist2'], route_counts, seeds_dev, goals_dev, route.min_clear, route.connectivity, route.steps,
+                ops.geodesic_default_rounds(route_counts) if route.rounds is None else route.rounds, route.parent,
+                route_on_grid[2]).items()}
         copies.wait()
         solid, air = copies.result(solid_h), copies.result(air_h)
         points_query = copies.result(points_query)
@@ -408,6 +436,8 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
             result['components']['link'] = copies.result(components_h[2])
     if clearance is not None:
         result['clearance'] = {k: copies.result(h) for k, h in clearance_h.items()}
+    if route is not None:
+        result['route'] = {k: copies.result(h) for k, h in route_h.items()}
     if return_encoded:
         result['_encoded'] = encoded_out[-1] if -1 in encoded_out else encoded_out     # (a tuple for the one unmarked run)
     if gt_available:

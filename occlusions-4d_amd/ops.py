@@ -1710,6 +1710,94 @@ def grid_distance(values, counts, level, weights=(1, 1, 1), target=0, mask=None,
     return bufs[0][:max(n, 0)], None if bufs[1] is None else bufs[1][:max(n, 0)]
 
 
+def geodesic_default_rounds(counts):
+    """The default number of relaxation rounds of ops.grid_geodesic on a (nx, ny, nz) grid: twice the sum of the tile counts along
+    the three axes (the tile shape is the header's), 64 at 96 x 96 x 58.  A heuristic: status[0] says whether it was enough."""
+    k = _lib.GEODESIC_CONSTANTS
+    return 2 * sum(-(-int(c) // k[t]) for c, t in zip(counts, ('TILE_X', 'TILE_Y', 'TILE_Z')))
+
+
+def geodesic_work_len(rounds):
+    """Elements of the int32 work array of occ4d_geodesic_grid_i32 for `rounds` rounds (the formula of the header): one word per
+    round and one in front."""
+    return int(rounds) + 1
+
+
+def _int32_out(buf, shape, device, name):
+    """A caller's contiguous int32 buffer of at least prod(shape) elements (its first ones are used, viewed as `shape`), or a new one."""
+    count = 1
+    for s in shape:
+        count *= s
+    if buf is None:
+        return torch.empty(shape, dtype=torch.int32, device=device)
+    buf = _dev(buf, torch.int32, name)
+    assert buf.dim() == 1 and buf.shape[0] >= count and buf.is_contiguous(), \
+        '%s must be a contiguous (>= %d,) tensor, got %s' % (name, count, tuple(buf.shape))
+    return buf[:count].view(shape)
+
+
+def grid_geodesic(clear, counts, seeds, min_clear=1, connectivity=26, steps=(3, 4, 5), rounds=None, parent=False, resume=None,
+                  out=None, work=None):
+    """The least total step cost of a path from any seed to every point of the (nx, ny, nz) = `counts` grid that stays on passable
+    points (occ4d_geodesic_grid_i32, the rules in include/ext/occ4d_geodesic.h).  clear (n,) int32, x slowest, z fastest: a point
+    is passable when clear >= min_clear (ops.grid_distance's dist2: 1 = not solid, r * r = a ball of radius r fits); seeds (S,)
+    int32 flat indices, those out of range or not passable are no sources (decided on the device); connectivity 6, 18 or 26; steps
+    = the integer costs >= 1 of a face, an edge and a corner move; rounds: the number of relaxation rounds = launches, None =
+    geodesic_default_rounds(counts); parent: also each point's predecessor.  resume: the cost tensor of an earlier call with the same
+    arguments, relaxed further IN PLACE (seeds is not read).  `out` = (cost, status, parent or None), `work`: the caller's
+    contiguous int32 buffers (>= n, >= 2, >= n, >= geodesic_work_len(rounds) elements).
+    -> (cost (n,) int32, GEODESIC_CONSTANTS['NONE'] where no path arrives; status (2,) int32: 1 iff a round changed nothing -- cost
+    is then THE shortest-path cost --, and the rounds that changed something; parent (n,) int32, -1 at seeds and unreached points,
+    or None), on the device.  rounds + 2 launches, one more with parent, whatever the data.  No host read."""
+    nx, ny, nz = (int(c) for c in counts)
+    n = max(nx * ny * nz, 0)
+    c, _ = _inst_column(clear, n, 'clear', torch.int32)
+    c = c if c.is_contiguous() else c.contiguous()
+    rounds = geodesic_default_rounds((nx, ny, nz)) if rounds is None else int(rounds)
+    face, edge, corner = (int(s) for s in steps)
+    if resume is None:
+        s = _dev(seeds, torch.int32, 'seeds')
+        assert s.dim() == 1, 'seeds must be (S,), got %s' % (tuple(s.shape),)
+        s = s if s.is_contiguous() else s.contiguous()
+    else:
+        assert out is None or out[0] is None, 'resume is relaxed in place: out must not hold a cost buffer'
+        s = None
+    out = (None, None, None) if out is None else out
+    assert parent or out[2] is None, 'out holds a parent buffer without parent=True'
+    cost = _int32_out(out[0] if resume is None else resume, (n,), c.device, 'resume' if resume is not None else 'out cost')
+    status = _int32_out(out[1], (2,), c.device, 'out status')
+    up = _int32_out(out[2], (n,), c.device, 'out parent') if parent else None
+    wk = _int32_out(work, (geodesic_work_len(max(rounds, 0)),), c.device, 'work')
+    if n == 0:
+        status.zero_()                   # (the entry point touches no pointer of an empty grid)
+    _lib.check(_lib.lib().occ4d_geodesic_grid_i32(_ptr(c), int(min_clear), nx, ny, nz, _ptr(s), 0 if s is None else s.shape[0],
+                                                  int(connectivity), face, edge, corner, rounds, 0 if resume is None else 1, _ptr(wk),
+                                                  _ptr(cost), _ptr(up), _ptr(status), _stream()))
+    return cost, status, up
+
+
+def geodesic_trace(cost, parent, goals, cap, out=None):
+    """The paths from `goals` (G,) int32 flat indices back to a seed along `parent` (occ4d_geodesic_trace_i32): cost, parent (n,)
+    int32 of ops.grid_geodesic(parent=True), cap: the most points of a path.  `out` = (paths, path_len): the caller's contiguous
+    int32 buffers (>= G * cap, >= G).  -> (paths (G, cap) int32: goal first, the seed last, -1 behind it; path_len (G,) int32: the
+    number of points, 0 for a goal that is out of range or unreached, -needed when the path has more than cap points), on the
+    device.  One launch, one serial chain per goal.  No host read."""
+    c = _dev(cost, torch.int32, 'cost')
+    p = _dev(parent, torch.int32, 'parent')
+    g = _dev(goals, torch.int32, 'goals')
+    assert c.dim() == 1 and p.shape == c.shape and c.is_contiguous() and p.is_contiguous(), \
+        'cost and parent must be contiguous (n,) tensors of one length, got %s and %s' % (tuple(c.shape), tuple(p.shape))
+    assert g.dim() == 1, 'goals must be (G,), got %s' % (tuple(g.shape),)
+    g = g if g.is_contiguous() else g.contiguous()
+    cap = int(cap)
+    out = (None, None) if out is None else out
+    paths = _int32_out(out[0], (g.shape[0], max(cap, 0)), c.device, 'out paths')
+    path_len = _int32_out(out[1], (g.shape[0],), c.device, 'out path_len')
+    _lib.check(_lib.lib().occ4d_geodesic_trace_i32(_ptr(c), _ptr(p), c.shape[0], _ptr(g), g.shape[0], cap, _ptr(paths), _ptr(path_len),
+                                                   _stream()))
+    return paths, path_len
+
+
 def link_work_len(n, cap):
     """Elements of the int32 work array of occ4d_link_overlap_i32 for n grid points and `cap` pair rows (the formula of the
     header): 4 * slots + n + 2 * tiles with slots the smallest power of two >= max(2 * min(cap, n), MIN_SLOTS), at most 2^31."""
