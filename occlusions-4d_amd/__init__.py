@@ -12,6 +12,7 @@ from . import _lib  # noqa: F401
 from . import kernels  # noqa: F401   (`with occlusions4d_amd.kernels(precision='bf16x6'):` -- per-thread kernel selection)
 from . import ops  # noqa: F401
 from . import autograd  # noqa: F401
+from . import products  # noqa: F401   (what the grid options of perform_inference share: Grid, GridProduct, columns)
 from . import surface  # noqa: F401   (the occupancy surface as a quad mesh: Surface, extract, write_ply)
 from . import point_transformer_layer, modules, model, geometry, implicit, inference, distributed, training  # noqa: F401
 from . import evaluation  # noqa: F401

@@ -15,23 +15,22 @@ it on the host in float64 (boxes_and_centroids)."""
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, products
 
 CONNECTIVITIES = (6, 18, 26)
 
 
-class Components:
-    """The option object of perform_inference(components=...) / evaluate_clip(components=...).  level: the density from which a
-    query is solid (density >= level, the comparison of the solid split), None = the call's density_threshold; connectivity: 6, 18
-    or 26; select = (column, threshold) or None: members also need implicit_output[:, column] >= threshold (with the track
+class Components(products.LevelProduct):
+    """The option object of perform_inference(components=...) / evaluate_clip(components=..., objects=[]).  level: the density from
+    which a query is solid (density >= level, the comparison of the solid split), None = the call's density_threshold; connectivity:
+    6, 18 or 26; select = (column, threshold) or None: members also need implicit_output[:, column] >= threshold (with the track
     channel: the tracked object alone); by_class: neighbours must share their semantic class (the argmax of the semantic columns,
-    first maximum wins; needs predict_segmentation); min_size: components of fewer points are dropped."""
+    first maximum wins; needs predict_segmentation); min_size: components of fewer points are dropped.  The product: dict(labels
+    (N,) int32, table (K, 12) int64) (label); one 12-byte device->host read sizes the table."""
+    keyword, clip_list = 'components', ('objects', 'one dict of labels and table')
 
     def __init__(self, level=None, connectivity=6, select=None, by_class=False, min_size=1):
-        if level is not None:
-            level = float(level)
-            if level != level:
-                raise ValueError('Components: level is NaN')
+        level = self._level(level)
         if isinstance(connectivity, bool) or connectivity not in CONNECTIVITIES:
             raise ValueError('Components: connectivity = %r must be 6, 18 or 26' % (connectivity,))
         if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)) or not 1 <= min_size <= 2 ** 31 - 1:
@@ -39,11 +38,17 @@ class Components:
         self.level, self.connectivity, self.min_size, self.by_class = level, int(connectivity), int(min_size), bool(by_class)
         self.select = None if select is None else (int(select[0]), float(select[1]))
 
-    def resolve(self, density_threshold):
-        level = float(density_threshold) if self.level is None else self.level
-        if level != level:
-            raise ValueError('Components: level is NaN')
-        return level
+    def prepare(self, grid):
+        if self.by_class and not grid.predict_segmentation:
+            raise ValueError('components with by_class=True needs predict_segmentation=True')
+        return self.resolve(grid.density_threshold)
+
+    def run(self, grid, level, made):
+        out, klass = grid.output, None
+        if self.by_class:
+            klass = semantic_class(out, out.shape[1] - grid.semantic_classes, grid.semantic_classes)
+        labels, table = label(out, grid.counts, level, self.connectivity, self.select, klass, self.min_size)
+        return dict(labels=labels, table=table)
 
     def __repr__(self):
         return 'Components(level=%r, connectivity=%d, select=%r, by_class=%r, min_size=%d)' % (
@@ -57,14 +62,8 @@ def label(implicit_output, counts, level, connectivity=6, select=None, klass=Non
     level = float(level)
     if level != level:
         raise ValueError('components.label: level is NaN')
-    out = implicit_output
-    assert out.dim() == 2 and 0 <= channel < out.shape[1], 'channel = %r' % (channel,)
-    mask, mask_level = None, 0.0
-    if select is not None:
-        column, mask_level = int(select[0]), float(select[1])
-        assert 0 <= column < out.shape[1], 'select column = %r' % (column,)
-        mask = out[:, column]
-    labels, _, table = ops.grid_components(out[:, channel], counts, level, connectivity, min_size, mask, mask_level, klass)
+    values, mask, mask_level = products.columns(implicit_output, channel, select)
+    labels, _, table = ops.grid_components(values, counts, level, connectivity, min_size, mask, mask_level, klass)
     return labels, table
 
 
@@ -75,13 +74,16 @@ def semantic_class(implicit_output, first, n_classes):
     return torch.argmax(implicit_output[:, first:first + n_classes], dim=1).to(torch.int32)
 
 
-class Tracker:
+class Tracker(products.GridProduct):
     """Links the components of consecutive output frames on the device (include/ext/occ4d_link.h): the option object of
     perform_inference(components=..., tracker=...) / evaluate_clip(..., tracker=...).  Component b of a frame continues component a
     of the frame before when each is the other's best overlap by intersection over union and that is >= min_iou (a float, or an
-    exact (num, den) pair); it then keeps a's track id, and every other component takes the next free id, in order.
+    exact (num, den) pair); it then keeps a's track id, and every other component takes the next free id, in order.  The product
+    joins the components' dict: link (K, 4) int32 (add_frame), made from that call's labels and table.
 
     The previous frame's labels, table and track ids and the id counter stay on the device; add_frame reads nothing back."""
+    keyword, into, reads_grid = 'tracker', 'components', False
+    needs = ('components', 'tracker needs components=<a components.Components>: it links the components of consecutive frames')
 
     def __init__(self, min_iou=0.0):
         num, den = ops._min_iou_fraction(min_iou)
@@ -109,6 +111,9 @@ class Tracker:
         link, _, self.next = ops.components_match(pairs, totals, self.table, table, self.track, self.next, self.min_iou)
         self.labels, self.table, self.track = labels, table, link[:, 0].contiguous()
         return link
+
+    def run(self, grid, prepared, made):
+        return dict(link=self.add_frame(made['components']['labels'], made['components']['table']))
 
     def n_tracks(self):
         """The number of track ids handed out so far: the one host read."""

@@ -20,7 +20,7 @@ points_query, whatever the weights."""
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, products
 
 NONE = _lib.DISTANCE_CONSTANTS['NONE']
 
@@ -35,27 +35,22 @@ def _weights(weights, who):
     return tuple(int(x) for x in w)
 
 
-class Clearance:
-    """The option object of perform_inference(clearance=...) / evaluate_clip(clearance=...).  level: the density from which a query
-    is solid (density >= level, the comparison of the solid split), None = the call's density_threshold; select = (column,
-    threshold) or None: solid queries also need implicit_output[:, column] >= threshold (with the track channel: the tracked
-    object alone); weights: three integers >= 1 (the module's doc-string); nearest: also the flat index of the nearest solid
-    query; inside: also inside2, the squared distance to the nearest query that is not solid."""
+class Clearance(products.LevelProduct):
+    """The option object of perform_inference(clearance=...) / evaluate_clip(clearance=..., clearances=[]).  level: the density from
+    which a query is solid (density >= level, the comparison of the solid split), None = the call's density_threshold; select =
+    (column, threshold) or None: solid queries also need implicit_output[:, column] >= threshold (with the track channel: the
+    tracked object alone); weights: three integers >= 1 (the module's doc-string); nearest: also the flat index of the nearest
+    solid query; inside: also inside2, the squared distance to the nearest query that is not solid.  The product: dict(dist2 (N,)
+    int32[, nearest (N,) int32][, inside2 (N,) int32]) (transform); no device value is read."""
+    keyword, clip_list = 'clearance', ('clearances', 'one dict of distances')
 
     def __init__(self, level=None, select=None, weights=(1, 1, 1), nearest=False, inside=False):
-        if level is not None:
-            level = float(level)
-            if level != level:
-                raise ValueError('Clearance: level is NaN')
-        self.level, self.weights = level, _weights(weights, 'Clearance')
+        self.level, self.weights = self._level(level), _weights(weights, 'Clearance')
         self.select = None if select is None else (int(select[0]), float(select[1]))
         self.nearest, self.inside = bool(nearest), bool(inside)
 
-    def resolve(self, density_threshold):
-        level = float(density_threshold) if self.level is None else self.level
-        if level != level:
-            raise ValueError('Clearance: level is NaN')
-        return level
+    def run(self, grid, level, made):
+        return transform(grid.output, grid.counts, level, self.select, self.weights, self.nearest, self.inside)
 
     def __repr__(self):
         return 'Clearance(level=%r, select=%r, weights=%r, nearest=%r, inside=%r)' % (
@@ -70,19 +65,13 @@ def transform(implicit_output, counts, level, select=None, weights=(1, 1, 1), ne
     if level != level:
         raise ValueError('distance.transform: level is NaN')
     weights = _weights(weights, 'distance.transform')
-    out = implicit_output
-    assert out.dim() == 2 and 0 <= channel < out.shape[1], 'channel = %r' % (channel,)
-    mask, mask_level = None, 0.0
-    if select is not None:
-        column, mask_level = int(select[0]), float(select[1])
-        assert 0 <= column < out.shape[1], 'select column = %r' % (column,)
-        mask = out[:, column]
-    dist2, site = ops.grid_distance(out[:, channel], counts, level, weights, 0, mask, mask_level, nearest)
+    values, mask, mask_level = products.columns(implicit_output, channel, select)
+    dist2, site = ops.grid_distance(values, counts, level, weights, 0, mask, mask_level, nearest)
     result = dict(dist2=dist2)
     if nearest:
         result['nearest'] = site
     if inside:
-        result['inside2'] = ops.grid_distance(out[:, channel], counts, level, weights, 1, mask, mask_level, False)[0]
+        result['inside2'] = ops.grid_distance(values, counts, level, weights, 1, mask, mask_level, False)[0]
     return result
 
 

@@ -27,7 +27,9 @@ from . import distance as distance_mod
 from . import geodesic as geodesic_mod
 from . import inference
 from . import ops
+from . import products
 from . import projection
+from . import surface as surface_mod
 
 _EC = _lib.EVAL_CONSTANTS
 # target columns (R; G, B follow / mark_track / semantic tag, -1 = absent) of the two data kinds (eval/inference.py:96):
@@ -342,44 +344,19 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
     inst_stats: an InstanceStats that every output frame is added to in the same way (track_mode 'all': the instance
     labelling); inst_group_fn(time_idx, frame_rows) -> (n_ids,) integer array: the group of every instance id, None: group 0.
     refine: an inference.GridRefine handed to every perform_inference call (the coarse-to-fine decode of the query grid), or None.
-    surface: a surface.Surface handed to every perform_inference call, or None; `meshes`: the list every output frame's
-    result['surface'] = dict(vertices, faces) is appended to (the tuples of pcl_all keep their contract).  A surface without
-    such a list is a ValueError.
-    views: a projection.FieldViews handed to every perform_inference call, or None; `images`: the list every output frame's
-    result['views'] = dict(depth, cell, features) is appended to, in the same way.
-    components: a components.Components handed to every perform_inference call, or None; `objects`: the list every output frame's
-    result['components'] = dict(labels, table) is appended to, in the same way.
+    surface / meshes, views / images, components / objects, clearance / clearances, route / routes: a grid product's option object
+    (surface.Surface, projection.FieldViews, components.Components, distance.Clearance, geodesic.Route; `route` needs `clearance`)
+    handed to every perform_inference call, or None, and the list every output frame's result[keyword] dict is appended to (the
+    tuples of pcl_all keep their contract).  An option without such a list is a ValueError; all options are checked before the
+    first frame.
     tracker: a components.Tracker, or None (needs `components`): reset here, then handed to every perform_inference call, so that
     every dict of `objects` gains 'link' (K, 4), the frame's components linked to those of the output frame before
-    (components.tracks turns the list into trajectories).
-    clearance: a distance.Clearance handed to every perform_inference call, or None; `clearances`: the list every output frame's
-    result['clearance'] = dict(dist2[, nearest][, inside2]) is appended to, in the same way.
-    route: a geodesic.Route handed to every perform_inference call, or None (needs `clearance`); `routes`: the list every output
-    frame's result['route'] = dict(cost, status[, parent][, paths, path_len]) is appended to, in the same way."""
-    if route is not None:
-        if not isinstance(route, geodesic_mod.Route):
-            raise ValueError('route must be a geodesic.Route or None, got %r' % (route,))
-        if clearance is None:
-            raise ValueError('route needs clearance=<a distance.Clearance>: a query is passable when its dist2 >= route.min_clear')
-        if not isinstance(routes, list):
-            raise ValueError('evaluate_clip(route=...) needs routes=<a list>: one dict of costs and paths per output frame is appended to it')
-    if clearance is not None:
-        if not isinstance(clearance, distance_mod.Clearance):
-            raise ValueError('clearance must be a distance.Clearance or None, got %r' % (clearance,))
-        if not isinstance(clearances, list):
-            raise ValueError('evaluate_clip(clearance=...) needs clearances=<a list>: one dict of distances per output frame is appended to it')
+    (components.tracks turns the list into trajectories)."""
+    chosen = products.check_clip((
+        (geodesic_mod.Route, route, routes), (distance_mod.Clearance, clearance, clearances), (components_mod.Tracker, tracker, None),
+        (components_mod.Components, components, objects), (projection.FieldViews, views, images), (surface_mod.Surface, surface, meshes)))
     if tracker is not None:
-        if not isinstance(tracker, components_mod.Tracker):
-            raise ValueError('tracker must be a components.Tracker or None, got %r' % (tracker,))
-        if components is None:
-            raise ValueError('tracker needs components=<a components.Components>: it links the components of consecutive frames')
         tracker.reset()
-    if components is not None and not isinstance(objects, list):
-        raise ValueError('evaluate_clip(components=...) needs objects=<a list>: one dict of labels and table per output frame is appended to it')
-    if views is not None and not isinstance(images, list):
-        raise ValueError('evaluate_clip(views=...) needs images=<a list>: one dict of images per output frame is appended to it')
-    if surface is not None and not isinstance(meshes, list):
-        raise ValueError('evaluate_clip(surface=...) needs meshes=<a list>: one mesh per output frame is appended to it')
     assert stats_group_fn is None or stats_occlusion is None, 'stats_group_fn and stats_occlusion exclude each other'
     if stats_occlusion is not None and stats is not None:
         assert stats.n_groups >= 3, 'stats_occlusion needs an EvalStats with n_groups >= 3, got %d' % stats.n_groups
@@ -418,23 +395,16 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
             predict_segmentation=args.segmentation_lw > 0.0, track_mode=args.track_mode,
             point_occupancy_radius=args.point_occupancy_radius, semantic_classes=args.semantic_classes,
             density_threshold=args.density_threshold, data_kind=data_kind, cube_mode=args.cube_mode, compress_air=True,
-            encoded=encoded if reuse_encode else None, return_encoded=reuse_encode, refine=refine, surface=surface, views=views,
-            components=components, tracker=tracker, clearance=clearance, route=route, **stats_kw)
+            encoded=encoded if reuse_encode else None, return_encoded=reuse_encode, refine=refine,
+            **{option.keyword: option for option, _ in chosen}, **stats_kw)
         if reuse_encode:                  # (track_mode 'all': a dict with one encode per tracked instance)
             encoded = res.pop('_encoded')
         else:
             res.pop('_encoded', None)
-        if surface is not None:
-            meshes.append(res['surface'])
-        if views is not None:
-            images.append(res['views'])
-        if components is not None:
-            objects.append(res['components'])
-        if clearance is not None:
-            clearances.append(res['clearance'])
-        if route is not None:
-            routes.append(res['route'])
-        item = (pcl_input_numpy, res['pcl_abstract'], res['output_solid'], frame, res['output_air'])
+        for option, into in chosen:
+            if into is not None:
+                into.append(res[option.keyword])
+        item =(pcl_input_numpy, res['pcl_abstract'], res['output_solid'], frame, res['output_air'])
         if save_gt:
             item = item + (pcl_input_sem_numpy, res['points_query'])
         pcl_all.append(item)

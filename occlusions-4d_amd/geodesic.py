@@ -23,7 +23,7 @@ until it is (one 8-byte read per batch).  Inside perform_inference nothing is re
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, products
 
 NONE = _lib.GEODESIC_CONSTANTS['NONE']
 
@@ -72,12 +72,17 @@ def _indices(what, name):
     raise ValueError('Route: %s must be (S,) integer flat indices or (S, 3) world points, got shape %s of %s' % (name, a.shape, a.dtype))
 
 
-class Route:
-    """The option object of perform_inference(route=...) / evaluate_clip(route=...).  seeds, goals: (S,) integer flat indices of
-    the query grid or (S, 3) world points (turned into indices on the host with grid_index before the decode; one outside the grid
-    raises ValueError), goals None = no paths; min_clear: a query is passable when its clearance's dist2 >= min_clear; connectivity
-    6 / 18 / 26 and steps = (face, edge, corner) integer costs; rounds None = ops.geodesic_default_rounds; parent: also return each
-    query's predecessor (goals imply it on the device); path_cap: the most points of a path, None = four times the longest axis."""
+class Route(products.GridProduct):
+    """The option object of perform_inference(route=...) / evaluate_clip(route=..., routes=[]); needs `clearance`.  seeds, goals: (S,)
+    integer flat indices of the query grid or (S, 3) world points (turned into indices on the host with grid_index before the decode;
+    one outside the grid raises ValueError), goals None = no paths; min_clear: a query is passable when its clearance's dist2 >=
+    min_clear; connectivity 6 / 18 / 26 and steps = (face, edge, corner) integer costs; rounds None = ops.geodesic_default_rounds;
+    parent: also return each query's predecessor (goals imply it on the device); path_cap: the most points of a path, None = four
+    times the longest axis.  The product: dict(cost (N,) int32, status (2,) int32[, parent (N,) int32][, paths (G, cap) int32,
+    path_len (G,) int32]) over that call's clearance dist2 (solve with rounds given): a fixed number of launches and no device value
+    read, so status[0] == 1 -- the costs are converged, i.e. THE shortest -- has to be looked at."""
+    keyword, clip_list = 'route', ('routes', 'one dict of costs and paths')
+    needs = ('clearance', 'route needs clearance=<a distance.Clearance>: a query is passable when its dist2 >= route.min_clear')
 
     def __init__(self, seeds, goals=None, min_clear=1, connectivity=26, steps=(3, 4, 5), rounds=None, parent=False, path_cap=None):
         self.seeds = _indices(seeds, 'seeds')
@@ -101,6 +106,15 @@ class Route:
             return a if kind == 'flat' else grid_index(a, mins, spacings, counts).astype(np.int32)
         cap = self.path_cap if self.path_cap is not None else 4 * max(int(c) for c in counts)
         return flat(self.seeds), None if self.goals is None else flat(self.goals), cap
+
+    def prepare(self, grid):
+        return self.resolve(grid.counts, grid.mins, grid.spacings)
+
+    def run(self, grid, on_grid, made):
+        seeds, goals = (None if a is None else torch.from_numpy(a).to(grid.device) for a in on_grid[:2])
+        rounds = ops.geodesic_default_rounds(grid.counts) if self.rounds is None else self.rounds
+        return solve(made['clearance']['dist2'], grid.counts, seeds, goals, self.min_clear, self.connectivity, self.steps, rounds,
+                     self.parent, on_grid[2])
 
     def __repr__(self):
         return 'Route(seeds=<%s %s>, goals=%s, min_clear=%r, connectivity=%r, steps=%r, rounds=%r, parent=%r, path_cap=%r)' % (

@@ -19,6 +19,7 @@ from . import implicit
 from . import kernels
 from . import model
 from . import ops
+from . import products
 from . import projection
 from . import surface as surface_nets
 from . import components as components_mod
@@ -220,54 +221,32 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     dependence of a row on its place in the mini-batch decode_refined reproduces; under another kernels.Selection only within
     the mini-batch-split bound, 1e-5.)
 
-    Surface.  `surface`: a surface.Surface, or None.  point_sample_mode 'grid' only (ValueError).  The result gains 'surface' =
-    dict(vertices (V, 3 + G) float32, faces (F, 4) int32): the surface density == surface.level (None: density_threshold) of the
-    squashed -- in track_mode 'all' merged, under `refine` expanded -- (N, G) array as a quad mesh, extracted on the device
-    (surface.extract, include/occ4d_surface.h): x, y, z and all G columns per vertex, normals from solid to air, open at the
-    grid's faces.  One 8-byte device->host read sizes it; the two arrays come back with the others, under the one host wait.
-    Under `refine` with refine.low <= level, a cell whose eight corners all lie in inactive blocks is never crossed (their
-    densities are the representatives', below `low`): the mesh exists only where blocks were decoded.
-
-    Views.  `views`: a projection.FieldViews (cameras, image size, level, channels, select, step), or None.  point_sample_mode
-    'grid' only (ValueError).  The result gains 'views' = dict(depth (V, H, W) float32, cell (V, H, W) int32, features
-    (V, H, W, C) float32): the same squashed (N, G) array -- merged, expanded -- ray-cast into the cameras on the device
-    (projection.render_field, include/ext/occ4d_raycast.h): per pixel the first crossing of density == views.level (None:
-    density_threshold), 0 / -1 / 0 where a ray meets none.  No device value is read; the three arrays come back with the others,
-    under the one host wait.
-
-    Components.  `components`: a components.Components (level, connectivity, select, by_class, min_size), or None.
-    point_sample_mode 'grid' only (ValueError); by_class needs predict_segmentation (ValueError).  The result gains 'components' =
-    dict(labels (N,) int32, table (K, 12) int64): the connected components of density >= components.level (None:
-    density_threshold) of the same squashed (N, G) array -- merged, expanded --, labelled on the device (components.label,
-    include/ext/occ4d_components.h): per query its component's number or -1, per component size, root, class, coordinate sums,
-    minima and maxima (components.boxes_and_centroids turns them into world-space boxes).  One 12-byte device->host read sizes
-    the table; the two arrays come back with the others, under the one host wait.
-
-    Tracker.  `tracker`: a components.Tracker, or None; needs `components` (ValueError).  result['components'] gains 'link' (K, 4)
-    int32: per component its track id, the component of the tracker's previous frame it continues or -1, its best overlap there
-    or -1 and that overlap's points (include/ext/occ4d_link.h), made on the device from the labels and the table above and
-    fetched under the same host wait: no extra read.  The tracker then holds this frame.
-
-    Clearance.  `clearance`: a distance.Clearance (level, select, weights, nearest, inside), or None.  point_sample_mode 'grid'
-    only (ValueError).  The result gains 'clearance' = dict(dist2 (N,) int32[, nearest (N,) int32][, inside2 (N,) int32]): the exact
-    distance transform of density >= clearance.level (None: density_threshold) of the same squashed (N, G) array -- merged,
-    expanded --, on the device (distance.transform, include/ext/occ4d_distance.h): per query the squared distance, in weighted grid
-    steps, to the nearest solid query (2^31 - 1: there is none), the flat index of that query, and the squared distance to the
-    nearest query that is not solid.  No device value is read; the arrays come back with the others, under the one host wait.
-
-    Route.  `route` (in the signature it stands in front of `tracker`: the suite pins the last two names): a geodesic.Route (seeds,
-    goals, min_clear, connectivity, steps, rounds, parent, path_cap), or None; needs `clearance` and point_sample_mode 'grid'
-    (ValueError).  World-point seeds and goals become grid indices on the host before the decode (geodesic.grid_index; ValueError
-    outside the grid).  The result gains 'route' = dict(cost (N,) int32, status (2,) int32[, parent (N,) int32][, paths (G, cap)
-    int32, path_len (G,) int32]): the least step cost of a path from any seed to every query over the queries with clearance
-    dist2 >= route.min_clear -- that call's dist2: merged, expanded --, and the goals' paths back to a seed (geodesic.solve,
-    include/ext/occ4d_geodesic.h).  A fixed number of launches -- route.rounds (None: ops.geodesic_default_rounds) + 2, one more for
-    the predecessors and one for the paths -- and no device value read: status[0] == 1 says that the costs are converged, i.e. THE
-    shortest, and has to be looked at; the arrays come back with the others, under the one host wait."""
+    Grid products.  `surface`, `views`, `components`, `tracker`, `clearance`, `route`: option objects (products.GridProduct), or
+    None = nothing is called and no key is added.  point_sample_mode 'grid' only (ValueError).  Each turns the same squashed (N, G)
+    array -- in track_mode 'all' merged, under `refine` expanded -- into more arrays on the device, which come back with the others,
+    under the one host wait; the option class describes its arguments and its arrays.  They are checked, and run, in this order:
+    `surface`: a surface.Surface -> result['surface'] = dict(vertices, faces), the quad mesh of density == level.  Under `refine`
+    with refine.low <= level the mesh exists only where blocks were decoded (surface.py).
+    `views`: a projection.FieldViews -> result['views'] = dict(depth, cell, features), the array ray-cast into the cameras.
+    `components`: a components.Components -> result['components'] = dict(labels, table), the connected components of density >=
+    level; by_class needs predict_segmentation (ValueError).
+    `tracker`: a components.Tracker; needs `components` (ValueError) -> result['components'] gains 'link': the components linked
+    to those of the tracker's previous frame.  The tracker then holds this frame.
+    `clearance`: a distance.Clearance -> result['clearance'] = dict(dist2[, nearest][, inside2]), the exact distance transform of
+    density >= level.
+    `route` (in the signature it stands in front of `tracker`: the suite pins the last two names): a geodesic.Route; needs
+    `clearance` (ValueError) -> result['route'] = dict(cost, status[, parent][, paths, path_len]), the shortest free-space paths over
+    that call's dist2.  World-point seeds and goals become grid indices on the host before the decode (ValueError outside the
+    grid); status[0] == 1 says that the costs are converged and has to be looked at."""
     assert task == 'if'
     assert sample_implicit
     assert track_merge in ('device', 'host'), track_merge
-    grid_shape = None
+    slots = ((surface_nets.Surface, surface), (projection.FieldViews, views), (components_mod.Components, components),
+             (components_mod.Tracker, tracker), (distance_mod.Clearance, clearance), (geodesic_mod.Route, route))
+    grid = None                               # the very floats the query grid is generated from
+    if point_sample_mode == 'grid' and (refine is not None or any(option is not None for _, option in slots)):
+        grid = products.Grid(geometry.grid_frame(num_sample, min_z, cube_bounds, data_kind, cube_mode), density_threshold,
+                             predict_segmentation, semantic_classes, device)
     if refine is not None:
         if not isinstance(refine, GridRefine):
             raise ValueError('refine must be a GridRefine or None, got %r' % (refine,))
@@ -275,51 +254,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
             raise ValueError("refine needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
         if neighbour_lists is not None:
             raise ValueError('refine decodes gathered queries: neighbour_lists cannot be given with it')
-        grid_shape = geometry.grid_counts(num_sample, min_z, cube_bounds, data_kind, cube_mode)
-    surface_level = None
-    if surface is not None:
-        if not isinstance(surface, surface_nets.Surface):
-            raise ValueError('surface must be a surface.Surface or None, got %r' % (surface,))
-        if point_sample_mode != 'grid':
-            raise ValueError("surface needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
-        surface_level = surface.resolve(density_threshold)
-    views_level = None
-    if views is not None:
-        if not isinstance(views, projection.FieldViews):
-            raise ValueError('views must be a projection.FieldViews or None, got %r' % (views,))
-        if point_sample_mode != 'grid':
-            raise ValueError("views needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
-        views_level = views.resolve(density_threshold)
-    components_level = None
-    if components is not None:
-        if not isinstance(components, components_mod.Components):
-            raise ValueError('components must be a components.Components or None, got %r' % (components,))
-        if point_sample_mode != 'grid':
-            raise ValueError("components needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
-        if components.by_class and not predict_segmentation:
-            raise ValueError('components with by_class=True needs predict_segmentation=True')
-        components_level = components.resolve(density_threshold)
-    if tracker is not None:
-        if not isinstance(tracker, components_mod.Tracker):
-            raise ValueError('tracker must be a components.Tracker or None, got %r' % (tracker,))
-        if components is None:
-            raise ValueError('tracker needs components=<a components.Components>: it links the components of consecutive frames')
-    clearance_level = None
-    if clearance is not None:
-        if not isinstance(clearance, distance_mod.Clearance):
-            raise ValueError('clearance must be a distance.Clearance or None, got %r' % (clearance,))
-        if point_sample_mode != 'grid':
-            raise ValueError("clearance needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
-        clearance_level = clearance.resolve(density_threshold)
-    route_on_grid = None
-    if route is not None:
-        if not isinstance(route, geodesic_mod.Route):
-            raise ValueError('route must be a geodesic.Route or None, got %r' % (route,))
-        if point_sample_mode != 'grid':
-            raise ValueError("route needs point_sample_mode 'grid', got %r" % (point_sample_mode,))
-        if clearance is None:
-            raise ValueError('route needs clearance=<a distance.Clearance>: a query is passable when its dist2 >= route.min_clear')
-        route_on_grid = route.resolve(*geometry.grid_frame(num_sample, min_z, cube_bounds, data_kind, cube_mode))
+    plan = products.prepare(slots, grid, point_sample_mode)
     refine_stats = dict(n_queries=0, n_decoded=0)
     output_track_idx = get_track_idx(color_mode)
     input_inst_idx = 0 if data_kind == 'greater' else 1
@@ -358,7 +293,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
             res = infer_device(pcl_input, queries_dev, pcl_net, implicit_net, batch_size, color_mode,
                                predict_segmentation, track_mode, semantic_classes,
                                encoded=_encoded_for(encoded, inst_id), neighbour_lists=neighbour_lists,
-                               squash=collector.squash, refine=refine, grid_counts=grid_shape)
+                               squash=collector.squash, refine=refine, grid_counts=None if refine is None else grid.counts)
             encoded_out[inst_id] = (res['pcl_abstract'], res['features_global'])
             if refine is not None:
                 for k in refine_stats:
@@ -389,34 +324,12 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
         # the device, not by a host pass over the array)
         solid_h = copies.fetch(solid)
         air_h = copies.fetch(air, torch.float64 if compress_air else None)
-        if surface is not None:               # the very floats the query grid was generated from
-            mesh_h = [copies.fetch(t) for t in surface_nets.extract(
-                output_dev, *geometry.grid_frame(num_sample, min_z, cube_bounds, data_kind, cube_mode), surface_level)]
-        if views is not None:
-            views_h = [copies.fetch(t) for t in views.render(
-                output_dev, *geometry.grid_frame(num_sample, min_z, cube_bounds, data_kind, cube_mode), views_level)]
-        if components is not None:
-            klass = None
-            if components.by_class:
-                klass = components_mod.semantic_class(output_dev, output_dev.shape[1] - semantic_classes, semantic_classes)
-            components_dev = components_mod.label(
-                output_dev, geometry.grid_counts(num_sample, min_z, cube_bounds, data_kind, cube_mode), components_level,
-                components.connectivity, components.select, klass, components.min_size)
-            components_h = [copies.fetch(t) for t in components_dev]
-            if tracker is not None:
-                components_h.append(copies.fetch(tracker.add_frame(*components_dev)))
-        if clearance is not None:
-            clearance_dev = distance_mod.transform(
-                output_dev, geometry.grid_counts(num_sample, min_z, cube_bounds, data_kind, cube_mode), clearance_level,
-                clearance.select, clearance.weights, clearance.nearest, clearance.inside)
-            clearance_h = {k: copies.fetch(t) for k, t in clearance_dev.items()}
-        if route is not None:                 # (rounds given: a fixed number of launches and no read of the status)
-            route_counts = geometry.grid_counts(num_sample, min_z, cube_bounds, data_kind, cube_mode)
-            seeds_dev, goals_dev = (None if a is None else torch.from_numpy(a).to(device) for a in route_on_grid[:2])
-            route_h = {k: copies.fetch(t) for k, t in geodesic_mod.solve(
-                clearance_dev['dist2'], route_counts, seeds_dev, goals_dev, route.min_clear, route.connectivity, route.steps,
-                ops.geodesic_default_rounds(route_counts) if route.rounds is None else route.rounds, route.parent,
-                route_on_grid[2]).items()}
+        if grid is not None:
+            grid.output = output_dev
+        made, fetched = {}, []                # per product its device tensors; (result key, the handles of their copies)
+        for product, prepared in plan:
+            made[product.keyword] = product.run(grid, prepared, made)
+            fetched.append((product.into or product.keyword, {k: copies.fetch(t) for k, t in made[product.keyword].items()}))
         copies.wait()
         solid, air = copies.result(solid_h), copies.result(air_h)
         points_query = copies.result(points_query)
@@ -426,18 +339,8 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                   features_global=features_global, implicit_output=implicit_output, points_query=points_query)
     if refine is not None:
         result['refine'] = refine_stats
-    if surface is not None:
-        result['surface'] = dict(vertices=copies.result(mesh_h[0]), faces=copies.result(mesh_h[1]))
-    if views is not None:
-        result['views'] = dict(zip(('depth', 'cell', 'features'), (copies.result(h) for h in views_h)))
-    if components is not None:
-        result['components'] = dict(labels=copies.result(components_h[0]), table=copies.result(components_h[1]))
-        if tracker is not None:
-            result['components']['link'] = copies.result(components_h[2])
-    if clearance is not None:
-        result['clearance'] = {k: copies.result(h) for k, h in clearance_h.items()}
-    if route is not None:
-        result['route'] = {k: copies.result(h) for k, h in route_h.items()}
+    for key, handles in fetched:
+        result.setdefault(key, {}).update((k, copies.result(h)) for k, h in handles.items())
     if return_encoded:
         result['_encoded'] = encoded_out[-1] if -1 in encoded_out else encoded_out     # (a tuple for the one unmarked run)
     if gt_available:

@@ -19,7 +19,7 @@ The arithmetic equals the reference's numpy results bit for bit (tests/golden/pr
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, products
 
 VISIBLE, OCCLUDED, OUTSIDE = 0, 1, 2
 
@@ -150,17 +150,16 @@ def march_range(counts, mins, spacings, rt64, near=None, far=None, step=None):
     return near, step, n_steps
 
 
-class FieldViews:
-    """The option object of perform_inference(views=...) / evaluate_clip(views=...): the cameras cam_RT (V, 3, 4), cam_K (3, 3) or
-    (V, 3, 3) and the image size the decoded field is ray-cast into (render_field).  level: the density of the surface shown,
-    None = the call's density_threshold; channels: the output columns sampled at the hit; select = (column, threshold) or None;
-    step: the march's step in depth, None = half the smallest grid spacing.  The cameras are inverted here, once, on the host."""
+class FieldViews(products.LevelProduct):
+    """The option object of perform_inference(views=...) / evaluate_clip(views=..., images=[]): the cameras cam_RT (V, 3, 4), cam_K
+    (3, 3) or (V, 3, 3) and the image size the decoded field is ray-cast into (render_field).  level: the density of the surface
+    shown, None = the call's density_threshold; channels: the output columns sampled at the hit; select = (column, threshold) or
+    None; step: the march's step in depth, None = half the smallest grid spacing.  The cameras are inverted here, once, on the host.
+    The product: dict(depth (V, H, W) float32, cell (V, H, W) int32, features (V, H, W, C) float32); no device value is read."""
+    keyword, clip_list = 'views', ('images', 'one dict of images')
 
     def __init__(self, cam_RT, cam_K, height, width, level=None, channels=(), select=None, step=None):
-        if level is not None:
-            level = float(level)
-            if level != level:
-                raise ValueError('FieldViews: level is NaN')
+        level = self._level(level)
         self.rt_inv, self.k_inv, self.rt64 = invert_cameras(cam_RT, cam_K)
         self.height, self.width = int(height), int(width)
         if self.height < 0 or self.width < 0:
@@ -168,21 +167,15 @@ class FieldViews:
         self.level, self.channels, self.step = level, tuple(int(c) for c in channels), step
         self.select = None if select is None else (int(select[0]), float(select[1]))
 
-    def resolve(self, density_threshold):
-        level = float(density_threshold) if self.level is None else self.level
-        if level != level:
-            raise ValueError('FieldViews: level is NaN')
-        return level
+    def run(self, grid, level, made):
+        return dict(zip(('depth', 'cell', 'features'), self.render(grid.output, grid.counts, grid.mins, grid.spacings, level)))
 
     def render(self, implicit_output, counts, mins, spacings, level, channel=0, near=None, far=None, background=0.0):
         """-> (depth, cell, features) of implicit_output (N, G) on its device."""
         out = implicit_output
-        assert out.dim() == 2 and 0 <= channel < out.shape[1], 'channel = %r' % (channel,)
-        field = out[:, channel]
-        if self.select is not None:
-            column, threshold = self.select
-            assert 0 <= column < out.shape[1], 'select column = %r' % (column,)
-            field = torch.where(out[:, column] >= threshold, field, torch.zeros((), dtype=out.dtype, device=out.device))
+        field, mask, threshold = products.columns(out, channel, self.select)
+        if mask is not None:
+            field = torch.where(mask >= threshold, field, torch.zeros((), dtype=out.dtype, device=out.device))
         near, step, n_steps = march_range(counts, mins, spacings, self.rt64, near, far, self.step)
         rt_inv, k_inv = (torch.from_numpy(m).to(out.device) for m in (self.rt_inv, self.k_inv))
         return ops.raycast_grid(field, counts, mins, spacings, level, rt_inv, k_inv, self.height, self.width, near, step, n_steps,

@@ -12,25 +12,21 @@ in inactive blocks is never crossed (their densities are copies of the represent
 where blocks were decoded."""
 import numpy as np
 
-from . import ops
+from . import ops, products
 
 
-class Surface:
-    """The option object of perform_inference(surface=...) / evaluate_clip(surface=...).  level: the density at which the
-    surface is taken (inside = density >= level, the comparison of the solid split); None = the call's density_threshold."""
+class Surface(products.LevelProduct):
+    """The option object of perform_inference(surface=...) / evaluate_clip(surface=..., meshes=[]).  level: the density at which the
+    surface is taken (inside = density >= level, the comparison of the solid split); None = the call's density_threshold.  The
+    product: dict(vertices (V, 3 + G) float32, faces (F, 4) int32) (extract); one 8-byte device->host read sizes it."""
+    keyword, clip_list = 'surface', ('meshes', 'one mesh')
 
     def __init__(self, level=None):
-        if level is not None:
-            level = float(level)
-            if level != level:
-                raise ValueError('Surface: level is NaN')
-        self.level = level
+        self.level = self._level(level)
 
-    def resolve(self, density_threshold):
-        level = float(density_threshold) if self.level is None else self.level
-        if level != level:
-            raise ValueError('Surface: level is NaN')
-        return level
+    def run(self, grid, level, made):             # (the very floats the query grid was generated from)
+        vertices, faces = extract(grid.output, grid.counts, grid.mins, grid.spacings, level)
+        return dict(vertices=vertices, faces=faces)
 
     def __repr__(self):
         return 'Surface(level=%r)' % (self.level,)

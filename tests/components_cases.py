@@ -7,7 +7,6 @@ consecutive flat indices.  The grids below are chosen against the first: (6, 7, 
 every axis, (40, 24, 20) is 7 x 4 x 4 tiles with no axis a multiple of its tile edge (40 = 6 * 6 + 4, 24 = 3 * 7 + 3, 20 = 3 * 6 + 2);
 (2, 3, 70) has z-runs longer than a wave, and 420 points: two numbering tiles."""
 import functools
-import types
 
 import numpy as np
 import pytest
@@ -412,13 +411,7 @@ def check_end_to_end(shared):
 def check_clip(shared):
     """evaluate_clip(components=..., objects=[]) over two frames: one dict per frame, that of the perform_inference call."""
     pcl, sem, target, inf, enc, dec = shared.inputs
-    frames = [target, target[:257] * np.float32(0.5)]
-    batch = dict(pcl_input=pcl, pcl_input_sem=torch.from_numpy(sem)[None], pcl_target=[torch.from_numpy(f)[None] for f in frames],
-                 meta_data=dict(pcl_target_size=[torch.tensor([f.shape[0]]) for f in frames]))
-    args = types.SimpleNamespace(min_z=inf['min_z'], cr_cube_bounds=inf['cube_bounds'], color_mode=inf['color_mode'],
-                                 sample_implicit=True, num_sample=rc.CASE['num_sample'], point_sample_mode='grid',
-                                 implicit_batch_size=rc.CASE['batch_size'], segmentation_lw=0.0, track_mode='none',
-                                 point_occupancy_radius=0.8, semantic_classes=13, density_threshold=0.5, cube_mode=4)
+    frames, batch, args = rc.clip_inputs(shared)
     objects = []
     option = pk.components.Components(connectivity=26)
     clip = pk.evaluation.evaluate_clip(batch, [enc, dec], shared.device, args, 'greater', save_gt=True, components=option, objects=objects)
@@ -435,13 +428,6 @@ def check_clip(shared):
 
 def check_none_is_untouched(shared, monkeypatch):
     """components=None: no new key, the entry points are not called; with components still one host wait."""
-    calls = dict(wait=0)
-    wait = pk.inference._HostCopies.wait
-
-    def counted_wait(self):
-        calls['wait'] += 1
-        return wait(self)
-
     def forbidden(*a, **k):
         raise AssertionError('components=None must not reach the labelling')
     monkeypatch.setattr(pk.ops, 'grid_components', forbidden)
@@ -452,7 +438,7 @@ def check_none_is_untouched(shared, monkeypatch):
     assert 'components' not in res
     rc.same_result(res, shared.dense)
     monkeypatch.undo()
-    monkeypatch.setattr(pk.inference._HostCopies, 'wait', counted_wait)
+    calls = rc.count_waits(monkeypatch)
     rc.infer(shared.device, shared.inputs, components=pk.components.Components())
     assert calls['wait'] == 1
 

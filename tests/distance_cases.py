@@ -10,7 +10,6 @@ TILES.  The launcher of csrc/distance.hip works on tiles of whole lines whose wi
 IMPORTED from there (never copied): for every width T the launcher has, a grid whose lines select it and whose `inner` extent is
 T - 1, T and T + 1, for the y stage (inner = nz) and for the x stage (inner = ny * nz)."""
 import functools
-import types
 
 import numpy as np
 import pytest
@@ -357,13 +356,7 @@ def check_end_to_end(shared):
 def check_clip(shared):
     """evaluate_clip(clearance=..., clearances=[]) over two frames: one dict per frame, that of the perform_inference call."""
     pcl, sem, target, inf, enc, dec = shared.inputs
-    frames = [target, target[:257] * np.float32(0.5)]
-    batch = dict(pcl_input=pcl, pcl_input_sem=torch.from_numpy(sem)[None], pcl_target=[torch.from_numpy(f)[None] for f in frames],
-                 meta_data=dict(pcl_target_size=[torch.tensor([f.shape[0]]) for f in frames]))
-    args = types.SimpleNamespace(min_z=inf['min_z'], cr_cube_bounds=inf['cube_bounds'], color_mode=inf['color_mode'],
-                                 sample_implicit=True, num_sample=rc.CASE['num_sample'], point_sample_mode='grid',
-                                 implicit_batch_size=rc.CASE['batch_size'], segmentation_lw=0.0, track_mode='none',
-                                 point_occupancy_radius=0.8, semantic_classes=13, density_threshold=0.5, cube_mode=4)
+    frames, batch, args = rc.clip_inputs(shared)
     clearances = []
     option = pk.distance.Clearance(nearest=True)
     clip = pk.evaluation.evaluate_clip(batch, [enc, dec], shared.device, args, 'greater', save_gt=True, clearance=option, clearances=clearances)
@@ -382,13 +375,6 @@ def check_clip(shared):
 
 def check_none_is_untouched(shared, monkeypatch):
     """clearance=None: no new key, the entry point is not called; with a clearance still one host wait."""
-    calls = dict(wait=0)
-    wait = pk.inference._HostCopies.wait
-
-    def counted_wait(self):
-        calls['wait'] += 1
-        return wait(self)
-
     def forbidden(*a, **k):
         raise AssertionError('clearance=None must not reach the distance transform')
     monkeypatch.setattr(pk.ops, 'grid_distance', forbidden)
@@ -399,7 +385,7 @@ def check_none_is_untouched(shared, monkeypatch):
     assert 'clearance' not in res
     rc.same_result(res, shared.dense)
     monkeypatch.undo()
-    monkeypatch.setattr(pk.inference._HostCopies, 'wait', counted_wait)
+    calls = rc.count_waits(monkeypatch)
     rc.infer(shared.device, shared.inputs, clearance=pk.distance.Clearance(nearest=True, inside=True))
     assert calls['wait'] == 1
 

@@ -12,7 +12,6 @@ TILES.  The kernel relaxes tiles whose shape is IMPORTED from the header's const
 extent is tile - 1, tile, tile + 1 and 2 tile + 1."""
 import functools
 import heapq
-import types
 
 import numpy as np
 import pytest
@@ -645,13 +644,7 @@ def check_end_to_end(shared):
 def check_clip(shared):
     """evaluate_clip(clearance=..., route=..., routes=[]) over two frames: one dict per frame, that of the perform_inference call."""
     pcl, sem, target, inf, enc, dec = shared.inputs
-    frames = [target, target[:257] * np.float32(0.5)]
-    batch = dict(pcl_input=pcl, pcl_input_sem=torch.from_numpy(sem)[None], pcl_target=[torch.from_numpy(f)[None] for f in frames],
-                 meta_data=dict(pcl_target_size=[torch.tensor([f.shape[0]]) for f in frames]))
-    args = types.SimpleNamespace(min_z=inf['min_z'], cr_cube_bounds=inf['cube_bounds'], color_mode=inf['color_mode'],
-                                 sample_implicit=True, num_sample=rc.CASE['num_sample'], point_sample_mode='grid',
-                                 implicit_batch_size=rc.CASE['batch_size'], segmentation_lw=0.0, track_mode='none',
-                                 point_occupancy_radius=0.8, semantic_classes=13, density_threshold=0.5, cube_mode=4)
+    frames, batch, args = rc.clip_inputs(shared)
     seeds, goals = fixture_points(shared)
     route = pk.geodesic.Route(seeds, goals)
     clearances, routes = [], []
@@ -676,13 +669,6 @@ def check_clip(shared):
 def check_none_is_untouched(shared, monkeypatch):
     """route=None: no new key, neither entry point is called, the result is that of the call without it; with a route still one
     host wait, and exactly the two library calls."""
-    calls = dict(wait=0, launched=[])
-    wait = pk.inference._HostCopies.wait
-
-    def counted_wait(self):
-        calls['wait'] += 1
-        return wait(self)
-
     def forbidden(*a, **k):
         raise AssertionError('route=None must not reach the geodesic entry points')
     for name in ('grid_geodesic', 'geodesic_trace'):
@@ -698,6 +684,8 @@ def check_none_is_untouched(shared, monkeypatch):
     assert sorted(res) == sorted(shared.dense)
     rc.same_result(res, shared.dense)
     monkeypatch.undo()
+    calls = rc.count_waits(monkeypatch)
+    calls['launched'] = []
 
     def recorded(name, fn):
         def call(*a, **k):
@@ -706,7 +694,6 @@ def check_none_is_untouched(shared, monkeypatch):
         return call
     for name in SYMBOLS:
         monkeypatch.setattr(L, name, recorded(name, getattr(L, name)))
-    monkeypatch.setattr(pk.inference._HostCopies, 'wait', counted_wait)
     seeds, goals = fixture_points(shared)
     rc.infer(shared.device, shared.inputs, clearance=pk.distance.Clearance(), route=pk.geodesic.Route(seeds, goals, parent=True))
     assert calls['wait'] == 1 and calls['launched'] == SYMBOLS

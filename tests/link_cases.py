@@ -436,15 +436,8 @@ def check_end_to_end(shared):
 def check_clip(shared):
     """evaluate_clip(components=..., objects=[], tracker=...) over three frames: the tracker is reset first, every dict gains
     `link`, the tuples of pcl_all keep their contract."""
-    import types
     pcl, sem, target, inf, enc, dec = shared.inputs
-    frames = [target, target[:257] * np.float32(0.5), target]
-    batch = dict(pcl_input=pcl, pcl_input_sem=torch.from_numpy(sem)[None], pcl_target=[torch.from_numpy(f)[None] for f in frames],
-                 meta_data=dict(pcl_target_size=[torch.tensor([f.shape[0]]) for f in frames]))
-    args = types.SimpleNamespace(min_z=inf['min_z'], cr_cube_bounds=inf['cube_bounds'], color_mode=inf['color_mode'],
-                                 sample_implicit=True, num_sample=rc.CASE['num_sample'], point_sample_mode='grid',
-                                 implicit_batch_size=rc.CASE['batch_size'], segmentation_lw=0.0, track_mode='none',
-                                 point_occupancy_radius=0.8, semantic_classes=13, density_threshold=0.5, cube_mode=4)
+    frames, batch, args = rc.clip_inputs(shared, n_frames=3)
     option, tracker = pk.components.Components(connectivity=26), pk.components.Tracker(min_iou=(1, 3))
     tracker.add_frame(torch.zeros(5, dtype=torch.int32, device=shared.device), torch.full((1, 12), 5, dtype=torch.int64, device=shared.device))
     objects = []
@@ -470,13 +463,6 @@ def check_clip(shared):
 def check_none_is_untouched(shared, monkeypatch):
     """tracker=None: the result's keys and arrays are exactly those of before, the entry points are not called; with a tracker
     still one host wait."""
-    calls = dict(wait=0)
-    wait = pk.inference._HostCopies.wait
-
-    def counted_wait(self):
-        calls['wait'] += 1
-        return wait(self)
-
     def forbidden(*a, **k):
         raise AssertionError('tracker=None must not reach the linking')
     before = rc.infer(shared.device, shared.inputs, components=pk.components.Components())
@@ -492,7 +478,7 @@ def check_none_is_untouched(shared, monkeypatch):
     rc.same_result({k: v for k, v in res.items() if k != 'components'}, shared.dense)
     assert 'components' not in rc.infer(shared.device, shared.inputs)
     monkeypatch.undo()
-    monkeypatch.setattr(pk.inference._HostCopies, 'wait', counted_wait)
+    calls = rc.count_waits(monkeypatch)
     rc.infer(shared.device, shared.inputs, components=pk.components.Components(), tracker=pk.components.Tracker())
     assert calls['wait'] == 1
 

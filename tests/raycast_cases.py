@@ -8,7 +8,6 @@ The ray setup goes through libm's fmaf, one scalar at a time (as tests/project_c
 the rays with masks."""
 import ctypes
 import ctypes.util
-import types
 
 import numpy as np
 import pytest
@@ -609,13 +608,7 @@ def check_clip(shared):
     """evaluate_clip(views=..., images=[]) over two frames: one dict per frame, that of the perform_inference call."""
     device = shared.device
     pcl, sem, target, inf, enc, dec = shared.inputs
-    frames = [target, target[:257] * F32(0.5)]
-    batch = dict(pcl_input=pcl, pcl_input_sem=torch.from_numpy(sem)[None], pcl_target=[torch.from_numpy(f)[None] for f in frames],
-                 meta_data=dict(pcl_target_size=[torch.tensor([f.shape[0]]) for f in frames]))
-    args = types.SimpleNamespace(min_z=inf['min_z'], cr_cube_bounds=inf['cube_bounds'], color_mode=inf['color_mode'],
-                                 sample_implicit=True, num_sample=rc.CASE['num_sample'], point_sample_mode='grid',
-                                 implicit_batch_size=rc.CASE['batch_size'], segmentation_lw=0.0, track_mode='none',
-                                 point_occupancy_radius=0.8, semantic_classes=13, density_threshold=0.5, cube_mode=4)
+    frames, batch, args = rc.clip_inputs(shared)
     views = fixture_views(shared, channels=(0, 1))
     images = []
     clip = pk.evaluation.evaluate_clip(batch, [enc, dec], device, args, 'greater', save_gt=True, views=views, images=images)
@@ -638,16 +631,10 @@ def check_clip(shared):
 def check_none_is_untouched(shared, monkeypatch):
     """views=None: no new key, the one host wait, the entry point is not called, implicit_output bit-identical; with views still
     one wait."""
-    calls = dict(wait=0)
-    wait = pk.inference._HostCopies.wait
-
-    def counted_wait(self):
-        calls['wait'] += 1
-        return wait(self)
+    calls = rc.count_waits(monkeypatch)
 
     def forbidden(*a, **k):
         raise AssertionError('views=None must not reach the ray cast')
-    monkeypatch.setattr(pk.inference._HostCopies, 'wait', counted_wait)
     monkeypatch.setattr(pk.ops, 'raycast_grid', forbidden)
     L = pk._lib.lib()
     for name in pk._lib.RAYCAST_SIGNATURES:
@@ -658,8 +645,7 @@ def check_none_is_untouched(shared, monkeypatch):
                            'points_query']
     same_result(res, shared.dense)
     monkeypatch.undo()
-    calls['wait'] = 0
-    monkeypatch.setattr(pk.inference._HostCopies, 'wait', counted_wait)
+    calls = rc.count_waits(monkeypatch)
     rc.infer(shared.device, shared.inputs, views=fixture_views(shared))
     assert calls['wait'] == 1
 

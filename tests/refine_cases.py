@@ -306,6 +306,32 @@ class Shared:
         self.dense_all = infer(device, self.inputs, track_mode='all')
 
 
+def clip_inputs(shared, n_frames=2):
+    """The clip the check_clip of every cases module runs evaluate_clip over -> (frames, batch, args): the target frame, its first
+    257 rows scaled by a half and, as a third frame, the target again."""
+    pcl, sem, target, inf, enc, dec = shared.inputs
+    frames = [target, target[:257] * F32(0.5), target][:n_frames]
+    batch = dict(pcl_input=pcl, pcl_input_sem=torch.from_numpy(sem)[None], pcl_target=[torch.from_numpy(f)[None] for f in frames],
+                 meta_data=dict(pcl_target_size=[torch.tensor([f.shape[0]]) for f in frames]))
+    args = types.SimpleNamespace(min_z=inf['min_z'], cr_cube_bounds=inf['cube_bounds'], color_mode=inf['color_mode'],
+                                 sample_implicit=True, num_sample=CASE['num_sample'], point_sample_mode='grid',
+                                 implicit_batch_size=CASE['batch_size'], segmentation_lw=0.0, track_mode='none',
+                                 point_occupancy_radius=0.8, semantic_classes=13, density_threshold=0.5, cube_mode=4)
+    return frames, batch, args
+
+
+def count_waits(monkeypatch):
+    """Counts the host waits of the calls that follow -> the dict whose 'wait' counts them (monkeypatch.undo() ends the count)."""
+    calls = dict(wait=0)
+    wait = pk.inference._HostCopies.wait
+
+    def counted_wait(self):
+        calls['wait'] += 1
+        return wait(self)
+    monkeypatch.setattr(pk.inference._HostCopies, 'wait', counted_wait)
+    return calls
+
+
 def check_single_run(shared, dilate):
     """track_mode 'none' with GridRefine(2, 0.46, dilate) against the restatement applied to the dense call's output."""
     dense = shared.dense
@@ -383,15 +409,9 @@ def check_clip(shared):
     """evaluate_clip(refine=...) over two frames = two perform_inference calls."""
     device = shared.device
     pcl, sem, target, inf, enc, dec = shared.inputs
-    frames = [target, target[:257] * F32(0.5)]
-    batch = dict(pcl_input=pcl, pcl_input_sem=torch.from_numpy(sem)[None], pcl_target=[torch.from_numpy(f)[None] for f in frames],
-                 meta_data=dict(pcl_target_size=[torch.tensor([f.shape[0]]) for f in frames]))
-    args = types.SimpleNamespace(min_z=inf['min_z'], cr_cube_bounds=inf['cube_bounds'], color_mode=inf['color_mode'],
-                                 sample_implicit=True, num_sample=CASE['num_sample'], point_sample_mode='grid',
-                                 implicit_batch_size=CASE['batch_size'], segmentation_lw=0.0, track_mode='none',
-                                 point_occupancy_radius=0.8, semantic_classes=13, density_threshold=0.5, cube_mode=4)
+    frames, batch, args = clip_inputs(shared)
     refine = pk.inference.GridRefine(2, 0.46, 1)
-    clip = pk.evaluation.evaluate_clip(batch, [enc, dec], device, args, 'greater', save_gt=True, refine=refine)
+    clip =pk.evaluation.evaluate_clip(batch, [enc, dec], device, args, 'greater', save_gt=True, refine=refine)
     dense = pk.evaluation.evaluate_clip(batch, [enc, dec], device, args, 'greater', save_gt=True)
     assert len(clip) == len(dense) == 2
     for t, frame in enumerate(frames):
@@ -409,17 +429,12 @@ def check_clip(shared):
 
 def check_none_is_untouched(shared, monkeypatch):
     """refine=None: the result keys and the one host wait are what they were; the refinement's entry points are never called."""
-    calls = dict(wait=0, refine=0)
-    wait = pk.inference._HostCopies.wait
-
-    def counted_wait(self):
-        calls['wait'] += 1
-        return wait(self)
+    calls = count_waits(monkeypatch)
+    calls['refine'] = 0
 
     def counted(*a, **k):
         calls['refine'] += 1
         raise AssertionError('refine=None must not reach the refinement')
-    monkeypatch.setattr(pk.inference._HostCopies, 'wait', counted_wait)
     for name in ('refine_mark', 'refine_expand', 'compact_rows_with_offsets'):
         monkeypatch.setattr(pk.ops, name, counted)
     res = infer(shared.device, shared.inputs, refine=None)
@@ -428,8 +443,7 @@ def check_none_is_untouched(shared, monkeypatch):
                            'points_query']
     same_result(res, shared.dense)
     monkeypatch.undo()
-    calls['wait'] = 0
-    monkeypatch.setattr(pk.inference._HostCopies, 'wait', counted_wait)
+    calls = count_waits(monkeypatch)
     infer(shared.device, shared.inputs, refine=pk.inference.GridRefine(2, 0.46, 1))
     assert calls['wait'] == 1                                          # (the refinement adds a count read, not a wait on the copies)
 

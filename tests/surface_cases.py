@@ -3,7 +3,6 @@ restatement of the surface-nets rules (include/occ4d_surface.h) in the stated op
 points, the guard of the data-dependent positions, the property checks that do not use the restatement, and the end-to-end
 comparisons of perform_inference(surface=...) on the tracking fixture.
 Everything but the properties is compared EQUAL: the non-NaN elements bit for bit, the NaN positions as positions."""
-import types
 
 import numpy as np
 import pytest
@@ -518,13 +517,7 @@ def check_clip(shared):
     """evaluate_clip(surface=..., meshes=[]) over two frames: one mesh per frame, that of the perform_inference call."""
     device = shared.device
     pcl, sem, target, inf, enc, dec = shared.inputs
-    frames = [target, target[:257] * F32(0.5)]
-    batch = dict(pcl_input=pcl, pcl_input_sem=torch.from_numpy(sem)[None], pcl_target=[torch.from_numpy(f)[None] for f in frames],
-                 meta_data=dict(pcl_target_size=[torch.tensor([f.shape[0]]) for f in frames]))
-    args = types.SimpleNamespace(min_z=inf['min_z'], cr_cube_bounds=inf['cube_bounds'], color_mode=inf['color_mode'],
-                                 sample_implicit=True, num_sample=rc.CASE['num_sample'], point_sample_mode='grid',
-                                 implicit_batch_size=rc.CASE['batch_size'], segmentation_lw=0.0, track_mode='none',
-                                 point_occupancy_radius=0.8, semantic_classes=13, density_threshold=0.5, cube_mode=4)
+    frames, batch, args = rc.clip_inputs(shared)
     meshes = []
     clip = pk.evaluation.evaluate_clip(batch, [enc, dec], device, args, 'greater', save_gt=True, surface=pk.surface.Surface(),
                                        meshes=meshes)
@@ -546,16 +539,10 @@ def check_clip(shared):
 
 def check_none_is_untouched(shared, monkeypatch):
     """surface=None: no new key, the one host wait, and no surface entry point is called."""
-    calls = dict(wait=0)
-    wait = pk.inference._HostCopies.wait
-
-    def counted_wait(self):
-        calls['wait'] += 1
-        return wait(self)
+    calls = rc.count_waits(monkeypatch)
 
     def forbidden(*a, **k):
         raise AssertionError('surface=None must not reach the surface extraction')
-    monkeypatch.setattr(pk.inference._HostCopies, 'wait', counted_wait)
     monkeypatch.setattr(pk.ops, 'surface_nets', forbidden)
     monkeypatch.setattr(pk.surface, 'extract', forbidden)
     L = pk._lib.lib()
@@ -567,8 +554,7 @@ def check_none_is_untouched(shared, monkeypatch):
                            'points_query']
     same_result(res, shared.dense)
     monkeypatch.undo()
-    calls['wait'] = 0
-    monkeypatch.setattr(pk.inference._HostCopies, 'wait', counted_wait)
+    calls = rc.count_waits(monkeypatch)
     rc.infer(shared.device, shared.inputs, surface=pk.surface.Surface())
     assert calls['wait'] == 1                                           # (the mesh adds a count read, not a wait on the copies)
 
