@@ -45,6 +45,7 @@ ADDON_HEADERS = {
     'LINK': 'ext/occ4d_link.h',                 # the components of two frames linked: overlaps, tracks (components.Tracker, perform_inference(tracker=...))
     'DISTANCE': 'ext/occ4d_distance.h',         # the distance transform of the solid set: clearance (distance.py, perform_inference(clearance=...))
     'GEODESIC': 'ext/occ4d_geodesic.h',         # shortest free-space paths over the clearance (geodesic.py, perform_inference(route=...))
+    'WATERSHED': 'ext/occ4d_watershed.h',       # touching objects split at their necks: watershed segments (watershed.py, perform_inference(segments=...))
 }
 
 

@@ -36,6 +36,7 @@
 #include "ext/occ4d_link.h"
 #include "ext/occ4d_distance.h"
 #include "ext/occ4d_geodesic.h"
+#include "ext/occ4d_watershed.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -50,6 +51,7 @@
 #include "link_math.hpp"
 #include "distance_math.hpp"
 #include "geodesic_math.hpp"
+#include "watershed_math.hpp"
 #include "decoder_math.hpp"
 
 namespace fe = occ4d_frontend;
@@ -65,6 +67,7 @@ namespace cc = occ4d_components;
 namespace lk = occ4d_link;
 namespace dm = occ4d_distance;
 namespace gm = occ4d_geodesic;
+namespace ws = occ4d_watershed;
 
 static thread_local char g_err[512] = "";
 
@@ -920,6 +923,64 @@ int occ4d_geodesic_trace_i32(const int32_t* cost, const int32_t* parent, int n, 
   OCC4D_TRY(gm::check_trace(cost, parent, n, goals, n_goals, cap, paths, path_len, empty, a));
   if (empty) return OCC4D_OK;
   for (int g = 0; g < n_goals; ++g) gm::trace_item(a, g);
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- watershed
+// include/ext/occ4d_watershed.h: the passes of csrc/watershed.hip over csrc/watershed_math.hpp with ONE TILE, THE WHOLE GRID (the
+// ascent reads its neighbours straight from height[]), points in order, the atomics spelled as plain memory operations (one
+// thread); every point is a run of one.
+int occ4d_watershed_label_i32(const int32_t* height, int nx, int ny, int nz, int connectivity, int h, int min_size, int32_t* work,
+                              int32_t* labels, int32_t* totals, void*) {
+  ws::Args a; bool empty;
+  OCC4D_TRY(ws::check_label(height, nx, ny, nz, connectivity, h, min_size, work, labels, totals, empty, a));
+  if (empty) return OCC4D_OK;
+  const int64_t n = a.grid.points;
+  for (int k = 0; k < ws::ROUND_WORDS; ++k) ws::flag_init(a, k);
+  for (int64_t p = 0; p < n; ++p) {                                                           // ascent
+    int i[3];
+    cc::coords_of(a.grid, p, i);
+    const int32_t own = ws::level_of(height[p]);
+    ws::ascent_item(a, p, own, own < 1 ? ws::SELF : ws::ascent_choice(a.rank, own, ws::GridAt{a, i}));
+  }
+  for (int k = 1; k <= a.rounds && a.flags[k - 1]; ++k)                                       // jump rounds
+    for (int64_t p = 0; p < n; ++p)
+      if (ws::jump_item<ws::Plain>(a, p)) a.flags[k] = 1;
+  for (int64_t p = 0; p < n; ++p) ws::merge_item<ws::Plain>(a, p);                            // merge
+  for (int64_t p = 0; p < n; ++p) {                                                           // flatten
+    const int r = ws::flatten_item(a, p);
+    if (r < 0) continue;
+    a.size[r] += 1;
+    a.low[r] = std::min(a.low[r], (int32_t)p);
+  }
+  int32_t sums[ws::TOTALS] = {0, 0, 0, 0};
+  for (int64_t tile = 0; tile < a.grid.number_tiles; ++tile) {                                // counts and their exclusive prefixes
+    for (int c = 0; c < ws::TOTALS; ++c) a.counts[c][tile] = sums[c];
+    for (int64_t p = tile * ws::TILE; p < std::min(n, (tile + 1) * ws::TILE); ++p)
+      for (int c = 0; c < ws::TOTALS; ++c) sums[c] += ws::flag_of(a, p, c);
+  }
+  for (int c = 0; c < ws::TOTALS; ++c) totals[c] = sums[c];
+  for (int64_t tile = 0; tile < a.grid.number_tiles; ++tile) {                                // numbers: the prefix + the rank in the tile
+    int rank = 0;
+    for (int64_t p = tile * ws::TILE; p < std::min(n, (tile + 1) * ws::TILE); ++p)
+      if (ws::is_kept_root(a, p)) ws::number_item(a, p, a.counts[0][tile] + rank++);
+  }
+  for (int64_t p = 0; p < n; ++p) ws::label_item(a, p);                                       // labels
+  return OCC4D_OK;
+}
+int occ4d_watershed_peaks_i32(const int32_t* height, const int32_t* labels, int n, const int32_t* totals, int32_t* peaks, int cap,
+                              void*) {
+  ws::PeakArgs a; bool empty;
+  OCC4D_TRY(ws::check_peaks(height, labels, n, totals, peaks, cap, empty, a));
+  if (empty) return OCC4D_OK;
+  const int rows = ws::peak_rows(a);
+  for (int k = 0; k < rows; ++k) a.keys[k] = 0;
+  for (int64_t p = 0; p < n; ++p) {
+    unsigned long long key;
+    const int k = ws::peak_contribution(a, p, rows, key);
+    if (k >= 0) a.keys[k] = std::max(a.keys[k], key);
+  }
+  for (int k = 0; k < rows; ++k) ws::peak_unpack(a, k);
   return OCC4D_OK;
 }
 

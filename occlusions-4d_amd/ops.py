@@ -1666,6 +1666,46 @@ def grid_components(values, counts, level, connectivity=6, min_size=1, mask=None
     return labels, totals, table[:cap]
 
 
+def watershed_work_len(n):
+    """Elements of the int32 work array of occ4d_watershed_label_i32 for n grid points (the formula of the header)."""
+    k = _lib.WATERSHED_CONSTANTS
+    return 4 * n + 4 * ((n + k['TILE'] - 1) // k['TILE']) + k['ROUND_WORDS']
+
+
+def grid_watershed(height, counts, h, connectivity=26, min_size=1, cap=None):
+    """The watershed segments of an integer height map on the (nx, ny, nz) = `counts` grid (occ4d_watershed_label_i32 /
+    occ4d_components_table_i64 / occ4d_watershed_peaks_i32, the rules in include/ext/occ4d_watershed.h).  height (n,) int32, x
+    slowest, z fastest: the members are height >= 1 (ops.grid_distance's inside2 with target=1: the squared depth of every solid
+    point).  Every member climbs to its highest neighbour -- ties to the lower flat index -- until a maximum; two basins merge when
+    the highest saddle between them lies within `h` (an integer in [0, 2^31 - 1]) of the lower peak.  Segments of fewer than
+    min_size points are dropped, the others numbered in the order of their lowest flat index.
+    -> (labels (n,) int32, -1 = none; totals (4,) int32: kept segments, kept points, all segments, basins; table (K, 12) int64, the
+    components table of the segments; peaks (K, 2) int32: per kept segment the flat index and the height of its highest point), on
+    the device.  cap=None: one 16-byte device->host read of totals sizes table and peaks, K = totals[0].  cap = an int: no read, K =
+    cap, and only the rows below min(cap, totals[0]) are written."""
+    nx, ny, nz = (int(c) for c in counts)
+    n = max(nx * ny * nz, 0)
+    hgt, _ = _inst_column(height, n, 'height', torch.int32)
+    hgt = hgt if hgt.is_contiguous() else hgt.contiguous()
+    words = _lib.WATERSHED_CONSTANTS['TOTALS']
+    # (an empty grid is a no-op of the library: its totals are the zeros put here)
+    scratch = (torch.empty if n else torch.zeros)(watershed_work_len(n) + words, dtype=torch.int32, device=hgt.device)
+    work, totals = scratch[:-words], scratch[-words:]
+    labels = torch.empty((n,), dtype=torch.int32, device=hgt.device)
+    st = _stream()
+    _lib.check(_lib.lib().occ4d_watershed_label_i32(_ptr(hgt), nx, ny, nz, int(connectivity), int(h), int(min_size), _ptr(work),
+                                                    _ptr(labels), _ptr(totals), st))
+    if cap is None:
+        cap = int(totals.tolist()[0]) if n else 0
+    cap = int(cap)
+    assert cap >= 0, 'cap = %d must be >= 0' % cap
+    table = torch.empty((cap, _lib.COMPONENTS_CONSTANTS['COLS']), dtype=torch.int64, device=hgt.device)
+    peaks = torch.empty((cap, 2), dtype=torch.int32, device=hgt.device)
+    _lib.check(_lib.lib().occ4d_components_table_i64(_ptr(labels), None, nx, ny, nz, _ptr(totals), _ptr(table), cap, st))
+    _lib.check(_lib.lib().occ4d_watershed_peaks_i32(_ptr(hgt), _ptr(labels), n, _ptr(totals), _ptr(peaks), cap, st))
+    return labels, totals, table, peaks
+
+
 def distance_tile_width(length, stage=1):
     """Lines of a workgroup's tile in the launcher of occ4d_distance_grid_f32 for lines of `length` points (the formulas of the
     header's constants): stage 0 (z) max(1, RUN_POINTS // length) consecutive lines; stages 1, 2 (y, x) TILE_WIDTH halved until
