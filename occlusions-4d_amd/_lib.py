@@ -46,6 +46,7 @@ ADDON_HEADERS = {
     'DISTANCE': 'ext/occ4d_distance.h',         # the distance transform of the solid set: clearance (distance.py, perform_inference(clearance=...))
     'GEODESIC': 'ext/occ4d_geodesic.h',         # shortest free-space paths over the clearance (geodesic.py, perform_inference(route=...))
     'WATERSHED': 'ext/occ4d_watershed.h',       # touching objects split at their necks: watershed segments (watershed.py, perform_inference(segments=...))
+    'SIGHT': 'ext/occ4d_sight.h',               # line of sight through the solid set: seen, hidden, by what (sight.py, perform_inference(sight=...))
 }
 
 
@@ -71,7 +72,7 @@ def parse_constants(text):
 
 _SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'int64_t': C.c_int64, 'unsigned': C.c_uint, 'float': C.c_float,
             'double': C.c_double}
-_POINTEES = set(_SCALARS) | {'void', 'unsigned long long'}
+_POINTEES = set(_SCALARS) | {'void', 'unsigned long long', 'uint32_t'}
 _NOT_A_NAME = {'const', 'unsigned', 'signed', 'long', 'short', 'char', 'int', 'float', 'double', 'void', 'struct'}
 
 

@@ -37,6 +37,7 @@
 #include "ext/occ4d_distance.h"
 #include "ext/occ4d_geodesic.h"
 #include "ext/occ4d_watershed.h"
+#include "ext/occ4d_sight.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -52,6 +53,7 @@
 #include "distance_math.hpp"
 #include "geodesic_math.hpp"
 #include "watershed_math.hpp"
+#include "sight_math.hpp"
 #include "decoder_math.hpp"
 
 namespace fe = occ4d_frontend;
@@ -68,6 +70,7 @@ namespace lk = occ4d_link;
 namespace dm = occ4d_distance;
 namespace gm = occ4d_geodesic;
 namespace ws = occ4d_watershed;
+namespace sm = occ4d_sight;
 
 static thread_local char g_err[512] = "";
 
@@ -981,6 +984,32 @@ int occ4d_watershed_peaks_i32(const int32_t* height, const int32_t* labels, int 
     if (k >= 0) a.keys[k] = std::max(a.keys[k], key);
   }
   for (int k = 0; k < rows; ++k) ws::peak_unpack(a, k);
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- sight
+// include/ext/occ4d_sight.h: the member test, the walk and the body of a query of csrc/sight_math.hpp, ALL QUERIES IN FLAT ORDER,
+// another order than the kernel's blocks.
+int occ4d_sight_bits_f32(const float* field, int64_t ld, float level, const float* mask, int64_t ld_mask, float mask_level, int64_t n,
+                         uint32_t* bits, void*) {
+  sm::BitsArgs a; bool empty;
+  OCC4D_TRY(sm::check_bits(field, ld, level, mask, ld_mask, mask_level, n, bits, empty, a));
+  if (empty) return OCC4D_OK;
+  for (int64_t w = 0; w < a.words; ++w) {
+    uint32_t word = 0;
+    for (int64_t p = w * 32; p < n && p < w * 32 + 32; ++p) word |= (uint32_t)sm::member(a, p) << (p & 31);
+    bits[w] = word;
+  }
+  return OCC4D_OK;
+}
+int occ4d_sight_grid_u32(const uint32_t* bits, int nx, int ny, int nz, const int32_t* origins_host, int V, const int32_t* framed,
+                         int32_t* seen, int32_t* blocker, int flags, void*) {
+  sm::Args a; bool empty;
+  OCC4D_TRY(sm::check_grid(bits, nx, ny, nz, origins_host, V, framed, seen, blocker, flags, empty, a));
+  if (empty) return OCC4D_OK;
+  for (int x = 0; x < nx; ++x)
+    for (int y = 0; y < ny; ++y)
+      for (int z = 0; z < nz; ++z) sm::query_item(a, sm::GlobalWords{bits}, x, y, z);
   return OCC4D_OK;
 }
 

@@ -1706,6 +1706,43 @@ def grid_watershed(height, counts, h, connectivity=26, min_size=1, cap=None):
     return labels, totals, table, peaks
 
 
+def grid_solid_bits(values, level, mask=None, mask_level=0.0):
+    """The solid set values >= level (with mask (n,) also mask >= mask_level) packed one bit per grid point (occ4d_sight_bits_f32,
+    the rules in include/ext/occ4d_sight.h): values (n,), a strided column view is read in place -> (ceil(n / 32),) int32 on the
+    device, bit p % 32 of word p // 32 is point p, the unused bits of the last word are 0.  No host read."""
+    n = int(values.shape[0])
+    v, ld = _inst_column(values, n, 'values')
+    m, ld_mask = (None, 0) if mask is None else _inst_column(mask, n, 'mask')
+    bits = torch.empty(((n + 31) // 32,), dtype=torch.int32, device=v.device)
+    _lib.check(_lib.lib().occ4d_sight_bits_f32(_ptr(v), ld, float(level), _ptr(m), ld_mask, float(mask_level), n, _ptr(bits), _stream()))
+    return bits
+
+
+def grid_sight(bits, counts, origins, framed=None, blocker=False, flags=0):
+    """Line of sight on the (nx, ny, nz) = `counts` grid (occ4d_sight_grid_u32, the rules in include/ext/occ4d_sight.h): bits
+    (ceil(n / 32),) int32 from ops.grid_solid_bits; origins (V, 3) integer lattice points ON THE HOST (numpy or a list), 1 <= V <=
+    31, inside the grid or not; framed (n,) int32 or None: bit v = origin v may look at the query; blocker: also the blocking cells;
+    flags: 0 (the header has no flag bit).  -> (seen (n,) int32, bit v = seen from origin v; blocker (V, n) int32, -1
+    where seen or not framed, or None), on the device.  No host read."""
+    nx, ny, nz = (int(c) for c in counts)
+    n = nx * ny * nz
+    words = _dev(bits, torch.int32, 'bits')
+    assert words.dim() == 1 and words.shape[0] == (max(n, 0) + 31) // 32 and words.is_contiguous(), \
+        'bits must be a contiguous (%d,) tensor, got %s' % ((max(n, 0) + 31) // 32, tuple(words.shape))
+    org = np.ascontiguousarray(origins, dtype=np.int64)
+    assert org.ndim == 2 and org.shape[1] == 3, 'origins must be (V, 3), got %s' % (org.shape,)
+    assert org.size == 0 or (org.min() >= -2 ** 31 and org.max() <= 2 ** 31 - 1), 'origins must fit int32'
+    org = org.astype(np.int32)
+    V = org.shape[0]
+    fr = None if framed is None else _dev(framed, torch.int32, 'framed')
+    assert fr is None or (tuple(fr.shape) == (max(n, 0),) and fr.is_contiguous()), 'framed must be a contiguous (%d,) tensor' % n
+    seen = torch.empty((max(n, 0),), dtype=torch.int32, device=words.device)
+    block = torch.empty((max(V, 0), max(n, 0)), dtype=torch.int32, device=words.device) if blocker else None
+    _lib.check(_lib.lib().occ4d_sight_grid_u32(_ptr(words), nx, ny, nz, org.ctypes.data_as(C.c_void_p), V, _ptr(fr), _ptr(seen),
+                                               _ptr(block), int(flags), _stream()))
+    return seen, block
+
+
 def distance_tile_width(length, stage=1):
     """Lines of a workgroup's tile in the launcher of occ4d_distance_grid_f32 for lines of `length` points (the formulas of the
     header's constants): stage 0 (z) max(1, RUN_POINTS // length) consecutive lines; stages 1, 2 (y, x) TILE_WIDTH halved until

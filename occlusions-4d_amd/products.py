@@ -1,4 +1,5 @@
-"""The grid products of perform_inference: what its options surface, views, components, tracker, clearance and route have in common.
+"""The grid products of perform_inference: what its options surface, views, components, tracker, clearance, segments, sight and route
+have in common.
 Each of them turns the squashed (N, G) output of a point_sample_mode='grid' call into more device tensors, which come home under the
 call's one host wait.  An option class derives from GridProduct and says which keyword it answers to, what it needs and how it
 runs; perform_inference and evaluate_clip walk the options they are given and know nothing else about them."""
@@ -7,8 +8,9 @@ runs; perform_inference and evaluate_clip walk the options they are given and kn
 class Grid:
     """The query grid of one perform_inference call: counts (nx, ny, nz), mins, spacings = `frame` (geometry.grid_frame, evaluated
     once per call), the call's density_threshold, predict_segmentation, semantic_classes and device; after the decode also `output`,
-    the squashed -- in track_mode 'all' merged, under `refine` expanded -- (N, G) device tensor."""
-    output = None
+    the squashed -- in track_mode 'all' merged, under `refine` expanded -- (N, G) device tensor, and `points`, the (N, 3) device view
+    of the call's own query points."""
+    output = points = None
 
     def __init__(self, frame, density_threshold, predict_segmentation, semantic_classes, device):
         self.counts, self.mins, self.spacings = tuple(frame[0]), frame[1], frame[2]
