@@ -308,7 +308,8 @@ int occ4d_pt_pair_mlp_f32(const float* aq, int64_t ld_aq, const float* kt, int64
  * occ4d_resblock_f32:  y = x + W1 relu(W0 relu(x) + b0) + b1   -- ResnetBlockFC.forward, model/implicit.py:92-101
  *   (fc_0, fc_1, identity shortcut), optionally followed by  y += zconst + sum_j zw[:, j] ztab[zidx[:, j], :]
  *   -- the `x = x + lin_z[i+1](features_query)` of the NEXT block (model/implicit.py:416-417) in the exact-in-R
- *   form of occ4d_interp_add_f32.  y may alias x.
+ *   form of occ4d_interp_add_f32.  y may alias x.  (With a term, both entry points run occ4d_interp_add_f32 behind the
+ *   matrix launch; the forms that hide the term inside the launch are in ext/occ4d_linz.h.)
  * occ4d_rowlin_f32:  y[:, 0..n_out) = [res +] W [relu](x) + b [+ the same interpolation term], K = 416,
  *   n_out % 32 == 0 -- the Linear layers around the cross-attention (model/modules.py:61-65: layer1 merged into
  *   the query projection, layer3 + residual).  res may alias y.
@@ -565,7 +566,9 @@ int occ4d_broadcast_rows_f32(const float* vec, float scale, int n, int d, float*
 #define OCC4D_PATH_TRUNK4 16        /* half-CU trunk kernels (csrc/trunk4.hip) */
 #define OCC4D_PATH_BF16X6 64        /* opt-in, fp32-class: d = 416 attention GEMMs on 3-way split bf16 MFMAs, 6 partial products */
 #define OCC4D_PATH_BF16X6_TRUNK 128 /* opt-in, fp32-class: the decoder's 416-input Linear layers on the same split (csrc/trunk_bf16x6.hip) */
-#define OCC4D_PATH_FUSED_INTERP 32 /* A/B only (slower): lin_z table term of block i + 1 in block i's epilogue */
+#define OCC4D_PATH_FUSED_INTERP 32 /* accepted, selects nothing the default does not do: it put the lin_z table term of block i + 1 into
+                                    * block i's epilogue (exposed gathers, neutral: DESIGN.md 6e); the default now hides the terms
+                                    * inside the trunk kernels (ext/occ4d_linz.h, where the opt-out bit lives) */
 #define OCC4D_PATH_SPLIT_F16 256    /* with OCC4D_PATH_BF16X6 / _TRUNK: the split is fp16 x 2 pieces, 3 partial products (round 6;
                                      * half the matrix instructions; inference forwards only; |w| < 255.9, |activation| < 65504; the prepare calls fail with
  * OCC4D_EINVAL for a weight outside the window) */

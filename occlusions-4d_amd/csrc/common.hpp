@@ -54,6 +54,50 @@ int check_rowlin_args(const Args& a, const char* who, int width, int stage, int 
   return OCC4D_OK;
 }
 
+// n rows of d floats with row stride ld from p / from q: do the two spans share a byte?
+inline bool rows_overlap(const float* p, int64_t ldp, const float* q, int64_t ldq, int n, int d) {
+  if (!p || !q || n <= 0) return false;
+  const uintptr_t p0 = (uintptr_t)p, p1 = (uintptr_t)(p + (int64_t)(n - 1) * ldp + d);
+  const uintptr_t q0 = (uintptr_t)q, q1 = (uintptr_t)(q + (int64_t)(n - 1) * ldq + d);
+  return p0 < q1 && q0 < p1;
+}
+
+// ... what occ4d_rowlin_linz_f32 (include/ext/occ4d_linz.h) adds to the rowlin contract: at least one of the two terms, exactly
+// `zk` neighbours (the kernel holds a row's list in registers), and for the second term its table, its constant and the
+// dense rows it is stored to, which no stage may read back (x, the residual) or write as well (y).
+template <class Args>
+int check_linz_args(const Args& a, const char* who, int zk, int n_out) {
+  OCC4D_REQUIRE(a.ztab || a.ztab2, "%s: no interpolation term (ztab and ztab2 are both null; occ4d_rowlin_f32 is the plain launch)", who);
+  OCC4D_REQUIRE(a.zidx && a.zw && a.kz == zk, "%s: the terms take zidx / zw with kz = %d neighbours (kz = %d: run "
+                "occ4d_interp_add_f32 behind occ4d_rowlin_f32)", who, zk, a.kz);
+  OCC4D_REQUIRE(a.ldz >= n_out && a.ldz % 4 == 0, "%s: ldz = %lld must be a multiple of 4 >= n_out", who, (long long)a.ldz);
+  OCC4D_REQUIRE(a.zrows >= 1 && (int64_t)a.zrows * a.ldz < ((int64_t)1 << 30), "%s: zrows = %d table rows of stride %lld: zrows "
+                "ldz must stay below 2^30 (32-bit row offsets)", who, a.zrows, (long long)a.ldz);
+  if (a.ztab2) {
+    OCC4D_REQUIRE(a.zconst2 && ((uintptr_t)a.ztab2 % 16) == 0 && ((uintptr_t)a.zconst2 % 16) == 0,
+                  "%s: the second term needs zconst2 and a 16-byte aligned table", who);
+    OCC4D_REQUIRE(a.dense && ((uintptr_t)a.dense % 16) == 0 && a.ldd % 4 == 0 && a.ldd >= n_out,
+                  "%s: dense rows must be 16-byte aligned with ldd %% 4 == 0 and ldd >= n_out", who);
+    OCC4D_REQUIRE(!rows_overlap(a.dense, a.ldd, a.y, a.ldy, a.n, n_out) && !rows_overlap(a.dense, a.ldd, a.x, a.ldx, a.n, n_out) &&
+                      !rows_overlap(a.dense, a.ldd, a.res, a.ldr, a.n, n_out),
+                  "%s: dense rows must not alias x, y or the residual rows", who);
+  } else {
+    OCC4D_REQUIRE(!a.dense && !a.zconst2, "%s: dense / zconst2 given without ztab2", who);
+  }
+  return OCC4D_OK;
+}
+
+// ... and occ4d_resblock_addrows_f32: the dense rows are read while other workgroups already store their y rows
+template <class Args>
+int check_addrows_args(const Args& a, const char* who, int width) {
+  OCC4D_REQUIRE(a.addrows && ((uintptr_t)a.addrows % 16) == 0 && a.lda % 4 == 0 && a.lda >= width,
+                "%s: addrows must be 16-byte aligned with ld_add %% 4 == 0 and ld_add >= %d", who, width);
+  OCC4D_REQUIRE((int64_t)a.n * a.lda < ((int64_t)1 << 30), "%s: n ld_add = %lld must stay below 2^30 (32-bit row offsets: chunk "
+                "the rows)", who, (long long)((int64_t)a.n * a.lda));
+  OCC4D_REQUIRE(!rows_overlap(a.addrows, a.lda, a.y, a.ldy, a.n, width), "%s: addrows must not alias y", who);
+  return OCC4D_OK;
+}
+
 // fps_bucket.hip: the pruned single-workgroup FPS (FPS_BUCKET_MIN_POINTS <= n <= 16384); -1 = n outside that range.
 // Since a round of the pruned kernel accepts several samples (round 3) it also wins on the small encoder levels, whose
 // step is bound by the serial argmax chain (profiles/time_fps.py, pruned vs exhaustive: 9558 points 1.84 vs 3.54 ms,

@@ -12,6 +12,7 @@
 
 #include "common.hpp"
 #include "decoder_math.hpp"
+#include "ext/occ4d_linz.h"
 
 namespace {
 
@@ -441,12 +442,27 @@ int rowlin_x6(bool f16, const float* x, int64_t ldx, float* y, int64_t ldy, cons
   return rc;
 }
 
+// lin_z terms a decoder hands to a cross layer's post Linear (layer3 + residual, a rowlin launch): the term of the block
+// that directly follows the layer is added to the output rows, and -- with ztab2 -- the term of the block after that one is
+// stored as dense rows, which the block between adds (occ4d_rowlin_linz_f32, include/ext/occ4d_linz.h).
+struct LinzTerms {
+  const float *zconst, *ztab, *zconst2, *ztab2;
+  int64_t ldz;
+  int zrows;
+  const int32_t* zidx;
+  const float* zw;
+  int kz;
+  float* dense;
+  int64_t ldd;
+};
+
 // The forward of one layer / block.  dry: only the workspace is counted (no pointer is dereferenced, nothing launched).
+// lz (the caller has checked that the post Linear is the fp32 row kernel): the terms that launch takes along.
 int layer_forward(const occ4d_pt_layer_weights& w, const LayerLayout& L, const float* prep, const float* x, int64_t ldx,
                   const float* pos, int64_t ps, int n, const float* x2, int64_t ldx2, const float* pos2, int64_t p2s, int m,
                   int k, const int32_t* knn_idx, const float* scene, float* out, int64_t ldo, Bump& ws,
                   const Events& E, hipStream_t st, bool dry, float* logits_out = nullptr, float* a_out = nullptr,
-                  float* pe_out = nullptr) {
+                  float* pe_out = nullptr, const LinzTerms* lz = nullptr) {
   const int D = L.D, h = L.h;
   const int64_t mark = ws.mark();
   const float *kt, *vt, *vtc, *aq_all = nullptr, *yfeat = x;
@@ -584,7 +600,14 @@ int layer_forward(const occ4d_pt_layer_weights& w, const LayerLayout& L, const f
   if (w.post_w && !dry) {
     if (L.x6rows)
       TRY(rowlin_x6(L.f16, agg, D, out, ldo, prep + L.w3_x6, w.post_b, w.d_out, 0, x, ldx, n, E, st));
-    else if (L.w3_rows)
+    else if (L.w3_rows && lz) {
+      E.before(OCC4D_PROFILE_ROWLIN);
+      const int rc = occ4d_rowlin_linz_f32(agg, D, out, ldo, prep + L.w3_packed, w.post_b, w.d_out, 0, x, ldx, lz->zconst,
+                                           lz->ztab, lz->zconst2, lz->ztab2, lz->ldz, lz->zrows, lz->zidx, lz->zw, lz->kz,
+                                           lz->dense, lz->ldd, n, st);
+      E.after(OCC4D_PROFILE_ROWLIN);
+      TRY(rc);
+    } else if (L.w3_rows)
       TRY(rowlin_any(L.trunk4, agg, D, out, ldo, prep + L.w3_packed, w.post_b, w.d_out, 0, x, ldx, n, E, st));
     else
       TRY(lin(agg, D, w.post_w, D, w.post_b, out, ldo, n, D, w.d_out, 0, 0, x, ldx, st));
@@ -772,21 +795,35 @@ int decoder_forward(const occ4d_decoder_weights& w, const DecoderLayout& L, cons
       if (pe) TRY(query_embed(w, q, qs, c, pe, x, ldx, st));
       else if (!x_given) TRY(occ4d::copy_rows(x, ldx, pre->x0 + (int64_t)lo * pre->ld_x0, pre->ld_x0, c, H, st));
     }
+    // Where the lin_z term of block i (x += lin_z[i](features_query), the exact-in-R form of DESIGN.md 4 (ii)) is added
+    // (DESIGN.md 6e).  On the fp32 row-resident trunk, for a cross layer j behind block b - 1 whose post Linear is the
+    // fp32 row kernel: the term of block b rides in that launch (added to its output rows), and where no cross layer
+    // sits behind block b, the same launch stores the term of block b + 1 as dense rows, which block b's launch adds
+    // from loads under its last chunk.  Every other term (blocks 0 and 1 of the published layouts; k_local != 8; the
+    // penult output; trunk4; the split-precision trunks; OCC4D_LINZ_PATH_STANDALONE) is the stand-alone pass in front of
+    // its block.  All three placements add the same s last onto the same row: one result, bit for bit.
+    // OCC4D_PATH_FUSED_INTERP (the exposed gathers in the block's epilogue, measured neutral) is accepted and selects
+    // nothing: what it moved is where the default puts it now, hidden.
+    const bool linz = !(flags & OCC4D_LINZ_PATH_STANDALONE) && L.resblock && !L.trunk4 && !L.x6trunk && !penult &&
+                      w.k_local == 8 && (int64_t)m * L.nB * H < ((int64_t)1 << 30) && (int64_t)c * H < ((int64_t)1 << 30);
+    bool in_rowlin[OCC4D_MAX_BLOCKS + 2] = {}, as_dense[OCC4D_MAX_BLOCKS + 2] = {};
+    bool any_dense = false;
+    for (int j = 0; linz && j < L.nC; ++j) {
+      const int b = w.cross_after[j] + 1;
+      const LayerLayout& lc = L.cl[j];
+      if (b >= L.nB || !w.cross[j].post_w || !lc.w3_rows || lc.x6rows || lc.trunk4) continue;
+      in_rowlin[b] = true;
+      const bool cross_behind_b = j + 1 < L.nC && w.cross_after[j + 1] == b;
+      if (b + 1 < L.nB && !cross_behind_b) as_dense[b + 1] = any_dense = true;
+    }
+    float* dense = any_dense ? ws.take((int64_t)c * H) : nullptr;
+    const int64_t ldz = (int64_t)L.nB * H;
     int next_cross = 0;
     for (int i = 0; i < L.nB; ++i) {
       if (!dry) {
-        // x += lin_z[i](features_query) in the exact-in-R form.  OCC4D_PATH_FUSED_INTERP (A/B only,
-        // measured slower: DESIGN.md 6e): the term of block i + 1 is added in block i's epilogue instead, wherever no
-        // cross-attention layer sits between the two blocks.  Only the fp32 fused block has that epilogue: where the
-        // split-precision trunk takes the block (L.x6trunk, L.f16block included) every term is added here.
-        const bool fuse_ok = (flags & OCC4D_PATH_FUSED_INTERP) && L.resblock && !L.trunk4 && !L.x6trunk;
-        const bool cross_behind = next_cross < L.nC && w.cross_after[next_cross] == i;
-        const bool cross_before = i > 0 && next_cross > 0 && w.cross_after[next_cross - 1] == i - 1;
-        const bool had_it = fuse_ok && i > 0 && !cross_before;           // block i - 1's epilogue added this block's term
-        const bool give_next = fuse_ok && i + 1 < L.nB && !cross_behind;
-        if (!had_it)
-          TRY(occ4d_interp_add_f32(x, ldx, scene + S.zconst + (int64_t)i * H, scene + S.ztab + (int64_t)i * H,
-                                   (int64_t)L.nB * H, idx8, w8, c, w.k_local, H, st));
+        if (!in_rowlin[i] && !as_dense[i])
+          TRY(occ4d_interp_add_f32(x, ldx, scene + S.zconst + (int64_t)i * H, scene + S.ztab + (int64_t)i * H, ldz, idx8, w8, c,
+                                   w.k_local, H, st));
         if (L.f16block) {
           // x = x + fc_1(relu(fc_0(relu(x)))) in place, one launch, h in registers
           E.before(OCC4D_PROFILE_RESBLOCK);
@@ -802,14 +839,14 @@ int decoder_forward(const occ4d_decoder_weights& w, const DecoderLayout& L, cons
           TRY(rc);
         } else if (L.resblock) {
           E.before(OCC4D_PROFILE_RESBLOCK);
-          const float* zc = give_next ? scene + S.zconst + (int64_t)(i + 1) * H : nullptr;
-          const float* zt = give_next ? scene + S.ztab + (int64_t)(i + 1) * H : nullptr;
           const int rc = L.trunk4
               ? occ4d_resblock4_f32(x, ldx, x, ldx, prep + L.w0p[i], w.fc0_b[i], prep + L.w1p[i], w.fc1_b[i], nullptr,
                                     nullptr, 0, nullptr, nullptr, 0, c, st)
-              : occ4d_resblock_f32(x, ldx, x, ldx, prep + L.w0p[i], w.fc0_b[i], prep + L.w1p[i], w.fc1_b[i], zc, zt,
-                                   (int64_t)L.nB * H, give_next ? idx8 : nullptr, give_next ? w8 : nullptr,
-                                   give_next ? w.k_local : 0, c, st);
+              : as_dense[i + 1]     // (the next block's term, left as dense rows by the cross layer in front of this block)
+              ? occ4d_resblock_addrows_f32(x, ldx, x, ldx, prep + L.w0p[i], w.fc0_b[i], prep + L.w1p[i], w.fc1_b[i], dense, H,
+                                           c, st)
+              : occ4d_resblock_f32(x, ldx, x, ldx, prep + L.w0p[i], w.fc0_b[i], prep + L.w1p[i], w.fc1_b[i], nullptr,
+                                   nullptr, 0, nullptr, nullptr, 0, c, st);
           E.after(OCC4D_PROFILE_RESBLOCK);
           TRY(rc);
         } else {
@@ -819,15 +856,24 @@ int decoder_forward(const occ4d_decoder_weights& w, const DecoderLayout& L, cons
       }
       if (next_cross < L.nC && w.cross_after[next_cross] == i) {
         const int j = next_cross++;
+        LinzTerms lz{};
+        if (!dry && in_rowlin[i + 1]) {
+          lz.zconst = scene + S.zconst + (int64_t)(i + 1) * H; lz.ztab = scene + S.ztab + (int64_t)(i + 1) * H;
+          if (as_dense[i + 2]) {
+            lz.zconst2 = scene + S.zconst + (int64_t)(i + 2) * H; lz.ztab2 = scene + S.ztab + (int64_t)(i + 2) * H;
+            lz.dense = dense; lz.ldd = H;
+          }
+          lz.ldz = ldz; lz.zrows = m; lz.zidx = idx8; lz.zw = w8; lz.kz = w.k_local;
+        }
         TRY(layer_forward(w.cross[j], L.cl[j], prep ? prep + L.cross[j] : nullptr, x, ldx, q, qs, c, nullptr, 0, xyz, 3, m,
-                          w.k_cross, idx_att, scene ? scene + S.layer[j] : nullptr, x, ldx, ws, E, st, dry));
+                          w.k_cross, idx_att, scene ? scene + S.layer[j] : nullptr, x, ldx, ws, E, st, dry, nullptr, nullptr,
+                          nullptr, !dry && in_rowlin[i + 1] ? &lz : nullptr));
       }
     }
     if (!dry)
       TRY(lin(x, ldx, w.lin_out_w, H, w.lin_out_b, out + (int64_t)lo * ld_out, ld_out, c, H, w.d_out, act, 0, nullptr, 0, st));
     ws.release(mark);
   }
-  (void)flags;
   return OCC4D_OK;
 }
 

@@ -22,6 +22,9 @@
 // (64 lanes x 16 B, lane-linear: conflict-free ds_read_b128, contiguous global_load_lds_dwordx4), two
 // stage buffers of 52 KB: while a stage's MFMAs read one buffer the DMA fills the other; one
 // s_waitcnt vmcnt(0) + barrier per stage ("my part of the next stage has landed" + "everybody's has").
+#include <type_traits>
+
+#include "ext/occ4d_linz.h"
 #include "tile.hpp"
 
 namespace {
@@ -47,6 +50,10 @@ struct TrunkArgs {
   int n_stages;                              // rowlin: output channels / 32
   int relu_in;                               // rowlin: relu on the operand
   const float* mask; int64_t ldm;            // rowlin: output rows zeroed where mask <= 0 (ReLU mask of a data gradient), or null
+  // rowlin, second interpolation term (same zidx / zw / ldz / kz), STORED as dense rows instead of added:
+  // dense[i, :] = zconst2[:] + sum_j zw[i, j] * ztab2[zidx[i, j], :]
+  const float* zconst2; const float* ztab2; float* dense; int64_t ldd; int zrows;
+  const float* addrows; int64_t lda;         // resblock: dense rows added to the output rows last (y = block(x) + addrows), or null
 };
 
 // One stage = 52 fragments of 1 KB, global (L2) -> LDS by DMA (dma_frag, csrc/tile.hpp); wave w moves fragments w,
@@ -65,27 +72,14 @@ __device__ __forceinline__ void dma_part(const float* __restrict__ src, const fl
   if (c < STAGE_FRAGS) dma_frag(src + c * FRAG_FLOATS, lds_addr(dst) + (unsigned)c * (FRAG_FLOATS * 4), (unsigned)lane * 16u);
 }
 
-// out[t] += zconst + sum_j zw[row, j] * ztab[zidx[row, j], 16 t + 4 g ..]   (one neighbour at a time: 26 gathers in flight)
-__device__ __forceinline__ void interp_into(const TrunkArgs& a, int rowc, int g, f32x4* out) {
-#pragma unroll
-  for (int t = 0; t < TKG; ++t) {
-    const f32x4 c = *reinterpret_cast<const f32x4*>(a.zconst + 16 * t + 4 * g);
-    out[t].x += c.x; out[t].y += c.y; out[t].z += c.z; out[t].w += c.w;
-  }
-  for (int j = 0; j < a.kz; ++j) {
-    const float w = a.zw[(int64_t)rowc * a.kz + j];
-    const float* zr = a.ztab + (int64_t)a.zidx[(int64_t)rowc * a.kz + j] * a.ldz + 4 * g;
-#pragma unroll
-    for (int t = 0; t < TKG; ++t) {
-      const f32x4 z = *reinterpret_cast<const f32x4*>(zr + 16 * t);
-      out[t].x = fmaf(w, z.x, out[t].x); out[t].y = fmaf(w, z.y, out[t].y);
-      out[t].z = fmaf(w, z.z, out[t].z); out[t].w = fmaf(w, z.w, out[t].w);
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------
-// y = x + W1 relu(W0 relu(x) + b0) + b1  [+ interpolation term of the next block]
+// y = x + W1 relu(W0 relu(x) + b0) + b1  [+ addrows]
+// ADD: dense rows (the NEXT block's lin_z term, produced by an earlier rowlin launch) are added to the output rows as the
+// last operation.  Their loads sit under the MFMAs of the LAST hidden chunk, in the registers of relu(x), which die tile
+// by tile during that chunk's stage A: tiles 0 .. 10 after every second group of stage A (tile k after group 2 k + 1),
+// tiles 11 .. 25 with the first 15 groups of stage B -- every load has at least four groups of MFMAs before the
+// vmcnt(0) of the barrier that follows it.  The last chunk is peeled; chunks 0 .. 11 are the code of the plain kernel.
+template <bool ADD>
 __global__ __launch_bounds__(512, 2) void resblock_kernel(const TrunkArgs a) {
   // two separate LDS objects: the DMA into one is provably disjoint from the fragment reads of the other (one
   // array split by an offset made the compiler wait for vmcnt(0) -- the DMA just issued -- before the first ds_read)
@@ -130,8 +124,14 @@ __global__ __launch_bounds__(512, 2) void resblock_kernel(const TrunkArgs a) {
 #endif
   asm volatile("; OCC4D_MARK loop");
   // the packed W0 stream carries TNS + 1 stages (the last repeats stage 0), so "prefetch stage j + 1" is branch-free
-#pragma clang loop unroll(disable)
-  for (int j = 0; j < TNS; ++j) {
+  auto chunk = [&](const int j, auto last_chunk) __attribute__((always_inline)) {
+    constexpr bool LAST = ADD && decltype(last_chunk)::value;
+    // this lane's float4 of tile 0: scalar base + one 32-bit offset register (n ld_add < 2^30, checked by the launcher)
+    // (formed HERE from the row number, which the epilogue keeps anyway: the empty asm keeps the offset out of the prologue
+    // and the loop, where every register is taken)
+    int arow = row;
+    if (LAST) asm volatile("" : "+v"(arow));
+    const float* const ap = LAST ? a.addrows + (unsigned)(min(arow, a.n - 1) * (int)a.lda + 4 * g) : nullptr;
     // ---- stage A: h = relu(W0[32 j .. 32 j + 32, :] relu(x) + b0); meanwhile W1's chunk j lands in bufB
     f32x4 h0 = *reinterpret_cast<const f32x4*>(s_b0 + 32 * j + 4 * g);
     f32x4 h1 = *reinterpret_cast<const f32x4*>(s_b0 + 32 * j + 16 + 4 * g);
@@ -157,6 +157,8 @@ __global__ __launch_bounds__(512, 2) void resblock_kernel(const TrunkArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         mfma16x2_b(ca, cb, xr[t], h0, h1);
         __builtin_amdgcn_sched_barrier(0);
+        // (tile (t - 1) / 2 <= t of relu(x) has had its last use)
+        if (LAST && (t & 1) && t <= 21) xr[(t - 1) / 2] = *reinterpret_cast<const f32x4*>(ap + 16 * ((t - 1) / 2));
       }
     }
     h0 = relu4(h0);
@@ -178,6 +180,7 @@ __global__ __launch_bounds__(512, 2) void resblock_kernel(const TrunkArgs a) {
 #ifndef OCC4D_TR_NODMA
         if (q >= 2 && q <= 20 && (q - 2) % 3 == 0) dma_part(a.w0p + (int64_t)(j + 1) * STAGE_FLOATS, bufA, wave, lane, (q - 2) / 3);
 #endif
+        if (LAST && q < TKG - 11) xr[11 + q] = *reinterpret_cast<const f32x4*>(ap + 16 * (11 + q));
         const f32x4 ca = wa, cb = wb;
         if (q + 1 < TKG) {
           const int pn = (q + 1) >> 1, tn = (q + 1) & 1;
@@ -195,7 +198,10 @@ __global__ __launch_bounds__(512, 2) void resblock_kernel(const TrunkArgs a) {
     __syncthreads();
 #endif
     STAMP(3)
-  }
+  };
+#pragma clang loop unroll(disable)
+  for (int j = 0; j < (ADD ? TNS - 1 : TNS); ++j) chunk(j, std::false_type{});
+  if (ADD) chunk(TNS - 1, std::true_type{});
   asm volatile("; OCC4D_MARK epilogue");
 #ifdef OCC4D_TR_STAMP
   if (lane == 0 && a.zw) {     // debug build: a.zw doubles as the stamp buffer (5 x u64 per wave)
@@ -203,7 +209,10 @@ __global__ __launch_bounds__(512, 2) void resblock_kernel(const TrunkArgs a) {
     o[0] = tacc[0]; o[1] = tacc[1]; o[2] = tacc[2]; o[3] = tacc[3]; o[4] = tprev - tstart; o[5] = tstart;
   }
 #endif
-  if (a.ztab) interp_into(a, rowc, g, yacc);
+  if (ADD) {       // xr holds this row's addrows by now
+#pragma unroll
+    for (int t = 0; t < TKG; ++t) { yacc[t].x += xr[t].x; yacc[t].y += xr[t].y; yacc[t].z += xr[t].z; yacc[t].w += xr[t].w; }
+  }
 #ifdef OCC4D_TR_NOEPI
   {
     float tsum = 0.f;
@@ -222,14 +231,55 @@ __global__ __launch_bounds__(512, 2) void resblock_kernel(const TrunkArgs a) {
 
 // ---------------------------------------------------------------------------------------------------
 // y[:, 0 .. 32 S) = [res +] W [relu](x) + b  [+ interpolation term], K = 416, one stage per 32 output channels
+//
+// The interpolation terms (Z1: added to the output rows; Z2: a second table, stored as dense rows) take ZK = 8 neighbours.
+// The kernel holds a row's weights and the BYTE OFFSETS of its table rows (zo[j] = 4 (zidx[j] ldz + 4 g): 32 bits, the
+// launcher checks zrows ldz < 2^30) in registers, the same for every stage; a stage's table base is scalar, so a gather
+// costs no vector arithmetic.  The gathers are software-pipelined under the stage's MFMAs, one neighbour per slot:
+// neighbour j is ISSUED in group 3 j + 2, right after that group's DMA fragment, and CONSUMED three groups later, right
+// before the next DMA fragment (neighbour 7 and zconst: issued in group 23, consumed after the loop).  The hardware's
+// vmcnt is in order, and the DMA (inline asm) is invisible to the compiler's count: a wait for a gather therefore also
+// waits for everything issued before it -- the DMA fragment of its own group, as old as itself -- and for nothing issued
+// later.  The sums run in the order of interp_add4_kernel (csrc/pointops.hip), separate multiplies and adds:
+//   s = (..((0 + w0 t0) + w1 t1) + ..) + zconst,   y = (acc + (b + res)) + s
+// -- bit for bit the stand-alone pass behind the plain launch.
+constexpr int ZK = 8;
+
+__device__ __forceinline__ void zacc(f32x4& s, const float w, const f32x4 t) {
+  s.x += w * t.x; s.y += w * t.y; s.z += w * t.z; s.w += w * t.w;
+}
+__device__ __forceinline__ void add4(f32x4& s, const f32x4 t) { s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w; }
+__device__ __forceinline__ f32x4 ld4(const float* base, unsigned byte_off) {    // scalar base + 32-bit lane offset
+  return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+
+template <bool Z1, bool Z2>
 __device__ __forceinline__ void rowlin_stage(const TrunkArgs& a, int s, const float* __restrict__ frag, const f32x4* xr,
                                              int row, int rowc, int g, const float* next_src, const float* next_dst,
-                                             int wave, int lane) {
+                                             int wave, int lane, const unsigned* zo, const float* zwt) {
+  constexpr bool Z = Z1 || Z2;
   const int c0 = 32 * s + 4 * g;
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 s1a = zero4, s1b = zero4, s2a = zero4, s2b = zero4;       // the terms' sums for this stage's 2 x 4 channels
+  f32x4 g1a, g1b, g2a, g2b;                                       // the neighbour in flight
+  f32x4 k1a, k1b, k2a, k2b;                                       // zconst
+  const float* const t1 = Z1 ? a.ztab + 32 * s : nullptr;         // (wave-uniform)
+  const float* const t2 = Z2 ? a.ztab2 + 32 * s : nullptr;
+  auto issue = [&](const int j) __attribute__((always_inline)) {
+    if (Z1) { g1a = ld4(t1, zo[j]); g1b = ld4(t1 + 16, zo[j]); }
+    if (Z2) { g2a = ld4(t2, zo[j]); g2b = ld4(t2 + 16, zo[j]); }
+  };
+  auto consume = [&](const int j) __attribute__((always_inline)) {
+    // (the empty asm pins the arithmetic to this slot: left alone, instruction selection sinks every slot's adds to
+    // the end of the stage and keeps all eight neighbours' gathers in registers until then)
+    if (Z1) { zacc(s1a, zwt[j], g1a); zacc(s1b, zwt[j], g1b); asm volatile("" : "+v"(s1a), "+v"(s1b)); }
+    if (Z2) { zacc(s2a, zwt[j], g2a); zacc(s2b, zwt[j], g2b); asm volatile("" : "+v"(s2a), "+v"(s2b)); }
+  };
   // bias / residual: compiler-tracked global loads issued AFTER this stage's DMA and consumed at the END of the stage
-  // (the hardware's vmcnt is in order: consuming them earlier would wait for the DMA as well)
-  const f32x4 bz0 = *reinterpret_cast<const f32x4*>(a.b0 + c0);
-  const f32x4 bz1 = *reinterpret_cast<const f32x4*>(a.b0 + c0 + 16);
+  // (the hardware's vmcnt is in order: consuming them earlier would wait for the DMA as well; with terms, b + res is
+  // formed at the first consume slot, which waits for them anyway, and four registers are held instead of eight)
+  f32x4 bz0 = *reinterpret_cast<const f32x4*>(a.b0 + c0);
+  f32x4 bz1 = *reinterpret_cast<const f32x4*>(a.b0 + c0 + 16);
   f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
   f32x4 r0 = {0.f, 0.f, 0.f, 0.f}, r1 = {0.f, 0.f, 0.f, 0.f};
   if (a.res) {
@@ -241,7 +291,19 @@ __device__ __forceinline__ void rowlin_stage(const TrunkArgs& a, int s, const fl
     f32x4 wb = *reinterpret_cast<const f32x4*>(frag + TKG * FRAG_FLOATS);
 #pragma unroll
     for (int t = 0; t < TKG; ++t) {
-      if (t >= 2 && t <= 20 && (t - 2) % 3 == 0) dma_part(next_src, next_dst, wave, lane, (t - 2) / 3);   // (see resblock_kernel)
+      if (Z && t == 5) { add4(bz0, r0); add4(bz1, r1); asm volatile("" : "+v"(bz0), "+v"(bz1)); }
+      if (Z && t >= 5 && t <= 3 * ZK - 1 && (t - 2) % 3 == 0) consume((t - 5) / 3);
+      if (Z && t >= 2 && t <= 17 && (t - 2) % 3 == 0) {       // fragments wave + 8 i, i < 6, exist for every wave: no branch
+        const int c = wave + 8 * ((t - 2) / 3);
+        dma_frag(next_src + c * FRAG_FLOATS, lds_addr(next_dst) + (unsigned)c * (FRAG_FLOATS * 4), (unsigned)lane * 16u);
+      } else if (t >= 2 && t <= 20 && (t - 2) % 3 == 0) {
+        dma_part(next_src, next_dst, wave, lane, (t - 2) / 3);   // (see resblock_kernel)
+      }
+      if (Z && t >= 2 && t <= 3 * ZK - 1 && (t - 2) % 3 == 0) issue((t - 2) / 3);
+      if (Z && t == 3 * ZK - 1) {
+        if (Z1) { k1a = *reinterpret_cast<const f32x4*>(a.zconst + c0); k1b = *reinterpret_cast<const f32x4*>(a.zconst + c0 + 16); }
+        if (Z2) { k2a = *reinterpret_cast<const f32x4*>(a.zconst2 + c0); k2b = *reinterpret_cast<const f32x4*>(a.zconst2 + c0 + 16); }
+      }
       const f32x4 ca = wa, cb = wb;
       if (t + 1 < TKG) {
         wa = *reinterpret_cast<const f32x4*>(frag + (t + 1) * FRAG_FLOATS);
@@ -252,21 +314,20 @@ __device__ __forceinline__ void rowlin_stage(const TrunkArgs& a, int s, const fl
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  o0.x += bz0.x + r0.x; o0.y += bz0.y + r0.y; o0.z += bz0.z + r0.z; o0.w += bz0.w + r0.w;
-  o1.x += bz1.x + r1.x; o1.y += bz1.y + r1.y; o1.z += bz1.z + r1.z; o1.w += bz1.w + r1.w;
-  if (a.ztab) {
-    const f32x4 ca = *reinterpret_cast<const f32x4*>(a.zconst + c0);
-    const f32x4 cb = *reinterpret_cast<const f32x4*>(a.zconst + c0 + 16);
-    o0.x += ca.x; o0.y += ca.y; o0.z += ca.z; o0.w += ca.w;
-    o1.x += cb.x; o1.y += cb.y; o1.z += cb.z; o1.w += cb.w;
-    for (int j = 0; j < a.kz; ++j) {
-      const float w = a.zw[(int64_t)rowc * a.kz + j];
-      const float* zr = a.ztab + (int64_t)a.zidx[(int64_t)rowc * a.kz + j] * a.ldz + c0;
-      const f32x4 za = *reinterpret_cast<const f32x4*>(zr);
-      const f32x4 zb = *reinterpret_cast<const f32x4*>(zr + 16);
-      o0.x = fmaf(w, za.x, o0.x); o0.y = fmaf(w, za.y, o0.y); o0.z = fmaf(w, za.z, o0.z); o0.w = fmaf(w, za.w, o0.w);
-      o1.x = fmaf(w, zb.x, o1.x); o1.y = fmaf(w, zb.y, o1.y); o1.z = fmaf(w, zb.z, o1.z); o1.w = fmaf(w, zb.w, o1.w);
-    }
+  if (Z) {
+    static_assert(3 * ZK - 1 < TKG && STAGE_FRAGS > 7 + 8 * 5, "slots inside the group loop; six fragments per wave");
+    add4(o0, bz0); add4(o1, bz1);
+    consume(ZK - 1);
+    if (Z1) { add4(s1a, k1a); add4(s1b, k1b); add4(o0, s1a); add4(o1, s1b); }
+    if (Z2) { add4(s2a, k2a); add4(s2b, k2b); }
+  } else {
+    o0.x += bz0.x + r0.x; o0.y += bz0.y + r0.y; o0.z += bz0.z + r0.z; o0.w += bz0.w + r0.w;
+    o1.x += bz1.x + r1.x; o1.y += bz1.y + r1.y; o1.z += bz1.z + r1.z; o1.w += bz1.w + r1.w;
+  }
+  if (Z2 && row < a.n) {
+    float* dp = a.dense + (int64_t)row * a.ldd + c0;
+    *reinterpret_cast<f32x4*>(dp) = s2a;
+    *reinterpret_cast<f32x4*>(dp + 16) = s2b;
   }
   if (a.mask) {      // dx = (x > 0) ? dx : 0: the ReLU of a relu_in layer, applied to its data gradient in the epilogue
     const f32x4 m0 = *reinterpret_cast<const f32x4*>(a.mask + (int64_t)rowc * a.ldm + c0);
@@ -281,6 +342,7 @@ __device__ __forceinline__ void rowlin_stage(const TrunkArgs& a, int s, const fl
   }
 }
 
+template <bool Z1, bool Z2>
 __global__ __launch_bounds__(512, 2) void rowlin_kernel(const TrunkArgs a) {
   __shared__ __attribute__((aligned(16))) float bufA[STAGE_FLOATS];
   __shared__ __attribute__((aligned(16))) float bufB[STAGE_FLOATS];
@@ -298,32 +360,51 @@ __global__ __launch_bounds__(512, 2) void rowlin_kernel(const TrunkArgs a) {
       xr[t] = a.relu_in ? relu4(v) : v;
     }
   }
+  // this row's table row offsets (bytes, this lane's channels 4 g ..) and weights: the same for every stage
+  unsigned zo[ZK];
+  float zwt[ZK];
+#pragma unroll
+  for (int j = 0; j < ZK; ++j) {
+    zo[j] = (Z1 || Z2) ? 4u * ((unsigned)a.zidx[(int64_t)rowc * ZK + j] * (unsigned)a.ldz + 4u * g) : 0u;
+    zwt[j] = (Z1 || Z2) ? a.zw[(int64_t)rowc * ZK + j] : 0.f;
+  }
   dma_wait();
   __syncthreads();
   // the packed stream carries n_stages + 1 stages (the last repeats stage 0): prefetching is branch-free
 #pragma clang loop unroll(disable)
   for (int s = 0; s < a.n_stages; s += 2) {
-    rowlin_stage(a, s, bufA + lane * 4, xr, row, rowc, g, a.w0p + (int64_t)(s + 1) * STAGE_FLOATS, bufB, wave, lane);
+    rowlin_stage<Z1, Z2>(a, s, bufA + lane * 4, xr, row, rowc, g, a.w0p + (int64_t)(s + 1) * STAGE_FLOATS, bufB, wave, lane, zo,
+                         zwt);
     dma_wait();
     __syncthreads();
     if (s + 1 < a.n_stages)
-      rowlin_stage(a, s + 1, bufB + lane * 4, xr, row, rowc, g, a.w0p + (int64_t)(s + 2) * STAGE_FLOATS, bufA, wave, lane);
+      rowlin_stage<Z1, Z2>(a, s + 1, bufB + lane * 4, xr, row, rowc, g, a.w0p + (int64_t)(s + 2) * STAGE_FLOATS, bufA, wave, lane,
+                           zo, zwt);
     dma_wait();
     __syncthreads();
   }
 }
 
-// Host side of the two rowlin entry points: the struct, the argument checks (`masked`: a mask is required) and the launch.
-int rowlin_launch(const char* who, const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed, const float* b,
-                  int n_out, int relu_in, const float* res, int64_t ldr, const float* zconst, const float* ztab, int64_t ldz,
-                  const int32_t* zidx, const float* zw, int kz, bool masked, const float* mask, int64_t ldm, int n,
-                  void* stream) {
-  if (n == 0) return OCC4D_OK;               // (an empty batch has no storage: nothing to check)
-  TrunkArgs a{x, ldx, y, ldy, w_packed, b, nullptr, nullptr, res, ldr, zconst, ztab, ldz, zidx, zw, kz, n,
-              n_out / 32, relu_in, mask, ldm};
+// Host side of the rowlin entry points: the argument checks (`masked`: a mask is required) and the launch.  The terms of
+// `a` (ztab: added; ztab2: stored to a.dense) run inside the stages: kz == 8 and 32-bit table offsets, which
+// occ4d_rowlin_linz_f32 checks (occ4d_rowlin_f32 never passes a term down here).
+int rowlin_launch(const char* who, const TrunkArgs& a, int n_out, bool masked, void* stream) {
   if (int rc = occ4d::check_rowlin_args(a, who, TH, 32, n_out, masked)) return rc;
-  rowlin_kernel<<<occ4d::cdiv(n, TROWS), 512, 0, (hipStream_t)stream>>>(a);
+  const dim3 grid(occ4d::cdiv(a.n, TROWS));
+  hipStream_t st = (hipStream_t)stream;
+  if (a.ztab && a.ztab2) rowlin_kernel<true, true><<<grid, 512, 0, st>>>(a);
+  else if (a.ztab) rowlin_kernel<true, false><<<grid, 512, 0, st>>>(a);
+  else if (a.ztab2) rowlin_kernel<false, true><<<grid, 512, 0, st>>>(a);
+  else rowlin_kernel<false, false><<<grid, 512, 0, st>>>(a);
   return occ4d::check_launch(who);
+}
+
+TrunkArgs rowlin_args(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed, const float* b, int n_out,
+                      int relu_in, const float* res, int64_t ldr, const float* mask, int64_t ldm, int n) {
+  TrunkArgs a{};
+  a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.w0p = w_packed; a.b0 = b; a.res = res; a.ldr = ldr;
+  a.n = n; a.n_stages = n_out / 32; a.relu_in = relu_in; a.mask = mask; a.ldm = ldm;
+  return a;
 }
 
 }  // namespace
@@ -331,25 +412,73 @@ int rowlin_launch(const char* who, const float* x, int64_t ldx, float* y, int64_
 extern "C" int occ4d_trunk_width(void) { return TH; }
 extern "C" int64_t occ4d_trunk_packed_floats(int n_out) { return (int64_t)(n_out / 32 + 1) * STAGE_FLOATS; }
 
+// occ4d_resblock_f32 keeps its interpolation arguments: the term is the stand-alone pass behind the block (the block's
+// own epilogue of exposed gathers is gone; the decoder hides the term with occ4d_resblock_addrows_f32)
 extern "C" int occ4d_resblock_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w0_packed,
                                   const float* b0, const float* w1_packed, const float* b1, const float* zconst,
                                   const float* ztab, int64_t ldz, const int32_t* zidx, const float* zw, int kz, int n,
                                   void* stream) {
-  TrunkArgs a{x, ldx, y, ldy, w0_packed, b0, w1_packed, b1, nullptr, 0, zconst, ztab, ldz, zidx, zw, kz, n, TNS, 1, nullptr, 0};
+  TrunkArgs a{};
+  a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.w0p = w0_packed; a.b0 = b0; a.w1p = w1_packed; a.b1 = b1;
+  a.zconst = zconst; a.ztab = ztab; a.ldz = ldz; a.zidx = zidx; a.zw = zw; a.kz = kz; a.n = n; a.n_stages = TNS; a.relu_in = 1;
   if (n == 0) return OCC4D_OK;               // (an empty batch has no storage: nothing to check)
   if (int rc = occ4d::check_trunk_args(a, "occ4d_resblock_f32", TH)) return rc;
   OCC4D_REQUIRE(w1_packed && b1 && ((uintptr_t)w1_packed % 16) == 0 && ((uintptr_t)b1 % 16) == 0 && ldy >= TH,
                 "occ4d_resblock_f32: second layer weights / bias missing or misaligned");
-  resblock_kernel<<<occ4d::cdiv(n, TROWS), 512, 0, (hipStream_t)stream>>>(a);
-  return occ4d::check_launch("occ4d_resblock_f32");
+  resblock_kernel<false><<<occ4d::cdiv(n, TROWS), 512, 0, (hipStream_t)stream>>>(a);
+  if (int rc = occ4d::check_launch("occ4d_resblock_f32")) return rc;
+  return ztab ? occ4d_interp_add_f32(y, ldy, zconst, ztab, ldz, zidx, zw, n, kz, TH, stream) : OCC4D_OK;
+}
+
+// y = x + W1 relu(W0 relu(x) + b0) + b1 + addrows: the dense rows are added last, from loads that sit under the last
+// hidden chunk's MFMAs (include/ext/occ4d_linz.h)
+extern "C" int occ4d_resblock_addrows_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w0_packed,
+                                          const float* b0, const float* w1_packed, const float* b1, const float* addrows,
+                                          int64_t ld_add, int n, void* stream) {
+  const char* who = "occ4d_resblock_addrows_f32";
+  TrunkArgs a{};
+  a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.w0p = w0_packed; a.b0 = b0; a.w1p = w1_packed; a.b1 = b1;
+  a.addrows = addrows; a.lda = ld_add; a.n = n; a.n_stages = TNS; a.relu_in = 1;
+  if (n == 0) return OCC4D_OK;               // (an empty batch has no storage: nothing to check)
+  if (int rc = occ4d::check_trunk_args(a, who, TH)) return rc;
+  OCC4D_REQUIRE(w1_packed && b1 && ((uintptr_t)w1_packed % 16) == 0 && ((uintptr_t)b1 % 16) == 0 && ldy >= TH,
+                "%s: second layer weights / bias missing or misaligned", who);
+  if (int rc = occ4d::check_addrows_args(a, who, TH)) return rc;
+  resblock_kernel<true><<<occ4d::cdiv(n, TROWS), 512, 0, (hipStream_t)stream>>>(a);
+  return occ4d::check_launch(who);
 }
 
 extern "C" int occ4d_rowlin_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed,
                                 const float* b, int n_out, int relu_in, const float* res, int64_t ldr,
                                 const float* zconst, const float* ztab, int64_t ldz, const int32_t* zidx,
                                 const float* zw, int kz, int n, void* stream) {
-  return rowlin_launch("occ4d_rowlin_f32", x, ldx, y, ldy, w_packed, b, n_out, relu_in, res, ldr, zconst, ztab, ldz, zidx, zw,
-                       kz, false, nullptr, 0, n, stream);
+  const char* who = "occ4d_rowlin_f32";
+  if (n == 0) return OCC4D_OK;               // (an empty batch has no storage: nothing to check)
+  TrunkArgs a = rowlin_args(x, ldx, y, ldy, w_packed, b, n_out, relu_in, res, ldr, nullptr, 0, n);
+  a.zconst = zconst; a.ztab = ztab; a.ldz = ldz; a.zidx = zidx; a.zw = zw; a.kz = kz;
+  if (!ztab) return rowlin_launch(who, a, n_out, false, stream);
+  // the interpolation arguments keep working, for any kz and any table size: the contract as before, the term as the
+  // stand-alone pass behind the plain launch (inside the stages: occ4d_rowlin_linz_f32)
+  if (int rc = occ4d::check_rowlin_args(a, who, TH, 32, n_out, false)) return rc;
+  a.zconst = a.ztab = nullptr;
+  if (int rc = rowlin_launch(who, a, n_out, false, stream)) return rc;
+  return occ4d_interp_add_f32(y, ldy, zconst, ztab, ldz, zidx, zw, n, kz, n_out, stream);
+}
+
+// occ4d_rowlin_f32 with up to two interpolation terms over the same neighbour lists, both inside the stages: the first
+// added to y, the second stored to `dense` (include/ext/occ4d_linz.h)
+extern "C" int occ4d_rowlin_linz_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed,
+                                     const float* b, int n_out, int relu_in, const float* res, int64_t ldr,
+                                     const float* zconst, const float* ztab, const float* zconst2, const float* ztab2,
+                                     int64_t ldz, int zrows, const int32_t* zidx, const float* zw, int kz, float* dense,
+                                     int64_t ldd, int n, void* stream) {
+  const char* who = "occ4d_rowlin_linz_f32";
+  if (n == 0) return OCC4D_OK;               // (an empty batch has no storage: nothing to check)
+  TrunkArgs a = rowlin_args(x, ldx, y, ldy, w_packed, b, n_out, relu_in, res, ldr, nullptr, 0, n);
+  a.zconst = zconst; a.ztab = ztab; a.ldz = ldz; a.zidx = zidx; a.zw = zw; a.kz = kz;
+  a.zconst2 = zconst2; a.ztab2 = ztab2; a.dense = dense; a.ldd = ldd; a.zrows = zrows;
+  if (int rc = occ4d::check_linz_args(a, who, ZK, n_out)) return rc;
+  return rowlin_launch(who, a, n_out, false, stream);
 }
 
 // y = mask > 0 ? ([res +] W [relu](x) + b) : 0 -- occ4d_rowlin_f32 with the ReLU mask of a data gradient applied in
@@ -357,6 +486,7 @@ extern "C" int occ4d_rowlin_f32(const float* x, int64_t ldx, float* y, int64_t l
 extern "C" int occ4d_rowlin_masked_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w_packed,
                                        const float* b, int n_out, int relu_in, const float* res, int64_t ldr,
                                        const float* mask, int64_t ldm, int n, void* stream) {
-  return rowlin_launch("occ4d_rowlin_masked_f32", x, ldx, y, ldy, w_packed, b, n_out, relu_in, res, ldr, nullptr, nullptr, 0,
-                       nullptr, nullptr, 0, true, mask, ldm, n, stream);
+  if (n == 0) return OCC4D_OK;               // (an empty batch has no storage: nothing to check)
+  return rowlin_launch("occ4d_rowlin_masked_f32", rowlin_args(x, ldx, y, ldy, w_packed, b, n_out, relu_in, res, ldr, mask, ldm, n),
+                       n_out, true, stream);
 }

@@ -43,8 +43,11 @@ class Selection:
     attn16: bool = True               # d = 416: csrc/crossattn16p.hip; False: csrc/crossattn.hip (OCC4D_PATH_FIRST_GEN)
     trunk_kernels: bool = True        # row-resident trunk kernels; False: the generic Linear kernel
     trunk4: bool = False              # half-CU trunk kernels (csrc/trunk4.hip): measured slower at the decode chunk
-    fused_interp: bool = False        # A/B only: lin_z table term of block i + 1 in block i's epilogue (the fp32 fused
-                                      # block's; without effect under trunk4 or a split trunk_precision)
+    fused_interp: bool = False        # accepted, selects nothing the default does not do (OCC4D_PATH_FUSED_INTERP: it put the lin_z term
+                                      # of block i + 1 into block i's epilogue as exposed gathers, measured neutral)
+    linz_shadow: bool = True          # the decoder's lin_z terms inside the trunk kernels, under their MFMAs (the post
+                                      # Linear of a cross layer adds the next block's term and stores the one after as dense rows,
+                                      # which the block between adds); False: six stand-alone passes (OCC4D_LINZ_PATH_STANDALONE, A/B)
     logit_precision: str = 'f32'      # the d = 416 attention layers' GEMMs
     trunk_precision: str = 'f32'      # the decoder's 416-input Linear layers (residual blocks, query projection, layer3)
     train_precision: str = 'f32'      # training path: forward Linears, data gradients, pair-tensor recompute ('f32' | 'bf16x6')
@@ -87,6 +90,8 @@ class Selection:
             f |= L.PATH_TRUNK4
         if self.fused_interp:
             f |= L.PATH_FUSED_INTERP
+        if not self.linz_shadow:
+            f |= L.LINZ_CONSTANTS['PATH_STANDALONE']
         return f
 
     def replace(self, **kw):
@@ -110,6 +115,7 @@ def _from_environment():
     return Selection(
         trunk4=_env_flag('OCC4D_TRUNK4', '0'),
         fused_interp=_env_flag('OCC4D_FUSED_INTERP', '0'),
+        linz_shadow=_env_flag('OCC4D_LINZ_SHADOW', '1'),
         logit_precision=os.environ.get('OCC4D_LOGIT_PRECISION', 'f32'),
         trunk_precision=os.environ.get('OCC4D_TRUNK_PRECISION', 'f32'),
         train_precision=os.environ.get('OCC4D_TRAIN_PRECISION', 'f32'),

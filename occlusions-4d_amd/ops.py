@@ -810,12 +810,22 @@ def _interp_args(interp, n):
     return (_ptr(zc), _ptr(zt), ldz, _ptr(idx), _ptr(_dev(w, name='w')), idx.shape[1], (zc, zt))
 
 
-def resblock(x, w0_packed, b0, w1_packed, b1, out=None, interp=None):
-    """out = x + W1 relu(W0 relu(x) + b0) + b1 [+ interpolation term]: one fused kernel (occ4d_resblock_f32)."""
+def resblock(x, w0_packed, b0, w1_packed, b1, out=None, interp=None, addrows=None):
+    """out = x + W1 relu(W0 relu(x) + b0) + b1 [+ interpolation term]: one fused kernel (occ4d_resblock_f32; the term is
+    the stand-alone pass behind it).  addrows (n, 416): out = block(x) + addrows in one launch, the rows loaded under the
+    last hidden chunk (occ4d_resblock_addrows_f32, include/ext/occ4d_linz.h); they must not alias out."""
     xx, ldx = _rows(_dev(x, name='x'), 'x')
     n, d = xx.shape
     assert d == TRUNK_WIDTH
     o, ldo = _out(out, (n, d), x.device)
+    if addrows is not None:
+        assert interp is None and (w0_packed is None or w0_packed.numel() == 14 * 13312), 'resblock: addrows takes the full-CU packing'
+        aa, lda = _rows(_dev(addrows, name='addrows'), 'addrows')
+        assert aa.shape == (n, d)
+        b0c, b1c = _dev(b0).contiguous(), _dev(b1).contiguous()
+        _lib.check(_launch('resblock', dict(n=n), 4.0 * n * d * d, lambda: _lib.lib().occ4d_resblock_addrows_f32(
+            _ptr(xx), ldx, _ptr(o), ldo, _ptr(w0_packed), _ptr(b0c), _ptr(w1_packed), _ptr(b1c), _ptr(aa), lda, n, _stream())))
+        return o
     ia = _interp_args(interp, n)
     b0c, b1c = _dev(b0).contiguous(), _dev(b1).contiguous()
     # the packing tells the kernel generation: 27 stages of 6656 floats = csrc/trunk4.hip, 14 of 13312 = csrc/trunk.hip
@@ -863,6 +873,44 @@ def rowlin(x, w_packed, b, n_out, relu_in=False, residual=None, out=None, interp
         args += ia[:6]
     _lib.check(_launch('rowlin', dict(n=n, n_out=n_out), 2.0 * n * d * n_out, lambda: fn(*args, n, _stream())))
     return o
+
+
+def rowlin_linz(x, w_packed, b, n_out, idx, w, term=None, term2=None, relu_in=False, residual=None, out=None, dense=None):
+    """occ4d_rowlin_linz_f32 (include/ext/occ4d_linz.h): out (n, n_out) = ([residual +] W [relu](x) + b) + s1 and
+    dense (n, n_out) = s2, the interpolation terms s_t = sum_j w[:, j] ztab_t[idx[:, j]] + zconst_t of `term` = (zconst,
+    ztab) and `term2`, both tables row views of the same stride, gathered under the stages' MFMAs.  Returns (out, dense);
+    dense is None without term2."""
+    xx, ldx = _rows(_dev(x, name='x'), 'x')
+    n, d = xx.shape
+    assert d == TRUNK_WIDTH and n_out % 32 == 0 and w_packed.numel() == (n_out // 32 + 1) * 13312
+    o, ldo = _out(out, (n, n_out), x.device)
+    rr, ldr = (None, 0)
+    if residual is not None:
+        rr, ldr = _rows(_dev(residual, name='residual'), 'residual')
+        assert rr.shape == (n, n_out)
+    bc = _dev(b).contiguous()
+    assert bc.numel() == n_out
+    idx = _dev(idx, torch.int32, 'idx')
+    w = _dev(w, name='w')
+    assert idx.is_contiguous() and w.is_contiguous() and idx.shape == w.shape and idx.shape[0] == n
+    keep, ptrs, ldz, zrows = [], [], 0, 0
+    for t in (term, term2):
+        if t is None:
+            ptrs += [None, None]
+            continue
+        zc = _dev(t[0]).contiguous()
+        zt, ld = _rows(_dev(t[1], name='ztab'), 'ztab')
+        assert zc.numel() == n_out and zt.shape[1] == n_out and ldz in (0, ld), 'rowlin_linz: one row stride for both tables'
+        ldz, zrows = ld, zt.shape[0]
+        keep += [zc, zt]
+        ptrs += [_ptr(zc), _ptr(zt)]
+    dd, ldd = (None, 0)
+    if term2 is not None or dense is not None:
+        dd, ldd = _out(dense, (n, n_out), x.device)
+    _lib.check(_launch('rowlin', dict(n=n, n_out=n_out), 2.0 * n * d * n_out, lambda: _lib.lib().occ4d_rowlin_linz_f32(
+        _ptr(xx), ldx, _ptr(o), ldo, _ptr(w_packed), _ptr(bc), n_out, int(relu_in), _ptr(rr), ldr, ptrs[0], ptrs[1], ptrs[2],
+        ptrs[3], ldz, zrows, _ptr(idx), _ptr(w), idx.shape[1], _ptr(dd), ldd, n, _stream())))
+    return o, dd
 
 
 # --------------------------------------------------------------------------------------
