@@ -21,7 +21,7 @@ from . import frontend  # noqa: F401   (frames -> clouds on the device: greater_
 from . import projection  # noqa: F401   (clouds -> camera views: projection, z-buffer, visibility codes)
 from . import components  # noqa: F401   (connected components of the decoded occupancy: Components, label, boxes_and_centroids; linked across frames: Tracker, tracks)
 from . import distance  # noqa: F401   (the distance transform of the decoded occupancy: Clearance, transform, metric, signed, expand_labels)
-from . import geodesic  # noqa: F401   (shortest free-space paths over the clearance: Route, solve, grid_index, metric, paths_to_world)
+from . import geodesic  # noqa: F401   (shortest free-space paths over the clearance: Route, solve, grid_index, metric, paths_to_world; pulled straight into waypoints: straight, pull, polyline_length)
 from . import watershed  # noqa: F401   (touching objects split at their necks: Segments, split)
 from . import sight  # noqa: F401   (line of sight through the decoded occupancy: Sight, look, grid_origin, codes, by_label)
 from . import cpu_twin  # noqa: F401   (explicit opt-in only: pk.cpu_twin.enable(); never a fallback)

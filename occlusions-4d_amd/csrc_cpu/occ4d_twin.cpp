@@ -38,6 +38,7 @@
 #include "ext/occ4d_geodesic.h"
 #include "ext/occ4d_watershed.h"
 #include "ext/occ4d_sight.h"
+#include "ext/occ4d_pull.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -54,6 +55,7 @@
 #include "geodesic_math.hpp"
 #include "watershed_math.hpp"
 #include "sight_math.hpp"
+#include "pull_math.hpp"
 #include "decoder_math.hpp"
 
 namespace fe = occ4d_frontend;
@@ -71,6 +73,7 @@ namespace dm = occ4d_distance;
 namespace gm = occ4d_geodesic;
 namespace ws = occ4d_watershed;
 namespace sm = occ4d_sight;
+namespace pm = occ4d_pull;
 
 static thread_local char g_err[512] = "";
 
@@ -1010,6 +1013,53 @@ int occ4d_sight_grid_u32(const uint32_t* bits, int nx, int ny, int nz, const int
   for (int x = 0; x < nx; ++x)
     for (int y = 0; y < ny; ++y)
       for (int z = 0; z < nz; ++z) sm::query_item(a, sm::GlobalWords{bits}, x, y, z);
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- pull
+// include/ext/occ4d_pull.h: the blocked test, HIT and the candidate test of csrc/pull_math.hpp, GOALS AND CANDIDATES IN ORDER: per
+// anchor the candidates from the far end one at a time, the first free one is the largest.
+int occ4d_pull_bits_i32(const int32_t* clear, int min_clear, int64_t n, uint32_t* blocked, void*) {
+  pm::BitsArgs a; bool empty;
+  OCC4D_TRY(pm::check_bits(clear, min_clear, n, blocked, empty, a));
+  if (empty) return OCC4D_OK;
+  for (int64_t w = 0; w < a.words; ++w) {
+    uint32_t word = 0;
+    for (int64_t p = w * 32; p < n && p < w * 32 + 32; ++p) word |= (uint32_t)pm::blocked_at(a, p) << (p & 31);
+    blocked[w] = word;
+  }
+  return OCC4D_OK;
+}
+int occ4d_pull_pairs_u32(const uint32_t* blocked, int nx, int ny, int nz, const int32_t* a, const int32_t* b, int n_pairs, int32_t* hit,
+                         void*) {
+  pm::PairArgs args; bool empty;
+  OCC4D_TRY(pm::check_pairs(blocked, nx, ny, nz, a, b, n_pairs, hit, empty, args));
+  if (empty) return OCC4D_OK;
+  for (int i = 0; i < n_pairs; ++i) hit[i] = pm::hit(args.n, args.points, sm::GlobalWords{blocked}, a[i], b[i]);
+  return OCC4D_OK;
+}
+int occ4d_pull_paths_i32(const uint32_t* blocked, int nx, int ny, int nz, const int32_t* paths, const int32_t* path_len, int n_goals,
+                         int cap, int32_t* waypoints, int32_t* waypoint_len, void*) {
+  pm::PathArgs a; bool empty;
+  OCC4D_TRY(pm::check_paths(blocked, nx, ny, nz, paths, path_len, n_goals, cap, waypoints, waypoint_len, empty, a));
+  if (empty) return OCC4D_OK;
+  const sm::GlobalWords words{blocked};
+  for (int g = 0; g < n_goals; ++g) {
+    const int32_t* row = paths + (int64_t)g * cap;
+    int32_t* out = waypoints + (int64_t)g * cap;
+    const int L = pm::chain_length(a, g);
+    int k = 0, count = 0;
+    for (int anchor = 0; anchor < cap && L > 0; ++anchor) {
+      out[count++] = row[k];
+      if (k >= L - 1) break;
+      int next = k + 1;                                           // the fallback: the original move, untested
+      for (int j = L - 1; j > k + 1; --j)
+        if (pm::candidate_free(a, words, row, L, k, j)) { next = j; break; }
+      k = next;
+    }
+    for (int c = count; c < cap; ++c) out[c] = -1;
+    waypoint_len[g] = L > 0 ? count : path_len[g];
+  }
   return OCC4D_OK;
 }
 

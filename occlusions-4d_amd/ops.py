@@ -1923,6 +1923,63 @@ def geodesic_trace(cost, parent, goals, cap, out=None):
     return paths, path_len
 
 
+def _blocked_words(blocked, counts):
+    """(the contiguous (ceil(n / 32),) int32 words of ops.grid_blocked_bits, nx, ny, nz) for the grid `counts`."""
+    nx, ny, nz = (int(c) for c in counts)
+    words = _dev(blocked, torch.int32, 'blocked')
+    assert words.dim() == 1 and words.shape[0] == (max(nx * ny * nz, 0) + 31) // 32 and words.is_contiguous(), \
+        'blocked must be a contiguous (%d,) tensor, got %s' % ((max(nx * ny * nz, 0) + 31) // 32, tuple(words.shape))
+    return words, nx, ny, nz
+
+
+def grid_blocked_bits(clear, min_clear=1):
+    """The blocked set !(clear >= min_clear), the complement of ops.grid_geodesic's passable set, packed one bit per grid point
+    (occ4d_pull_bits_i32, the rules in include/ext/occ4d_pull.h): clear (n,) int32 -> (ceil(n / 32),) int32 on the device, bit
+    p % 32 of word p // 32 is point p, the unused bits of the last word are 0.  One launch, no host read."""
+    n = int(clear.shape[0])
+    c, _ = _inst_column(clear, n, 'clear', torch.int32)
+    c = c if c.is_contiguous() else c.contiguous()
+    bits = torch.empty(((n + 31) // 32,), dtype=torch.int32, device=c.device)
+    _lib.check(_lib.lib().occ4d_pull_bits_i32(_ptr(c), int(min_clear), n, _ptr(bits), _stream()))
+    return bits
+
+
+def grid_segments(blocked, counts, a, b):
+    """Line of sight between arbitrary pairs of points of the (nx, ny, nz) = `counts` grid (occ4d_pull_pairs_u32, HIT of include/
+    ext/occ4d_pull.h): blocked (ceil(n / 32),) int32 from ops.grid_blocked_bits, a, b (P,) int32 flat indices, any values.
+    -> hit (P,) int32 on the device: -1 where the segment a -> b is free, -2 where an index is outside the grid, else the flat
+    index of the first blocked cell (a or b itself when blocked).  One launch, no host read."""
+    words, nx, ny, nz = _blocked_words(blocked, counts)
+    a, b = _dev(a, torch.int32, 'a'), _dev(b, torch.int32, 'b')
+    assert a.dim() == 1 and a.shape == b.shape, 'a and b must be (P,) tensors of one length, got %s and %s' % (tuple(a.shape), tuple(b.shape))
+    a, b = (t if t.is_contiguous() else t.contiguous() for t in (a, b))
+    hit = torch.empty((a.shape[0],), dtype=torch.int32, device=words.device)
+    _lib.check(_lib.lib().occ4d_pull_pairs_u32(_ptr(words), nx, ny, nz, _ptr(a), _ptr(b), a.shape[0], _ptr(hit), _stream()))
+    return hit
+
+
+def geodesic_pull(blocked, counts, paths, path_len, out=None):
+    """The traced paths of ops.geodesic_trace pulled straight (occ4d_pull_paths_i32, PULL of include/ext/occ4d_pull.h): blocked
+    (ceil(n / 32),) int32 from ops.grid_blocked_bits, paths (G, cap) int32, path_len (G,) int32.  `out` = (waypoints, waypoint_len):
+    the caller's contiguous int32 buffers (>= G * cap, >= G).  -> (waypoints (G, cap) int32: a subsequence of the path, goal first,
+    whose legs are free segments or single moves of the path, -1 behind it; waypoint_len (G,) int32: their number, path_len itself
+    where that is <= 0 or > cap), on the device.  One launch, one workgroup per goal.  No host read."""
+    words, nx, ny, nz = _blocked_words(blocked, counts)
+    p, length = _dev(paths, torch.int32, 'paths'), _dev(path_len, torch.int32, 'path_len')
+    assert p.dim() == 2 and tuple(length.shape) == (p.shape[0],) and p.is_contiguous() and length.is_contiguous(), \
+        'paths and path_len must be contiguous (G, cap) and (G,) tensors, got %s and %s' % (tuple(p.shape), tuple(length.shape))
+    goals, cap = int(p.shape[0]), int(p.shape[1])
+    out = (None, None) if out is None else out
+    waypoints = _int32_out(out[0], (goals, cap), words.device, 'out waypoints')
+    waypoint_len = _int32_out(out[1], (goals,), words.device, 'out waypoint_len')
+    if goals and nx * ny * nz <= 0:
+        waypoints.fill_(-1)              # (the entry point touches no pointer of an empty grid, where the trace leaves no chain)
+        waypoint_len.copy_(length)
+    _lib.check(_lib.lib().occ4d_pull_paths_i32(_ptr(words), nx, ny, nz, _ptr(p), _ptr(length), goals, cap, _ptr(waypoints),
+                                               _ptr(waypoint_len), _stream()))
+    return waypoints, waypoint_len
+
+
 def link_work_len(n, cap):
     """Elements of the int32 work array of occ4d_link_overlap_i32 for n grid points and `cap` pair rows (the formula of the
     header): 4 * slots + n + 2 * tiles with slots the smallest power of two >= max(2 * min(cap, n), MIN_SLOTS), at most 2^31."""
