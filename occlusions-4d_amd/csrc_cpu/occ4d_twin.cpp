@@ -39,6 +39,7 @@
 #include "ext/occ4d_watershed.h"
 #include "ext/occ4d_sight.h"
 #include "ext/occ4d_pull.h"
+#include "ext/occ4d_viewplan.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -56,6 +57,7 @@
 #include "watershed_math.hpp"
 #include "sight_math.hpp"
 #include "pull_math.hpp"
+#include "viewplan_math.hpp"
 #include "decoder_math.hpp"
 
 namespace fe = occ4d_frontend;
@@ -74,6 +76,7 @@ namespace gm = occ4d_geodesic;
 namespace ws = occ4d_watershed;
 namespace sm = occ4d_sight;
 namespace pm = occ4d_pull;
+namespace vm = occ4d_viewplan;
 
 static thread_local char g_err[512] = "";
 
@@ -1059,6 +1062,69 @@ int occ4d_pull_paths_i32(const uint32_t* blocked, int nx, int ny, int nz, const 
     }
     for (int c = count; c < cap; ++c) out[c] = -1;
     waypoint_len[g] = L > 0 ? count : path_len[g];
+  }
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- viewplan
+// include/ext/occ4d_viewplan.h: DEAD, RANGE and the pair test of csrc/viewplan_math.hpp, CANDIDATES, WORDS AND BITS IN ORDER; GREEDY
+// over the same work array, rows and keys, each count a plain sum and the best key a plain maximum.
+int occ4d_viewplan_visible_u32(const uint32_t* solid, int nx, int ny, int nz, const uint32_t* targets, const int32_t* candidates, int C,
+                               int wx, int wy, int wz, int64_t max_dist2, uint32_t* vis, void*) {
+  vm::VisArgs a; bool empty;
+  OCC4D_TRY(vm::check_visible(solid, nx, ny, nz, targets, candidates, C, wx, wy, wz, max_dist2, vis, empty, a));
+  if (empty) return OCC4D_OK;
+  const sm::GlobalWords words{solid};
+  for (int c = 0; c < C; ++c) {
+    const vm::Candidate k = vm::candidate_at(a, words, c);
+    for (int64_t w = 0; w < a.words; ++w) {
+      uint32_t word = 0;
+      for (int64_t p = w * 32; p < w * 32 + 32; ++p) {
+        if (!vm::target_at(a, p)) continue;
+        int px, py, pz;
+        vm::point_of(a, (int32_t)p, px, py, pz);
+        word |= (uint32_t)vm::sees(a, words, px, py, pz, k) << (p & 31);
+      }
+      vis[(int64_t)c * a.words + w] = word;
+    }
+  }
+  return OCC4D_OK;
+}
+int occ4d_viewplan_greedy_u32(const uint32_t* vis, int C, int64_t W, const uint32_t* targets, int k, int32_t* work, int32_t* gain,
+                              int32_t* picks, int32_t* pick_gain, int32_t* status, void*) {
+  vm::GreedyArgs a; bool empty;
+  OCC4D_TRY(vm::check_greedy(vis, C, W, targets, k, work, gain, picks, pick_gain, status, empty, a));
+  if (empty) return OCC4D_OK;
+  uint32_t* remaining = vm::remaining_of(a);
+  int32_t *count = vm::count_of(a), *flag = vm::flag_of(a);
+  for (int64_t w = 0; w < W; ++w) remaining[w] = targets[w];
+  *flag = 1;
+  for (int round = 0; round < std::max(k, 1); ++round) {
+    if (*flag == 0) {                                             // behind a -1 pick
+      picks[round] = -1, pick_gain[round] = 0;
+      continue;
+    }
+    unsigned long long key = 0;
+    for (int row = 0; row < C + (round == 0); ++row) {
+      int32_t sum = 0;
+      for (int64_t w = 0; w < W; ++w) sum += __builtin_popcount(vm::row_word(a, row, w) & remaining[w]);
+      count[row] = sum;
+      if (row < C) key = std::max(key, vm::key_of(sum, row));
+      if (row < C && round == 0) gain[row] = sum;
+    }
+    if (round == 0) status[0] = status[1] = count[C];
+    if (round >= k) break;                                        // k == 0: gain and status only
+    if (!vm::key_picks(a, key)) {
+      picks[round] = -1, pick_gain[round] = 0, *flag = 0;
+      continue;
+    }
+    const int best = vm::key_pick(key);
+    int32_t left = 0;
+    for (int64_t w = 0; w < W; ++w) {
+      remaining[w] &= ~vis[(int64_t)best * W + w];
+      left += __builtin_popcount(remaining[w]);
+    }
+    status[1] = left, picks[round] = best, pick_gain[round] = vm::key_count(key);
   }
   return OCC4D_OK;
 }

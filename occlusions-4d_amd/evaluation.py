@@ -333,7 +333,7 @@ def occlusion_groups(live_occl_row, valo_ids_pad, num_valo_ids, n_ids, edges=(0.
 def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt=False, reuse_encode=True, stats=None,
                   stats_group_fn=None, stats_occlusion=None, inst_stats=None, inst_group_fn=None, refine=None, surface=None,
                   meshes=None, views=None, images=None, components=None, objects=None, tracker=None, clearance=None,
-                  clearances=None, sight=None, sights=None, segments=None, parts=None, route=None, routes=None):
+                  clearances=None, next_view=None, next_views=None, sight=None, sights=None, segments=None, parts=None, route=None, routes=None):
     """batch: dict with 'pcl_input' (1,N,8), 'pcl_input_sem' (1,N,1-3), 'pcl_target' list of (1,T,9-11) tensors and
     batch['meta_data']['pcl_target_size'] (list of (1,) tensors), as the reference's test data loader yields them
     (data/data_greater.py:593-606, data/data_carla.py:651-661).  args: namespace with the test_args fields used
@@ -346,9 +346,9 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
     inst_stats: an InstanceStats that every output frame is added to in the same way (track_mode 'all': the instance
     labelling); inst_group_fn(time_idx, frame_rows) -> (n_ids,) integer array: the group of every instance id, None: group 0.
     refine: an inference.GridRefine handed to every perform_inference call (the coarse-to-fine decode of the query grid), or None.
-    surface / meshes, views / images, components / objects, clearance / clearances, segments / parts, sight / sights, route / routes: a grid product's
+    surface / meshes, views / images, components / objects, clearance / clearances, segments / parts, sight / sights, next_view / next_views, route / routes: a grid product's
     option object (surface.Surface, projection.FieldViews, components.Components, distance.Clearance, watershed.Segments,
-    sight.Sight, geodesic.Route; `route` needs `clearance`)
+    sight.Sight, sight.NextView, geodesic.Route; `route` needs `clearance`, `next_view` needs `sight`)
     handed to every perform_inference call, or None, and the list every output frame's result[keyword] dict is appended to (the
     tuples of pcl_all keep their contract).  An option without such a list is a ValueError; all options are checked before the
     first frame.
@@ -356,7 +356,7 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
     every dict of `objects` gains 'link' (K, 4), the frame's components linked to those of the output frame before
     (components.tracks turns the list into trajectories)."""
     chosen = products.check_clip((
-        (geodesic_mod.Route, route, routes), (sight_mod.Sight, sight, sights), (watershed_mod.Segments, segments, parts), (distance_mod.Clearance, clearance, clearances),
+        (geodesic_mod.Route, route, routes), (sight_mod.NextView, next_view, next_views), (sight_mod.Sight, sight, sights), (watershed_mod.Segments, segments, parts), (distance_mod.Clearance, clearance, clearances),
         (components_mod.Tracker, tracker, None),
         (components_mod.Components, components, objects), (projection.FieldViews, views, images), (surface_mod.Surface, surface, meshes)))
     if tracker is not None:

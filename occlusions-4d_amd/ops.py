@@ -1980,6 +1980,60 @@ def geodesic_pull(blocked, counts, paths, path_len, out=None):
     return waypoints, waypoint_len
 
 
+def viewplan_work_len(C, W):
+    """Elements of the int32 work array of occ4d_viewplan_greedy_u32 for C candidates and W words (the formula of the header):
+    remaining (W), count (C + 1), the flag word."""
+    return int(W) + int(C) + 2
+
+
+def grid_visible(solid_bits, counts, targets, candidates, max_dist2=None, weights=(1, 1, 1), out=None):
+    """Which of the target points of the (nx, ny, nz) = `counts` grid each candidate viewpoint sees (occ4d_viewplan_visible_u32, VIS
+    of include/ext/occ4d_viewplan.h): solid_bits (W,) int32 from ops.grid_solid_bits, W = ceil(n / 32); targets (W,) int32 of the
+    same layout, the points that count (ops.grid_blocked_bits(seen, 1): the points no sensor sees); candidates (C, 3) int32 lattice
+    points ON THE DEVICE, any values: one beyond 2^20 cells or inside a solid cell sees nothing (decided on the device); max_dist2:
+    None or negative = no limit, else a point counts when wx dx^2 + wy dy^2 + wz dz^2 <= max_dist2 with weights = (wx, wy, wz),
+    integers in [1, 1024].  `out`: the caller's contiguous int32 buffer (>= C * W).  -> vis (C, W) int32 on the device: bit p % 32
+    of word p // 32 of row c says that candidate c sees target point p.  One launch, no host read."""
+    words, nx, ny, nz = _blocked_words(solid_bits, counts)
+    tgt = _dev(targets, torch.int32, 'targets')
+    assert tgt.shape == words.shape and tgt.is_contiguous(), \
+        'targets must be a contiguous %s tensor, got %s' % (tuple(words.shape), tuple(tgt.shape))
+    cand = _dev(candidates, torch.int32, 'candidates')
+    assert cand.dim() == 2 and cand.shape[1] == 3, 'candidates must be (C, 3), got %s' % (tuple(cand.shape),)
+    cand = cand if cand.is_contiguous() else cand.contiguous()
+    C, W = int(cand.shape[0]), int(words.shape[0])
+    wx, wy, wz = (int(w) for w in weights)
+    vis = _int32_out(out, (C, W), words.device, 'out')
+    _lib.check(_lib.lib().occ4d_viewplan_visible_u32(_ptr(words), nx, ny, nz, _ptr(tgt), _ptr(cand), C, wx, wy, wz,
+                                                     -1 if max_dist2 is None else int(max_dist2), _ptr(vis), _stream()))
+    return vis
+
+
+def viewplan_greedy(vis, targets, k, work=None, out=None):
+    """The greedy choice of up to k candidates that together see the most target points (occ4d_viewplan_greedy_u32, GREEDY of
+    include/ext/occ4d_viewplan.h): vis (C, W) int32 from ops.grid_visible, targets (W,) int32, k in [0, 32].  `work`: the caller's
+    contiguous int32 buffer (>= viewplan_work_len(C, W)); `out` = (gain, picks, pick_gain, status): the caller's contiguous int32
+    buffers (>= C, >= k, >= k, >= 2).  -> (gain (C,) int32: the target points each candidate sees on its own; picks (k,) int32: in
+    each round the lowest candidate that sees the most of what no earlier pick sees, -1 from the round on in which nothing is left
+    to see; pick_gain (k,) int32: what it added; status (2,) int32: the number of target points and how many of them no pick
+    sees), on the device.  1 + 2 * max(k, 1) launches, whatever the data.  No host read."""
+    v, tgt = _dev(vis, torch.int32, 'vis'), _dev(targets, torch.int32, 'targets')
+    assert v.dim() == 2 and tuple(tgt.shape) == (v.shape[1],) and v.is_contiguous() and tgt.is_contiguous(), \
+        'vis and targets must be contiguous (C, W) and (W,) tensors, got %s and %s' % (tuple(v.shape), tuple(tgt.shape))
+    C, W, k = int(v.shape[0]), int(v.shape[1]), int(k)
+    out = (None, None, None, None) if out is None else out
+    gain = _int32_out(out[0], (C,), v.device, 'out gain')
+    picks = _int32_out(out[1], (max(k, 0),), v.device, 'out picks')
+    pick_gain = _int32_out(out[2], (max(k, 0),), v.device, 'out pick_gain')
+    status = _int32_out(out[3], (2,), v.device, 'out status')
+    wk = _int32_out(work, (viewplan_work_len(C, W),), v.device, 'work')
+    if C == 0 or W == 0:
+        gain.zero_(), status.zero_(), picks.fill_(-1), pick_gain.zero_()      # (the entry point touches no pointer then)
+    _lib.check(_lib.lib().occ4d_viewplan_greedy_u32(_ptr(v), C, W, _ptr(tgt), k, _ptr(wk), _ptr(gain), _ptr(picks), _ptr(pick_gain),
+                                                    _ptr(status), _stream()))
+    return gain, picks, pick_gain, status
+
+
 def link_work_len(n, cap):
     """Elements of the int32 work array of occ4d_link_overlap_i32 for n grid points and `cap` pair rows (the formula of the
     header): 4 * slots + n + 2 * tiles with slots the smallest power of two >= max(2 * min(cap, n), MIN_SLOTS), at most 2^31."""

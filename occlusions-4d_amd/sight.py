@@ -21,7 +21,18 @@ one inside an object is hidden.  Sensors may lie outside the grid (up to 2^20 ce
 Unlike the views= ray cast followed by projection.visibility this needs no image, no pixel and no float margin, so it serves a lidar as
 well as a camera.  Everything is an integer, so every output is the same bit for bit under any scheduling.
 
-NOT MEASURED: which share of a trained model's scene is hidden.  There is no checkpoint."""
+THE NEXT BEST VIEW (include/ext/occ4d_viewplan.h).  From where should the sensor look next?  perform_inference(sight=Sight(...),
+next_view=NextView(candidates, k)) adds result['next_view'] = dict(gain (C,), picks (k,), pick_gain (k,), status (2,)), all int32:
+of the queries no current sensor sees (seen == 0), how many each candidate viewpoint would see on its own (gain), and a greedy
+choice of up to k candidates that together see the most -- picks[r] is the lowest candidate that sees the most of what picks[:r]
+leave unseen, -1 once nothing is left; status = [the unseen queries, those no pick sees].  The same walk, the same snap of a
+candidate to its cell; a candidate inside a predicted solid cell sees nothing.  plan() is the stand-alone piece.
+
+    res = perform_inference(..., sight=Sight(origins=lidar_positions), next_view=NextView(ring_of_positions, k=3, among='solid'))
+    best = res['next_view']['picks']                                # indices into ring_of_positions, -1 behind the useful ones
+
+NOT MEASURED: which share of a trained model's scene is hidden, and what a trained model's candidates gain.  There is no
+checkpoint."""
 import numpy as np
 import torch
 
@@ -29,6 +40,10 @@ from . import _lib, ops, products, projection
 
 MAX_ORIGINS = _lib.SIGHT_CONSTANTS['MAX_ORIGINS']
 MAX_COORD = _lib.SIGHT_CONSTANTS['MAX_COORD']
+MAX_CANDIDATES = _lib.VIEWPLAN_CONSTANTS['MAX_CANDIDATES']
+MAX_PICKS = _lib.VIEWPLAN_CONSTANTS['MAX_PICKS']
+MAX_WEIGHT = _lib.VIEWPLAN_CONSTANTS['MAX_WEIGHT']
+AMONG = ('all', 'solid')
 
 
 def _count(V, who):
@@ -178,3 +193,121 @@ def by_label(labels, k, seen, framed=None):
     table = torch.zeros((3 * k + 1,), dtype=torch.int64, device=seen.device)
     table.scatter_add_(0, slot, torch.ones_like(slot))
     return table[:3 * k].view(k, 3)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the next best view
+def _plan_options(k, among, max_dist2, weights, who):
+    """(k, among, max_dist2 or None, (wx, wy, wz)) checked: ValueError."""
+    try:
+        k_int = int(k)
+        weights = tuple(int(w) for w in weights)
+        max_dist2 = None if max_dist2 is None else int(max_dist2)
+    except (TypeError, ValueError) as e:
+        raise ValueError('%s: k = %r, max_dist2 = %r and weights = %r must be integers' % (who, k, max_dist2, weights)) from e
+    if k_int != k or not 0 <= k_int <= MAX_PICKS:
+        raise ValueError('%s: k = %r must be an integer in [0, %d]' % (who, k, MAX_PICKS))
+    if among not in AMONG:
+        raise ValueError("%s: among = %r must be 'all' or 'solid'" % (who, among))
+    if len(weights) != 3 or not all(1 <= w <= MAX_WEIGHT for w in weights):
+        raise ValueError('%s: weights = %r must be three integers in [1, %d]' % (who, weights, MAX_WEIGHT))
+    if max_dist2 is not None and not -2 ** 63 <= max_dist2 < 2 ** 63:
+        raise ValueError('%s: max_dist2 = %r must fit int64' % (who, max_dist2))
+    return k_int, among, max_dist2, weights
+
+
+def _candidate_count(C, who):
+    if not 1 <= C <= MAX_CANDIDATES:
+        raise ValueError('%s: C = %d candidates, must be in [1, %d]' % (who, C, MAX_CANDIDATES))
+
+
+def _candidates(candidates_ijk, who):
+    """(C, 3) int32 numpy of integer lattice candidates; ValueError unless 1 <= C <= 4096 and every coordinate is within 2^20."""
+    c = np.asarray(candidates_ijk)
+    if c.ndim != 2 or c.shape[1] != 3 or c.dtype.kind not in 'iu':
+        raise ValueError('%s: candidates must be (C, 3) integers, got %s %s' % (who, c.dtype, c.shape))
+    _candidate_count(c.shape[0], who)
+    if np.abs(c.astype(np.int64)).max() > MAX_COORD:
+        raise ValueError('%s: a candidate lies beyond 2^20 cells' % who)
+    return np.ascontiguousarray(c, dtype=np.int32)
+
+
+def cells_to_world(ijk, mins, spacings):
+    """Lattice points (..., 3) integers -> the centres of their cells, float64 world points: mins + (ijk + 0.5) * spacings, the
+    inverse of grid_origin up to the snap.  candidates_world[picks] needs no such step; this one is for candidates that were cells
+    from the start (the cells route= found reachable)."""
+    c = np.asarray(ijk)
+    if c.shape[-1:] != (3,) or c.dtype.kind not in 'iu':
+        raise ValueError('cells_to_world: ijk must be (..., 3) integers, got %s %s' % (c.dtype, c.shape))
+    return np.asarray(mins, np.float64) + (c.astype(np.float64) + 0.5) * np.asarray(spacings, np.float64)
+
+
+def plan(implicit_output, counts, seen, candidates_ijk, k=1, level=0.5, select=None, among='all', max_dist2=None, weights=(1, 1, 1),
+         channel=0, keep_vis=False):
+    """The stand-alone piece of the next best view (include/ext/occ4d_viewplan.h): implicit_output (N, G) dense on the (nx, ny, nz)
+    = `counts` grid, its solid set column `channel` >= level (select = (column, threshold): the mask column), as in look(); seen
+    (N,) int32 of look() under the current sensors: THE TARGETS ARE THE QUERIES WITH seen == 0, with among='solid' only the solid
+    ones of them (the amodally completed object parts), with among='all' free space too (exploration).  candidates_ijk: (C, 3)
+    integers on the host, 1 <= C <= 4096, within 2^20 cells (ValueError) -- or an int32 (C, 3) tensor that is on the device already,
+    taken as it is: the kernel checks its values, one out of range sees nothing.  A candidate in a solid cell sees nothing.  k in
+    [0, 32]: the picks; max_dist2 (None: no limit) and weights (wx, wy, wz): a target counts for a candidate only within
+    wx dx^2 + wy dy^2 + wz dz^2 <= max_dist2, in cells.  ops.grid_solid_bits, ops.grid_blocked_bits, ops.grid_visible,
+    ops.viewplan_greedy -> dict(gain (C,), picks (k,), pick_gain (k,), status (2,)) int32 on the device (ops.viewplan_greedy
+    describes them), with keep_vis=True also vis (C, ceil(N / 32)): bit q % 32 of word q // 32 of row c = candidate c sees target q.
+    Nothing is read back."""
+    level = float(level)
+    if level != level:
+        raise ValueError('sight.plan: level is NaN')
+    k, among, max_dist2, weights = _plan_options(k, among, max_dist2, weights, 'sight.plan')
+    values, mask, mask_level = products.columns(implicit_output, channel, _select(select, 'sight.plan'))
+    if isinstance(candidates_ijk, torch.Tensor):
+        cand = candidates_ijk
+        if cand.dim() != 2 or cand.shape[1] != 3 or cand.dtype != torch.int32:
+            raise ValueError('sight.plan: a candidates tensor must be (C, 3) int32, got %s %s' % (cand.dtype, tuple(cand.shape)))
+        _candidate_count(cand.shape[0], 'sight.plan')
+    else:
+        cand = torch.from_numpy(_candidates(candidates_ijk, 'sight.plan')).to(values.device)
+    bits = ops.grid_solid_bits(values, level, mask, mask_level)
+    targets = ops.grid_blocked_bits(seen, 1)                          # !(seen >= 1): no sensor sees the query
+    if among == 'solid':
+        targets = targets & bits
+    vis = ops.grid_visible(bits, counts, targets, cand, max_dist2, weights)
+    gain, picks, pick_gain, status = ops.viewplan_greedy(vis, targets, k)
+    out = dict(gain=gain, picks=picks, pick_gain=pick_gain, status=status)
+    if keep_vis:
+        out['vis'] = vis
+    return out
+
+
+class NextView(products.LevelProduct):
+    """The option object of perform_inference(next_view=...) / evaluate_clip(next_view=..., next_views=[]); needs `sight`
+    (ValueError): the targets are the queries that call's sensors do not see.  candidates: (C, 3) world points, 1 <= C <= 4096, the
+    viewpoints to rank; k in [0, 32]: how many to pick; among: 'all' = every unseen query counts (exploration), 'solid' = the
+    unseen solid ones (the amodally completed object parts); max_dist2, weights: the sensor's range in cells (plan()); level,
+    select: the solid set the candidates look through -- THEY SHOULD BE THE Sight OPTION'S, so that both products walk the same
+    scene; level None = the call's density_threshold.  The product: dict(gain (C,), picks (k,), pick_gain (k,), status (2,)), all
+    int32 (plan()); picks index `candidates`.  No device value is read: the arrays come home under the call's one host wait.  All
+    host work happens in prepare(), before the encode: the candidates snapped to cells of the call's grid with grid_origin (the
+    same one approximation as the sensors', at most one cell), ValueError for one beyond 2^20 cells.
+    NOT MEASURED: the gains of a trained model's scene.  There is no checkpoint."""
+    keyword, clip_list = 'next_view', ('next_views', 'one dict of gain, picks, pick_gain, status')
+    needs = ('sight', 'next_view needs sight: the targets are the queries its sensors do not see')
+
+    def __init__(self, candidates, k=1, among='all', max_dist2=None, weights=(1, 1, 1), level=None, select=None):
+        self.k, self.among, self.max_dist2, self.weights = _plan_options(k, among, max_dist2, weights, 'NextView')
+        self.level, self.select = self._level(level), _select(select, 'NextView')
+        self.candidates = np.array(candidates, np.float64)
+        if self.candidates.ndim != 2 or self.candidates.shape[1] != 3:
+            raise ValueError('NextView: candidates must be (C, 3) world points, got %s' % (self.candidates.shape,))
+        _candidate_count(self.candidates.shape[0], 'NextView')
+
+    def prepare(self, grid):
+        return self.resolve(grid.density_threshold), _candidates(grid_origin(self.candidates, grid.mins, grid.spacings), 'NextView')
+
+    def run(self, grid, prepared, made):
+        level, candidates_ijk = prepared
+        return plan(grid.output, grid.counts, made['sight']['seen'], torch.from_numpy(candidates_ijk).to(grid.device), self.k, level,
+                    self.select, self.among, self.max_dist2, self.weights)
+
+    def __repr__(self):
+        return 'NextView(C=%d, k=%d, among=%r, max_dist2=%r, weights=%r, level=%r, select=%r)' % (
+            self.candidates.shape[0], self.k, self.among, self.max_dist2, self.weights, self.level, self.select)
