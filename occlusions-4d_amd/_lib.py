@@ -49,6 +49,7 @@ ADDON_HEADERS = {
     'SIGHT': 'ext/occ4d_sight.h',               # line of sight through the solid set: seen, hidden, by what (sight.py, perform_inference(sight=...))
     'PULL': 'ext/occ4d_pull.h',                 # straight free legs: pairwise line of sight over the clearance, routes pulled into waypoints (geodesic.straight, geodesic.pull, Route(pull=True))
     'VIEWPLAN': 'ext/occ4d_viewplan.h',         # the next best view: which unseen points each candidate viewpoint reveals, a greedy set of them (sight.plan, perform_inference(next_view=...))
+    'BOXES': 'ext/occ4d_boxes.h',               # upright oriented boxes of the labelled objects: extents over a table of headings, the least rectangle (components.Boxes, perform_inference(boxes=...))
     'LINZ': 'ext/occ4d_linz.h',                 # the decoder's lin_z terms inside the trunk kernels (ops.rowlin(interp2=...), ops.resblock(addrows=...)); the opt-out bit
 }
 

@@ -11,7 +11,11 @@ connectivity 6 / 18 / 26, min_size 1 and no classes that is scipy.ndimage.label'
     objects = boxes_and_centroids(res['components']['table'], frame[1], frame[2])
 
 The table holds integers only, so it is the same bit for bit under any scheduling; world-space centroids and boxes are made from
-it on the host in float64 (boxes_and_centroids)."""
+it on the host in float64 (boxes_and_centroids).
+
+perform_inference(components=Components(), boxes=Boxes()) also adds box (K, 8) int32 and dirs (A, 4) int32 to that dict: per object
+the upright oriented box of least footprint area over a table of headings (include/ext/occ4d_boxes.h; yaw_directions,
+oriented_boxes)."""
 import numpy as np
 import torch
 
@@ -123,23 +127,139 @@ class Tracker(products.GridProduct):
         return 'Tracker(min_iou=(%d, %d))' % self.min_iou
 
 
+BOXES_OF = ('components', 'segments')
+YAW_SCALE = 2 ** 14                  # S: the integer length of a heading's unit vector along the coarser of the two axes
+
+
+def yaw_directions(spacings, n=90, span_deg=90.0):
+    """The table of headings of the yaw search (DIRECTIONS of include/ext/occ4d_boxes.h), on the host: for theta_a = a * span / n,
+    a = 0 .. n - 1, with m = max(sx, sy) and S = 2^14 the row (ax, ay, bx, by) = rint(S sx / m cos, S sy / m sin, -S sx / m sin,
+    S sy / m cos): u = ax ix + ay iy is the world coordinate along the heading in units of m / S, v the one across it, so the
+    search is exact in world space on an anisotropic grid.  A rectangle's extents repeat after 90 degrees (length and width swap),
+    hence the default span.  -> dict(table (n, 4) int32, yaw (n,) float64 radians, unit float64 = m / S)."""
+    sx, sy = float(spacings[0]), float(spacings[1])
+    n = int(n)
+    if not (sx > 0.0 and sy > 0.0 and np.isfinite(sx) and np.isfinite(sy)):
+        raise ValueError('yaw_directions: spacings = %r must be positive' % (tuple(spacings),))
+    if not 1 <= n <= _lib.BOXES_CONSTANTS['MAX_DIRS']:
+        raise ValueError('yaw_directions: n = %r must lie in [1, %d]' % (n, _lib.BOXES_CONSTANTS['MAX_DIRS']))
+    m = max(sx, sy)
+    yaw = np.deg2rad(np.arange(n, dtype=np.float64) * (float(span_deg) / n))
+    c, s = np.cos(yaw), np.sin(yaw)
+    table = np.rint(np.stack([YAW_SCALE * sx / m * c, YAW_SCALE * sy / m * s, -YAW_SCALE * sx / m * s, YAW_SCALE * sy / m * c], axis=1))
+    return dict(table=table.astype(np.int32), yaw=yaw, unit=m / YAW_SCALE)
+
+
+class Boxes(products.GridProduct):
+    """The option object of perform_inference(components=..., boxes=...) / evaluate_clip(..., boxes=...): the upright oriented box
+    of every object of the product `of` ('components' or 'segments'), by a search over n headings of a quarter turn
+    (yaw_directions over the grid's spacings) for the footprint rectangle of least area (include/ext/occ4d_boxes.h).  The product
+    joins that product's dict: box (K, 8) int32 = [a*, min u, max u, min v, max v, min iz, max iz, points], dirs (n, 4) int32,
+    with extents=True also extent (K, n, 4) int32.  K is the length of that dict's table: no host read of its own.
+    oriented_boxes(box, dirs, mins, spacings) makes centre, size and yaw of it on the host."""
+    keyword, reads_grid = 'boxes', False
+
+    def __init__(self, of='components', n=90, extents=False):
+        if of not in BOXES_OF:
+            raise ValueError("Boxes: of = %r must be 'components' or 'segments'" % (of,))
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= _lib.BOXES_CONSTANTS['MAX_DIRS']:
+            raise ValueError('Boxes: n = %r must be an integer in [1, %d]' % (n, _lib.BOXES_CONSTANTS['MAX_DIRS']))
+        self.of = self.into = of
+        self.n, self.extents = int(n), bool(extents)
+
+    @classmethod
+    def check(cls, option, given, point_sample_mode='grid'):
+        """As GridProduct.check; the product it builds on is the instance's `of` (`needs` is a class attribute)."""
+        super().check(option, given, point_sample_mode)
+        if option.of not in BOXES_OF:
+            raise ValueError("Boxes: of = %r must be 'components' or 'segments'" % (option.of,))
+        if option.of not in given:
+            raise ValueError("boxes needs %s=<a %s>: it fits a box to each of that product's objects"
+                             % (option.of, 'components.Components' if option.of == 'components' else 'watershed.Segments'))
+
+    def prepare(self, grid):
+        return yaw_directions(grid.spacings, self.n)['table']
+
+    def run(self, grid, table, made):
+        of = made[self.of]
+        dirs = torch.from_numpy(table).to(of['labels'].device)
+        extent, zr = ops.grid_box_extents(of['labels'], grid.counts, of['table'].shape[0], dirs)
+        out = dict(box=ops.boxes_choose(extent, zr, dirs), dirs=dirs)
+        if self.extents:
+            out['extent'] = extent
+        return out
+
+    def __repr__(self):
+        return 'Boxes(of=%r, n=%d, extents=%r)' % (self.of, self.n, self.extents)
+
+
+def oriented_boxes(box, dirs, mins, spacings):
+    """World-space boxes from the rows of a Boxes product, on the host in float64: box (K, 8), dirs (A, 4) made by yaw_directions
+    over the same spacings.  -> dict(centre (K, 3), size (K, 3) = length, width, height with length >= width, yaw (K,) in
+    [-pi/2, pi/2): the heading of the length, points (K,) int64, fill (K,) = points / the box's volume in cells).  Rows with
+    a* = -1 are NaN (points: what the row holds).  A point (ix, iy) lies at origin + (i + 0.5) * spacing; with e1 = (ax / sx, ay / sy) /
+    |.| and e2 = (bx / sx, by / sy) / |.| the world unit vectors of a* and unit = max(sx, sy) / 2^14 the centre is origin + 0.5 *
+    spacing + unit * (mid u * e1 + mid v * e2), the sizes are W1 * unit, W2 * unit (W of the header's CHOICE) and (max iz - min iz
+    + 1) * sz."""
+    b = np.asarray(box.cpu() if hasattr(box, 'cpu') else box).astype(np.int64)
+    d = np.asarray(dirs.cpu() if hasattr(dirs, 'cpu') else dirs).astype(np.int64)
+    assert b.ndim == 2 and b.shape[1] == _lib.BOXES_CONSTANTS['COLS'], 'box must be (K, 8), got %s' % (b.shape,)
+    assert d.ndim == 2 and d.shape[1] == 4, 'dirs must be (A, 4), got %s' % (d.shape,)
+    origin, spacing = np.asarray(mins, np.float64).reshape(3), np.asarray(spacings, np.float64).reshape(3)
+    unit = max(spacing[0], spacing[1]) / YAW_SCALE
+    K = b.shape[0]
+    ok = (b[:, 0] >= 0) & (b[:, 0] < d.shape[0])
+    row = d[np.where(ok, b[:, 0], 0)].astype(np.float64)                       # (K, 4)
+    e1 = row[:, 0:2] / spacing[None, :2]                                        # (ax, ay) = S / m * (sx cos, sy sin)
+    e2 = row[:, 2:4] / spacing[None, :2]
+    with np.errstate(invalid='ignore', divide='ignore'):
+        e1, e2 = e1 / np.linalg.norm(e1, axis=1, keepdims=True), e2 / np.linalg.norm(e2, axis=1, keepdims=True)
+    w1 = (b[:, 2] - b[:, 1] + np.abs(d[np.where(ok, b[:, 0], 0), 0:2]).sum(1)).astype(np.float64) * unit
+    w2 = (b[:, 4] - b[:, 3] + np.abs(d[np.where(ok, b[:, 0], 0), 2:4]).sum(1)).astype(np.float64) * unit
+    mid_u, mid_v = 0.5 * (b[:, 1] + b[:, 2]) * unit, 0.5 * (b[:, 3] + b[:, 4]) * unit
+    centre = np.empty((K, 3), np.float64)
+    centre[:, :2] = origin[None, :2] + 0.5 * spacing[None, :2] + mid_u[:, None] * e1 + mid_v[:, None] * e2
+    centre[:, 2] = origin[2] + (0.5 * (b[:, 5] + b[:, 6]) + 0.5) * spacing[2]
+    height = (b[:, 6] - b[:, 5] + 1).astype(np.float64) * spacing[2]
+    swap = w2 > w1                                                              # the length is the longer side
+    head = np.where(swap[:, None], e2, e1)
+    yaw = np.arctan2(head[:, 1], head[:, 0])
+    yaw = (yaw + 0.5 * np.pi) % np.pi - 0.5 * np.pi                             # a box has no front: [-pi/2, pi/2)
+    size = np.stack([np.where(swap, w2, w1), np.where(swap, w1, w2), height], axis=1)
+    cells = size.prod(axis=1) / spacing.prod()
+    with np.errstate(invalid='ignore', divide='ignore'):
+        fill = b[:, 7].astype(np.float64) / cells
+    for arr in (centre, size, yaw, fill):
+        arr[~ok] = np.nan
+    return dict(centre=centre, size=size, yaw=yaw, points=b[:, 7].copy(), fill=fill)
+
+
 def tracks(objects, mins, spacings):
     """The trajectories, on the host in float64: `objects` is the list evaluate_clip(components=..., objects=[], tracker=...)
     appended one dict(labels, table, link) per output frame to.  -> {track id: dict(frames (T,) int64, components (T,) int64: the
-    component's number in its frame, size (T,) int64, centroid (T, 3), box_min (T, 3), box_max (T, 3))}, the T frames in order."""
+    component's number in its frame, size (T,) int64, centroid (T, 3), box_min (T, 3), box_max (T, 3))}, the T frames in order.
+    When every frame dict also holds box and dirs (evaluate_clip(..., boxes=Boxes())) a trajectory carries obox_centre (T, 3),
+    obox_size (T, 3) and obox_yaw (T,) as well (oriented_boxes); differencing obox_centre over the frames gives a velocity."""
     rows = {}
+    oriented = len(objects) > 0 and all('box' in frame and 'dirs' in frame for frame in objects)
     for t, frame in enumerate(objects):
         summary = boxes_and_centroids(frame['table'], mins, spacings)
+        obox = oriented_boxes(frame['box'], frame['dirs'], mins, spacings) if oriented else None
         link = np.asarray(frame['link'])
         assert link.ndim == 2 and link.shape == (len(summary['size']), 4), 'link must be (K, 4), got %s' % (link.shape,)
         for k, track in enumerate(link[:, 0].tolist()):
-            rows.setdefault(track, []).append((t, k, summary['size'][k], summary['centroid'][k], summary['box_min'][k], summary['box_max'][k]))
+            rows.setdefault(track, []).append((t, k, summary['size'][k], summary['centroid'][k], summary['box_min'][k], summary['box_max'][k])
+                                              + ((obox['centre'][k], obox['size'][k], obox['yaw'][k]) if oriented else ()))
     out = {}
     for track, items in sorted(rows.items()):
         out[track] = dict(frames=np.array([i[0] for i in items], np.int64), components=np.array([i[1] for i in items], np.int64),
                           size=np.array([i[2] for i in items], np.int64), centroid=np.array([i[3] for i in items], np.float64).reshape(-1, 3),
                           box_min=np.array([i[4] for i in items], np.float64).reshape(-1, 3),
                           box_max=np.array([i[5] for i in items], np.float64).reshape(-1, 3))
+        if oriented:
+            out[track].update(obox_centre=np.array([i[6] for i in items], np.float64).reshape(-1, 3),
+                              obox_size=np.array([i[7] for i in items], np.float64).reshape(-1, 3),
+                              obox_yaw=np.array([i[8] for i in items], np.float64).reshape(-1))
     return out
 
 

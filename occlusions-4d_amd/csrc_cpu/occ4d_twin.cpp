@@ -40,6 +40,7 @@
 #include "ext/occ4d_sight.h"
 #include "ext/occ4d_pull.h"
 #include "ext/occ4d_viewplan.h"
+#include "ext/occ4d_boxes.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -58,6 +59,7 @@
 #include "sight_math.hpp"
 #include "pull_math.hpp"
 #include "viewplan_math.hpp"
+#include "boxes_math.hpp"
 #include "decoder_math.hpp"
 
 namespace fe = occ4d_frontend;
@@ -77,6 +79,7 @@ namespace ws = occ4d_watershed;
 namespace sm = occ4d_sight;
 namespace pm = occ4d_pull;
 namespace vm = occ4d_viewplan;
+namespace bm = occ4d_boxes;
 
 static thread_local char g_err[512] = "";
 
@@ -1125,6 +1128,46 @@ int occ4d_viewplan_greedy_u32(const uint32_t* vis, int C, int64_t W, const uint3
       left += __builtin_popcount(remaining[w]);
     }
     status[1] = left, picks[round] = best, pick_gain[round] = vm::key_count(key);
+  }
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- boxes
+// include/ext/occ4d_boxes.h: the DEAD test, the projections and the keys of csrc/boxes_math.hpp, POINTS IN ORDER, every atomic
+// minimum / maximum / add a plain one; the choice OBJECT BY OBJECT, directions in order.
+int occ4d_boxes_extents_i32(const int32_t* labels, int nx, int ny, int nz, int K, const int32_t* dirs, int A, int32_t* extent,
+                            int32_t* zr, void*) {
+  bm::ExtentArgs a; bool empty;
+  OCC4D_TRY(bm::check_extents(labels, nx, ny, nz, K, dirs, A, extent, zr, empty, a));
+  if (empty) return OCC4D_OK;
+  for (int64_t i = 0; i < (int64_t)K * A * 4; ++i) extent[i] = bm::empty_extent((int)(i & 3));
+  for (int64_t i = 0; i < (int64_t)K * 3; ++i) zr[i] = bm::empty_zr((int)(i % 3));
+  std::vector<bm::Dir> d((size_t)A);
+  for (int j = 0; j < A; ++j) d[(size_t)j] = bm::dir_at(dirs, j);
+  for (int ix = 0; ix < nx; ++ix)
+    for (int iy = 0; iy < ny; ++iy)
+      for (int iz = 0; iz < nz; ++iz) {
+        const int32_t k = labels[((int64_t)ix * ny + iy) * nz + iz];
+        if (!bm::object_of(k, K)) continue;
+        int32_t* z = zr + (int64_t)k * 3;
+        z[0] = std::min(z[0], (int32_t)iz), z[1] = std::max(z[1], (int32_t)iz), z[2] += 1;
+        for (int j = 0; j < A; ++j) {
+          if (!d[(size_t)j].live) continue;
+          int32_t* e = extent + ((int64_t)k * A + j) * 4;
+          const int32_t u = bm::along(d[(size_t)j], ix, iy), v = bm::across(d[(size_t)j], ix, iy);
+          e[0] = std::min(e[0], u), e[1] = std::max(e[1], u), e[2] = std::min(e[2], v), e[3] = std::max(e[3], v);
+        }
+      }
+  return OCC4D_OK;
+}
+int occ4d_boxes_choose_i32(const int32_t* extent, const int32_t* zr, const int32_t* dirs, int K, int A, int32_t* box, void*) {
+  bm::ChooseArgs c; bool empty;
+  OCC4D_TRY(bm::check_choose(extent, zr, dirs, K, A, box, empty, c));
+  if (empty) return OCC4D_OK;
+  for (int k = 0; k < K; ++k) {
+    bm::Key key{bm::NO_AREA, -1};
+    for (int j = 0; j < A; ++j) key = bm::better(key, bm::key_of(c, k, j));
+    bm::write_box(c, k, key);
   }
   return OCC4D_OK;
 }

@@ -2034,6 +2034,48 @@ def viewplan_greedy(vis, targets, k, work=None, out=None):
     return gain, picks, pick_gain, status
 
 
+def grid_box_extents(labels, counts, K, dirs, out=None):
+    """Per object and heading the extent of the object's footprint (occ4d_boxes_extents_i32, EXTENTS and RANGE of include/ext/
+    occ4d_boxes.h): labels (n,) int32 on the (nx, ny, nz) = `counts` grid, any values -- point p belongs to object labels[p] when
+    0 <= labels[p] < K --; dirs (A, 4) int32 ON THE DEVICE, rows (ax, ay, bx, by), any values: a row with a coefficient beyond
+    2^15 is DEAD (decided on the device).  `out` = (extent, zr): the caller's contiguous int32 buffers (>= K * A * 4, >= K * 3).
+    -> (extent (K, A, 4) int32: [min u, max u, min v, max v] of u = ax ix + ay iy, v = bx ix + by iy over the object's points,
+    [INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN] for an object without points and a DEAD row; zr (K, 3) int32: [min iz, max iz,
+    points]), on the device.  Two launches, whatever the data.  No host read."""
+    nx, ny, nz = (int(c) for c in counts)
+    n = max(nx * ny * nz, 0)
+    lab = _dev(labels, torch.int32, 'labels')
+    assert lab.dim() == 1 and lab.shape[0] == n, 'labels must be (%d,), got %s' % (n, tuple(lab.shape))
+    lab = lab if lab.is_contiguous() else lab.contiguous()
+    d = _dev(dirs, torch.int32, 'dirs')
+    assert d.dim() == 2 and d.shape[1] == 4, 'dirs must be (A, 4), got %s' % (tuple(d.shape),)
+    d = d if d.is_contiguous() else d.contiguous()
+    K, A = int(K), int(d.shape[0])
+    out = (None, None) if out is None else out
+    extent = _int32_out(out[0], (max(K, 0), A, 4), lab.device, 'out extent')
+    zr = _int32_out(out[1], (max(K, 0), 3), lab.device, 'out zr')
+    _lib.check(_lib.lib().occ4d_boxes_extents_i32(_ptr(lab), nx, ny, nz, K, _ptr(d), A, _ptr(extent), _ptr(zr), _stream()))
+    return extent, zr
+
+
+def boxes_choose(extent, zr, dirs, out=None):
+    """Per object the heading whose rectangle has the least area (occ4d_boxes_choose_i32, CHOICE of include/ext/occ4d_boxes.h):
+    extent (K, A, 4) int32, zr (K, 3) int32 of ops.grid_box_extents (or any values), dirs (A, 4) int32.  `out`: the caller's
+    contiguous int32 buffer (>= K * 8).  -> box (K, 8) int32 on the device: [a*, min u, max u, min v, max v, min iz, max iz,
+    points]; a* the lowest heading of least area (W1 * W2 with W = max - min + the width of one cell along the heading), -1 with
+    zeros for an object without points, -1 with the z range and the count kept when no heading qualifies.  One launch, no host
+    read."""
+    e, z, d = _dev(extent, torch.int32, 'extent'), _dev(zr, torch.int32, 'zr'), _dev(dirs, torch.int32, 'dirs')
+    assert d.dim() == 2 and d.shape[1] == 4, 'dirs must be (A, 4), got %s' % (tuple(d.shape),)
+    K, A = int(z.shape[0]), int(d.shape[0])
+    assert tuple(e.shape) == (K, A, 4) and tuple(z.shape) == (K, 3) and e.is_contiguous() and z.is_contiguous(), \
+        'extent and zr must be contiguous (K, %d, 4) and (K, 3) tensors, got %s and %s' % (A, tuple(e.shape), tuple(z.shape))
+    d = d if d.is_contiguous() else d.contiguous()
+    box = _int32_out(out, (K, _lib.BOXES_CONSTANTS['COLS']), e.device, 'out')
+    _lib.check(_lib.lib().occ4d_boxes_choose_i32(_ptr(e), _ptr(z), _ptr(d), K, A, _ptr(box), _stream()))
+    return box
+
+
 def link_work_len(n, cap):
     """Elements of the int32 work array of occ4d_link_overlap_i32 for n grid points and `cap` pair rows (the formula of the
     header): 4 * slots + n + 2 * tiles with slots the smallest power of two >= max(2 * min(cap, n), MIN_SLOTS), at most 2^31."""

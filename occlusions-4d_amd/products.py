@@ -1,5 +1,5 @@
-"""The grid products of perform_inference: what its options surface, views, components, tracker, clearance, segments, sight, next_view
-and route have in common.
+"""The grid products of perform_inference: what its options surface, views, components, tracker, clearance, segments, boxes (components.Boxes), sight,
+next_view and route have in common.
 Each of them turns the squashed (N, G) output of a point_sample_mode='grid' call into more device tensors, which come home under the
 call's one host wait.  An option class derives from GridProduct and says which keyword it answers to, what it needs and how it
 runs; perform_inference and evaluate_clip walk the options they are given and know nothing else about them."""
