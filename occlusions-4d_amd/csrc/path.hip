@@ -12,6 +12,7 @@
 
 #include "common.hpp"
 #include "decoder_math.hpp"
+#include "ext/occ4d_chain.h"
 #include "ext/occ4d_linz.h"
 
 namespace {
@@ -34,6 +35,7 @@ inline int row_step(int n) {
   const int passes = (n + ROW_CHUNK - 1) / ROW_CHUNK;
   return passes <= 1 || !balance ? ROW_CHUNK : ((n + passes - 1) / passes + 8) / 9 * 9;
 }
+constexpr int CHAIN_BLOCKS = 3;       // most residual blocks of one occ4d_resblock_chain_f32 launch
 constexpr int64_t ALIGN = 64;         // floats: every sub-buffer starts on a 256-byte boundary
 
 inline int64_t up(int64_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
@@ -53,6 +55,13 @@ struct Bump {
   int64_t mark() const { return off; }
   void release(int64_t m) { off = m; }
 };
+
+// OCC4D_CHAIN_TAIL=0: the cross layers' query projection as a launch of its own behind a chain of blocks (A/B; default: in
+// the chain's launch)
+inline bool chain_tail() {
+  static const bool v = [] { const char* e = getenv("OCC4D_CHAIN_TAIL"); return !e || e[0] != '0'; }();
+  return v;
+}
 
 struct Events {
   occ4d_launch_events* ev;
@@ -458,14 +467,18 @@ struct LinzTerms {
 
 // The forward of one layer / block.  dry: only the workspace is counted (no pointer is dereferenced, nothing launched).
 // lz (the caller has checked that the post Linear is the fp32 row kernel): the terms that launch takes along.
+// aq_given (cross layers on wq_rows, row_step(n) == n): the merged query projection of x, (n, 2 D), which the caller's
+// launch in front of the layer has left (the tail of occ4d_resblock_chain_f32); the layer's own projection launch and its
+// buffer are skipped (aq_is_given says so in a dry run too, where every pointer is null).
 int layer_forward(const occ4d_pt_layer_weights& w, const LayerLayout& L, const float* prep, const float* x, int64_t ldx,
                   const float* pos, int64_t ps, int n, const float* x2, int64_t ldx2, const float* pos2, int64_t p2s, int m,
                   int k, const int32_t* knn_idx, const float* scene, float* out, int64_t ldo, Bump& ws,
                   const Events& E, hipStream_t st, bool dry, float* logits_out = nullptr, float* a_out = nullptr,
-                  float* pe_out = nullptr, const LinzTerms* lz = nullptr) {
+                  float* pe_out = nullptr, const LinzTerms* lz = nullptr, bool aq_is_given = false,
+                  const float* aq_given = nullptr) {
   const int D = L.D, h = L.h;
   const int64_t mark = ws.mark();
-  const float *kt, *vt, *vtc, *aq_all = nullptr, *yfeat = x;
+  const float *kt, *vt, *vtc, *aq_all = aq_given, *yfeat = x;
   int64_t ld_y = ldx;
   if (!w.cross) {
     // self-attention: queries, keys and values all come from the (post-layer1) features
@@ -519,8 +532,8 @@ int layer_forward(const occ4d_pt_layer_weights& w, const LayerLayout& L, const f
       idx = ib;
     }
     const float* aq;
-    if (aq_all) {
-      aq = aq_all + (int64_t)lo * 2 * D;
+    if (aq_all || aq_is_given) {
+      aq = aq_all ? aq_all + (int64_t)lo * 2 * D : nullptr;
     } else {
       float* ab = ws.take((int64_t)c * 2 * D);
       if (!dry) {
@@ -799,9 +812,10 @@ int decoder_forward(const occ4d_decoder_weights& w, const DecoderLayout& L, cons
     // (DESIGN.md 6e).  On the fp32 row-resident trunk, for a cross layer j behind block b - 1 whose post Linear is the
     // fp32 row kernel: the term of block b rides in that launch (added to its output rows), and where no cross layer
     // sits behind block b, the same launch stores the term of block b + 1 as dense rows, which block b's launch adds
-    // from loads under its last chunk.  Every other term (blocks 0 and 1 of the published layouts; k_local != 8; the
-    // penult output; trunk4; the split-precision trunks; OCC4D_LINZ_PATH_STANDALONE) is the stand-alone pass in front of
-    // its block.  All three placements add the same s last onto the same row: one result, bit for bit.
+    // from loads under its last chunk.  Every other term (the leading blocks of the published layouts; k_local != 8; the
+    // penult output; trunk4; the split-precision trunks; OCC4D_LINZ_PATH_STANDALONE) is a pass in front of its block: the
+    // stand-alone one, or the joint pass in front of a chain of blocks (below), which stores the later blocks' terms as
+    // dense rows too.  All placements add the same s last onto the same row: one result, bit for bit.
     // OCC4D_PATH_FUSED_INTERP (the exposed gathers in the block's epilogue, measured neutral) is accepted and selects
     // nothing: what it moved is where the default puts it now, hidden.
     const bool linz = !(flags & OCC4D_LINZ_PATH_STANDALONE) && L.resblock && !L.trunk4 && !L.x6trunk && !penult &&
@@ -818,13 +832,69 @@ int decoder_forward(const occ4d_decoder_weights& w, const DecoderLayout& L, cons
     }
     float* dense = any_dense ? ws.take((int64_t)c * H) : nullptr;
     const int64_t ldz = (int64_t)L.nB * H;
+    // Consecutive blocks with no cross layer between them run as ONE launch (occ4d_resblock_chain_f32), at
+    // most CHAIN_BLOCKS of them, where the terms are routed at all (`linz`) and OCC4D_CHAIN_PATH_SEPARATE is not set.  The
+    // term of a chained block other than the first must arrive as dense rows: from the post Linear in front of the chain
+    // (as_dense, as before) or from one occ4d_interp_dense_f32 pass in front of it, which also adds the first block's
+    // term.  With chain_tail the cross layer's merged query projection behind the chain runs in the chain's launch too.
+    const bool chain = linz && !(flags & OCC4D_CHAIN_PATH_SEPARATE);
     int next_cross = 0;
-    for (int i = 0; i < L.nB; ++i) {
+    for (int i = 0; i < L.nB;) {
+      const auto cross_behind = [&](int b) { return next_cross < L.nC && w.cross_after[next_cross] == b; };
+      int e = i;
+      while (chain && e - i + 1 < CHAIN_BLOCKS && e + 1 < L.nB && !cross_behind(e)) ++e;
+      const int nb = e - i + 1;
+      const bool cross = cross_behind(e);
+      const int64_t cmark = ws.mark();
+      float* aq = nullptr;
+      int n_tail = 0;
+      if (chain && chain_tail() && cross) {
+        const LayerLayout& lc = L.cl[next_cross];
+        if (lc.wq_rows && !lc.x6rows && !lc.trunk4 && row_step(c) >= c) {
+          n_tail = 2 * lc.D;
+          aq = ws.take((int64_t)c * n_tail);
+        }
+      }
+      const int64_t tmark = ws.mark();           // (the dense rows of this run are released before the cross layer)
+      // which terms the pass in front of the run forms: slot 0 = the first block's (added to x), slots 1, 2 = dense rows
+      const bool first = !in_rowlin[i] && !as_dense[i];
+      const float* addp[CHAIN_BLOCKS] = {};
+      int slot_term[3] = {first ? i : -1, -1, -1};
+      float* slot_rows[3] = {first ? x : nullptr, nullptr, nullptr};
+      bool dense_free = any_dense && !as_dense[i + 1];     // (the post Linear's dense rows are consumed by the run behind it)
+      int slots = 0;
+      for (int k = i; k <= e; ++k) {
+        if (as_dense[k + 1]) { addp[k - i] = dense; continue; }
+        if (k == e) continue;
+        float* rows = dense_free ? dense : ws.take((int64_t)c * H);
+        dense_free = false;
+        ++slots;
+        slot_term[slots] = k + 1; slot_rows[slots] = rows; addp[k - i] = rows;
+      }
       if (!dry) {
-        if (!in_rowlin[i] && !as_dense[i])
-          TRY(occ4d_interp_add_f32(x, ldx, scene + S.zconst + (int64_t)i * H, scene + S.ztab + (int64_t)i * H, ldz, idx8, w8, c,
-                                   w.k_local, H, st));
-        if (L.f16block) {
+        const auto zc = [&](int t) { return t < 0 ? nullptr : scene + S.zconst + (int64_t)t * H; };
+        const auto zt = [&](int t) { return t < 0 ? nullptr : scene + S.ztab + (int64_t)t * H; };
+        if (slots)
+          TRY(occ4d_interp_dense_f32(slot_rows[0], ldx, zc(slot_term[0]), zt(slot_term[0]), zc(slot_term[1]), zt(slot_term[1]),
+                                     slot_rows[1], H, zc(slot_term[2]), zt(slot_term[2]), slot_rows[2], H, ldz, m, idx8, w8,
+                                     w.k_local, c, H, st));
+        else if (first)
+          TRY(occ4d_interp_add_f32(x, ldx, zc(i), zt(i), ldz, idx8, w8, c, w.k_local, H, st));
+        if (nb > 1 || aq) {
+          const LayerLayout* lc = aq ? &L.cl[next_cross] : nullptr;
+          const float* lprep = aq ? prep + L.cross[next_cross] : nullptr;
+          const auto blk = [&](int k, int what) -> const float* {
+            if (i + k > e) return nullptr;
+            return what == 0 ? prep + L.w0p[i + k] : what == 1 ? w.fc0_b[i + k] : what == 2 ? prep + L.w1p[i + k] : w.fc1_b[i + k];
+          };
+          E.before(OCC4D_PROFILE_RESBLOCK);
+          const int rc = occ4d_resblock_chain_f32(
+              x, ldx, x, ldx, nb, blk(0, 0), blk(0, 1), blk(0, 2), blk(0, 3), addp[0], H, blk(1, 0), blk(1, 1), blk(1, 2),
+              blk(1, 3), addp[1], H, blk(2, 0), blk(2, 1), blk(2, 2), blk(2, 3), addp[2], H, aq ? lprep + lc->wq_packed : nullptr,
+              aq ? lprep + lc->bq : nullptr, n_tail, 0, aq, n_tail, c, st);
+          E.after(OCC4D_PROFILE_RESBLOCK);
+          TRY(rc);
+        } else if (L.f16block) {
           // x = x + fc_1(relu(fc_0(relu(x)))) in place, one launch, h in registers
           E.before(OCC4D_PROFILE_RESBLOCK);
           const int rc = occ4d_resblock_f16x3_f32(x, ldx, x, ldx, prep + L.w0x[i], w.fc0_b[i], w.fc1_b[i], c, st);
@@ -842,8 +912,8 @@ int decoder_forward(const occ4d_decoder_weights& w, const DecoderLayout& L, cons
           const int rc = L.trunk4
               ? occ4d_resblock4_f32(x, ldx, x, ldx, prep + L.w0p[i], w.fc0_b[i], prep + L.w1p[i], w.fc1_b[i], nullptr,
                                     nullptr, 0, nullptr, nullptr, 0, c, st)
-              : as_dense[i + 1]     // (the next block's term, left as dense rows by the cross layer in front of this block)
-              ? occ4d_resblock_addrows_f32(x, ldx, x, ldx, prep + L.w0p[i], w.fc0_b[i], prep + L.w1p[i], w.fc1_b[i], dense, H,
+              : addp[0]             // (the next block's term, left as dense rows by the cross layer in front of this block)
+              ? occ4d_resblock_addrows_f32(x, ldx, x, ldx, prep + L.w0p[i], w.fc0_b[i], prep + L.w1p[i], w.fc1_b[i], addp[0], H,
                                            c, st)
               : occ4d_resblock_f32(x, ldx, x, ldx, prep + L.w0p[i], w.fc0_b[i], prep + L.w1p[i], w.fc1_b[i], nullptr,
                                    nullptr, 0, nullptr, nullptr, 0, c, st);
@@ -854,21 +924,24 @@ int decoder_forward(const occ4d_decoder_weights& w, const DecoderLayout& L, cons
           TRY(lin(hbuf, H, w.fc1_w[i], H, w.fc1_b[i], x, ldx, c, H, H, act, 0, x, ldx, st));
         }
       }
-      if (next_cross < L.nC && w.cross_after[next_cross] == i) {
+      ws.release(tmark);
+      if (cross) {
         const int j = next_cross++;
         LinzTerms lz{};
-        if (!dry && in_rowlin[i + 1]) {
-          lz.zconst = scene + S.zconst + (int64_t)(i + 1) * H; lz.ztab = scene + S.ztab + (int64_t)(i + 1) * H;
-          if (as_dense[i + 2]) {
-            lz.zconst2 = scene + S.zconst + (int64_t)(i + 2) * H; lz.ztab2 = scene + S.ztab + (int64_t)(i + 2) * H;
+        if (!dry && in_rowlin[e + 1]) {
+          lz.zconst = scene + S.zconst + (int64_t)(e + 1) * H; lz.ztab = scene + S.ztab + (int64_t)(e + 1) * H;
+          if (as_dense[e + 2]) {
+            lz.zconst2 = scene + S.zconst + (int64_t)(e + 2) * H; lz.ztab2 = scene + S.ztab + (int64_t)(e + 2) * H;
             lz.dense = dense; lz.ldd = H;
           }
           lz.ldz = ldz; lz.zrows = m; lz.zidx = idx8; lz.zw = w8; lz.kz = w.k_local;
         }
         TRY(layer_forward(w.cross[j], L.cl[j], prep ? prep + L.cross[j] : nullptr, x, ldx, q, qs, c, nullptr, 0, xyz, 3, m,
                           w.k_cross, idx_att, scene ? scene + S.layer[j] : nullptr, x, ldx, ws, E, st, dry, nullptr, nullptr,
-                          nullptr, !dry && in_rowlin[i + 1] ? &lz : nullptr));
+                          nullptr, !dry && in_rowlin[e + 1] ? &lz : nullptr, n_tail != 0, aq));
       }
+      ws.release(cmark);
+      i = e + 1;
     }
     if (!dry)
       TRY(lin(x, ldx, w.lin_out_w, H, w.lin_out_b, out + (int64_t)lo * ld_out, ld_out, c, H, w.d_out, act, 0, nullptr, 0, st));

@@ -3,6 +3,7 @@
 // kernel maps the fastest-varying output dimension (channel) to consecutive lanes
 // so that stores and the gathered row reads are coalesced 256-byte wave accesses.
 #include "common.hpp"
+#include "ext/occ4d_chain.h"
 
 namespace {
 
@@ -254,6 +255,50 @@ __global__ __launch_bounds__(TPB) void interp_add4_kernel(float* __restrict__ x,
   *xp = xv;
 }
 
+// Up to three terms over the same lists and weights in one pass (occ4d_interp_dense_f32, include/ext/occ4d_chain.h): the
+// lane of interp_add4_kernel<8> reads its row's 8 indices and weights once and forms, per present term (a wave-uniform
+// test of the table pointer), the sum in that kernel's order -- s = (..((0 + w0 t0) + w1 t1) + ..) + cvec -- from the
+// term's own table (the common row offsets, another base); term 0 is added to x, terms 1 and 2 are stored as dense rows.
+struct DenseTerms {
+  const float* cvec[3]; const float* table[3];
+  float* out[3]; int64_t ldo[3];                // out[0] = x (read-modify-write); out[1], out[2]: dense rows (written)
+};
+
+__global__ __launch_bounds__(TPB) void interp_dense4_kernel(const DenseTerms a, int64_t ldt, const int32_t* __restrict__ idx,
+                                                            const float* __restrict__ w, int64_t total, int d4) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  constexpr int KC = 8;
+  const int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (e >= total) return;
+  const int c = 4 * (int)(e % d4);
+  const int64_t i = e / d4;
+  unsigned off[KC];                             // (zrows ldt < 2^30, checked by the launcher)
+  float wj[KC];
+#pragma unroll
+  for (int j = 0; j < KC; ++j) { off[j] = (unsigned)idx[i * KC + j] * (unsigned)ldt + (unsigned)c; wj[j] = w[i * KC + j]; }
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+    const float* __restrict__ table = a.table[t];
+    if (!table) continue;
+    f4 tv[KC];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) tv[j] = *reinterpret_cast<const f4*>(table + off[j]);
+    f4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < KC; ++j) { s.x += wj[j] * tv[j].x; s.y += wj[j] * tv[j].y; s.z += wj[j] * tv[j].z; s.w += wj[j] * tv[j].w; }
+    const f4 cv = *reinterpret_cast<const f4*>(a.cvec[t] + c);
+    s.x += cv.x; s.y += cv.y; s.z += cv.z; s.w += cv.w;
+    f4* op = reinterpret_cast<f4*>(a.out[t] + i * a.ldo[t] + c);
+    if (t == 0) {
+      f4 xv = *op;
+      xv.x += s.x; xv.y += s.y; xv.z += s.z; xv.w += s.w;
+      *op = xv;
+    } else {
+      *op = s;
+    }
+  }
+}
+
 struct SquashOps { int32_t op[32]; };
 
 __global__ __launch_bounds__(TPB) void squash_kernel(float* __restrict__ out, int64_t ld, int64_t total, int g,
@@ -409,6 +454,38 @@ int occ4d_interp_add_f32(float* x, int64_t ldx, const float* cvec, const float* 
     interp_add_kernel<<<grid1d(total), TPB, 0, (hipStream_t)stream>>>(x, ldx, cvec, table, ldt, idx, w, total, k, d);
   }
   return occ4d::check_launch("occ4d_interp_add_f32");
+}
+
+int occ4d_interp_dense_f32(float* x, int64_t ldx, const float* zconst0, const float* ztab0, const float* zconst1,
+                           const float* ztab1, float* dense1, int64_t ldd1, const float* zconst2, const float* ztab2,
+                           float* dense2, int64_t ldd2, int64_t ldz, int zrows, const int32_t* zidx, const float* zw, int kz,
+                           int n, int d, void* stream) {
+  const char* who = "occ4d_interp_dense_f32";
+  DenseTerms a{{zconst0, zconst1, zconst2}, {ztab0, ztab1, ztab2}, {x, dense1, dense2}, {ldx, ldd1, ldd2}};
+  OCC4D_REQUIRE(ztab0 || ztab1 || ztab2, "%s: no interpolation term (every table is null)", who);
+  OCC4D_REQUIRE(zidx && zw && kz == 8, "%s: the terms take zidx / zw with kz = 8 neighbours (kz = %d: run occ4d_interp_add_f32 "
+                "per term)", who, kz);
+  OCC4D_REQUIRE(n >= 0 && d >= 4 && d % 4 == 0 && ldz >= d && ldz % 4 == 0, "%s: d = %d, ldz = %lld: multiples of 4 with "
+                "ldz >= d expected", who, d, (long long)ldz);
+  OCC4D_REQUIRE(zrows >= 1 && (int64_t)zrows * ldz < ((int64_t)1 << 30), "%s: zrows = %d table rows of stride %lld: zrows ldz "
+                "must stay below 2^30 (32-bit row offsets)", who, zrows, (long long)ldz);
+  for (int t = 0; t < 3; ++t) {
+    if (!a.table[t]) {
+      OCC4D_REQUIRE(!a.cvec[t] && !a.out[t], "%s: term %d: constant / rows given without its table", who, t);
+      continue;
+    }
+    OCC4D_REQUIRE(a.cvec[t] && a.out[t], "%s: term %d needs its constant and its rows (term 0: x)", who, t);
+    OCC4D_REQUIRE(((uintptr_t)a.table[t] % 16) == 0 && ((uintptr_t)a.cvec[t] % 16) == 0 && ((uintptr_t)a.out[t] % 16) == 0 &&
+                      a.ldo[t] % 4 == 0 && a.ldo[t] >= d,
+                  "%s: term %d: table, constant and rows must be 16-byte aligned, the row stride a multiple of 4 >= d", who, t);
+    for (int u = 0; u < t; ++u)
+      OCC4D_REQUIRE(!occ4d::rows_overlap(a.out[t], a.ldo[t], a.out[u], a.ldo[u], n, d),
+                    "%s: the rows of terms %d and %d must not alias", who, u, t);
+  }
+  const int64_t total4 = (int64_t)n * (d / 4);
+  if (!total4) return OCC4D_OK;
+  interp_dense4_kernel<<<grid1d(total4), TPB, 0, (hipStream_t)stream>>>(a, ldz, zidx, zw, total4, d / 4);
+  return occ4d::check_launch(who);
 }
 
 int occ4d_squash_f32(float* out, int64_t ld, int n, int g, const int32_t* ops_host, void* stream) {

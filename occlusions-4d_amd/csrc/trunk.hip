@@ -24,6 +24,7 @@
 // s_waitcnt vmcnt(0) + barrier per stage ("my part of the next stage has landed" + "everybody's has").
 #include <type_traits>
 
+#include "ext/occ4d_chain.h"
 #include "ext/occ4d_linz.h"
 #include "tile.hpp"
 
@@ -385,6 +386,180 @@ __global__ __launch_bounds__(512, 2) void rowlin_kernel(const TrunkArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Up to CHAIN_MAX residual blocks over the same rows in one launch, then optionally a rowlin (include/ext/occ4d_chain.h):
+// the rows stay in registers from the first block's load to the last block's store, so a block -> block boundary costs
+// neither the store / reload of x nor the single-round memory phases that go with them.  chunk() is the body of
+// resblock_kernel (without its ablation switches), kept apart so that kernel's code stays what it is; it takes the two
+// weight streams as arguments: "prefetch stage j + 1" of a block's last chunk takes stage 0 of the NEXT stream -- the next
+// block's W0, the tail's W, or this block's own extra stage -- a wave-uniform select.  At a boundary the work is what the
+// store, the launch and the load did: yacc (+= the dense rows) is x, relu(x) the next operand, x + b1 the next accumulator;
+// the biases of the blocks behind the first wait in LDS from the prologue on.
+constexpr int CHAIN_MAX = 3;
+
+struct ChainBlock {
+  const float* w0p; const float* b0; const float* w1p; const float* b1;
+  const float* addrows; int64_t lda;         // dense rows added to this block's output rows, or null
+};
+
+struct ChainArgs {
+  const float* x; int64_t ldx;
+  float* y; int64_t ldy;
+  int n, nb;
+  ChainBlock blk[CHAIN_MAX];
+  TrunkArgs tail;                            // rowlin behind the last block (y, ldy, w0p, b0, n, n_stages, relu_in); w0p null: none
+};
+
+template <bool TAIL>
+__global__ __launch_bounds__(512, 2) void resblock_chain_kernel(const ChainArgs a) {
+  __shared__ __attribute__((aligned(16))) float bufA[STAGE_FLOATS];
+  __shared__ __attribute__((aligned(16))) float bufB[STAGE_FLOATS];
+  __shared__ __attribute__((aligned(16))) float s_b0[TH];                     // b0 of the current block
+  __shared__ __attribute__((aligned(16))) float s_bn[CHAIN_MAX - 1][2][TH];   // b0, b1 of the blocks behind the first
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int row = blockIdx.x * TROWS + wave * 16 + r;
+  const int rowc = min(row, a.n - 1);
+
+  dma_stage(a.blk[0].w0p, bufA, wave, lane);
+  if (tid < TH) {
+    s_b0[tid] = a.blk[0].b0[tid];
+#pragma unroll
+    for (int i = 1; i < CHAIN_MAX; ++i)
+      if (i < a.nb) { s_bn[i - 1][0][tid] = a.blk[i].b0[tid]; s_bn[i - 1][1][tid] = a.blk[i].b1[tid]; }
+  }
+  f32x4 xr[TKG], yacc[TKG];
+  {
+    const float* xp = a.x + (int64_t)rowc * a.ldx + 4 * g;
+    const float* bp = a.blk[0].b1 + 4 * g;
+#pragma unroll
+    for (int t = 0; t < TKG; ++t) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(xp + 16 * t);
+      const f32x4 b = *reinterpret_cast<const f32x4*>(bp + 16 * t);
+      xr[t] = relu4(v);
+      yacc[t].x = v.x + b.x; yacc[t].y = v.y + b.y; yacc[t].z = v.z + b.z; yacc[t].w = v.w + b.w;
+    }
+  }
+  dma_wait();
+  __syncthreads();
+  const float* const fa = bufA + lane * 4;
+  const float* const fb = bufB + lane * 4;
+
+  // one hidden chunk j of the current block: w1s = its W1 stage, w0n = the W0 stage that lands in bufA meanwhile.
+  // LAST (the block's last chunk): where the block has dense rows (`add`, wave-uniform), their loads under this chunk's
+  // MFMAs in the slots of resblock_kernel<true>, each behind a scalar branch -- ONE body for both kinds of block: two
+  // bodies behind one branch made the register allocator split the accumulators around them
+  auto chunk = [&](const int j, const float* __restrict__ w1s, const float* __restrict__ w0n, const float* add, const int lda,
+                   auto last_chunk) __attribute__((always_inline)) {
+    constexpr bool LAST = decltype(last_chunk)::value;
+    int arow = row;
+    if (LAST) asm volatile("" : "+v"(arow));
+    const float* const ap = LAST ? add + (unsigned)(min(arow, a.n - 1) * lda + 4 * g) : nullptr;
+    f32x4 h0 = *reinterpret_cast<const f32x4*>(s_b0 + 32 * j + 4 * g);
+    f32x4 h1 = *reinterpret_cast<const f32x4*>(s_b0 + 32 * j + 16 + 4 * g);
+    {
+      f32x4 wa = *reinterpret_cast<const f32x4*>(fa);
+      f32x4 wb = *reinterpret_cast<const f32x4*>(fa + TKG * FRAG_FLOATS);
+#pragma unroll
+      for (int t = 0; t < TKG; ++t) {
+        if (t >= 2 && t <= 20 && (t - 2) % 3 == 0) dma_part(w1s, bufB, wave, lane, (t - 2) / 3);
+        const f32x4 ca = wa, cb = wb;
+        if (t + 1 < TKG) {
+          wa = *reinterpret_cast<const f32x4*>(fa + (t + 1) * FRAG_FLOATS);
+          wb = *reinterpret_cast<const f32x4*>(fa + (TKG + t + 1) * FRAG_FLOATS);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        mfma16x2_b(ca, cb, xr[t], h0, h1);
+        __builtin_amdgcn_sched_barrier(0);
+        if (LAST && (t & 1) && t <= 21 && add) xr[(t - 1) / 2] = *reinterpret_cast<const f32x4*>(ap + 16 * ((t - 1) / 2));
+      }
+    }
+    h0 = relu4(h0);
+    h1 = relu4(h1);
+    dma_wait();
+    __syncthreads();
+    {
+      f32x4 wa = *reinterpret_cast<const f32x4*>(fb);
+      f32x4 wb = *reinterpret_cast<const f32x4*>(fb + 2 * FRAG_FLOATS);
+#pragma unroll
+      for (int q = 0; q < TKG; ++q) {
+        const int p = q >> 1, tt = q & 1;
+        if (q >= 2 && q <= 20 && (q - 2) % 3 == 0) dma_part(w0n, bufA, wave, lane, (q - 2) / 3);
+        if (LAST && q < TKG - 11 && add) xr[11 + q] = *reinterpret_cast<const f32x4*>(ap + 16 * (11 + q));
+        const f32x4 ca = wa, cb = wb;
+        if (q + 1 < TKG) {
+          const int pn = (q + 1) >> 1, tn = (q + 1) & 1;
+          wa = *reinterpret_cast<const f32x4*>(fb + (4 * pn + tn) * FRAG_FLOATS);
+          wb = *reinterpret_cast<const f32x4*>(fb + (4 * pn + 2 + tn) * FRAG_FLOATS);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        mfma16x2_b(ca, cb, tt ? h1 : h0, yacc[2 * p], yacc[2 * p + 1]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    dma_wait();
+    __syncthreads();
+  };
+
+#pragma clang loop unroll(disable)
+  for (int bi = 0; bi < a.nb; ++bi) {
+    // (wave-uniform, as everything that steers this loop.  The block's arguments are read from the kernel arguments where
+    // they are used -- the empty asm keeps the reads of the last chunk's out of the loop over the first twelve, which has
+    // no scalar register to spare)
+    {
+      const float* const w0 = a.blk[bi].w0p;
+      const float* const w1 = a.blk[bi].w1p;
+#pragma clang loop unroll(disable)
+      for (int j = 0; j < TNS - 1; ++j)
+        chunk(j, w1 + (int64_t)j * STAGE_FLOATS, w0 + (int64_t)(j + 1) * STAGE_FLOATS, nullptr, 0, std::false_type{});
+    }
+    int bl = bi;
+    asm volatile("" : "+s"(bl));
+    const bool lastb = bl + 1 == a.nb;
+    const float* const w0n = !lastb ? a.blk[bl + 1].w0p : TAIL ? a.tail.w0p : a.blk[bl].w0p + (int64_t)TNS * STAGE_FLOATS;
+    const float* const add = a.blk[bl].addrows;
+    chunk(TNS - 1, a.blk[bl].w1p + (int64_t)(TNS - 1) * STAGE_FLOATS, w0n, add, (int)a.blk[bl].lda, std::true_type{});
+    if (add) {
+#pragma unroll
+      for (int t = 0; t < TKG; ++t) { yacc[t].x += xr[t].x; yacc[t].y += xr[t].y; yacc[t].z += xr[t].z; yacc[t].w += xr[t].w; }
+    }
+    if (!lastb) {
+      // the boundary: yacc is x.  Every wave is past the chunk's last barrier, so past its last read of s_b0
+      if (tid < TH) s_b0[tid] = s_bn[bl][0][tid];
+      const float* const bp = &s_bn[bl][1][4 * g];
+#pragma unroll
+      for (int t = 0; t < TKG; ++t) {
+        const f32x4 b = *reinterpret_cast<const f32x4*>(bp + 16 * t);
+        xr[t] = relu4(yacc[t]);
+        yacc[t].x += b.x; yacc[t].y += b.y; yacc[t].z += b.z; yacc[t].w += b.w;
+      }
+      __syncthreads();
+    }
+  }
+  if (row < a.n) {
+    float* yp = a.y + (int64_t)row * a.ldy + 4 * g;
+#pragma unroll
+    for (int t = 0; t < TKG; ++t) *reinterpret_cast<f32x4*>(yp + 16 * t) = yacc[t];
+  }
+  if (TAIL) {
+    // the stage loop of rowlin_kernel<false, false> on the rows in registers; stage 0 landed in bufA under the last chunk
+#pragma unroll
+    for (int t = 0; t < TKG; ++t) xr[t] = a.tail.relu_in ? relu4(yacc[t]) : yacc[t];
+#pragma clang loop unroll(disable)
+    for (int s = 0; s < a.tail.n_stages; s += 2) {
+      rowlin_stage<false, false>(a.tail, s, bufA + lane * 4, xr, row, rowc, g, a.tail.w0p + (int64_t)(s + 1) * STAGE_FLOATS, bufB,
+                                 wave, lane, nullptr, nullptr);
+      dma_wait();
+      __syncthreads();
+      if (s + 1 < a.tail.n_stages)
+        rowlin_stage<false, false>(a.tail, s + 1, bufB + lane * 4, xr, row, rowc, g, a.tail.w0p + (int64_t)(s + 2) * STAGE_FLOATS,
+                                   bufA, wave, lane, nullptr, nullptr);
+      dma_wait();
+      __syncthreads();
+    }
+  }
+}
+
 // Host side of the rowlin entry points: the argument checks (`masked`: a mask is required) and the launch.  The terms of
 // `a` (ztab: added; ztab2: stored to a.dense) run inside the stages: kz == 8 and 32-bit table offsets, which
 // occ4d_rowlin_linz_f32 checks (occ4d_rowlin_f32 never passes a term down here).
@@ -405,6 +580,14 @@ TrunkArgs rowlin_args(const float* x, int64_t ldx, float* y, int64_t ldy, const 
   a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.w0p = w_packed; a.b0 = b; a.res = res; a.ldr = ldr;
   a.n = n; a.n_stages = n_out / 32; a.relu_in = relu_in; a.mask = mask; a.ldm = ldm;
   return a;
+}
+
+// occ4d::rows_overlap for two row sets of different widths
+bool spans_overlap(const float* p, int64_t ldp, int dp, const float* q, int64_t ldq, int dq, int n) {
+  if (!p || !q || n <= 0) return false;
+  const uintptr_t p0 = (uintptr_t)p, p1 = (uintptr_t)(p + (int64_t)(n - 1) * ldp + dp);
+  const uintptr_t q0 = (uintptr_t)q, q1 = (uintptr_t)(q + (int64_t)(n - 1) * ldq + dq);
+  return p0 < q1 && q0 < p1;
 }
 
 }  // namespace
@@ -445,6 +628,51 @@ extern "C" int occ4d_resblock_addrows_f32(const float* x, int64_t ldx, float* y,
                 "%s: second layer weights / bias missing or misaligned", who);
   if (int rc = occ4d::check_addrows_args(a, who, TH)) return rc;
   resblock_kernel<true><<<occ4d::cdiv(n, TROWS), 512, 0, (hipStream_t)stream>>>(a);
+  return occ4d::check_launch(who);
+}
+
+// nb residual blocks over the same rows in one launch, the rows in registers between them, optionally the rowlin behind the
+// last one (include/ext/occ4d_chain.h)
+extern "C" int occ4d_resblock_chain_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int nb,
+                                        const float* w0_0, const float* b0_0, const float* w1_0, const float* b1_0,
+                                        const float* add_0, int64_t lda_0, const float* w0_1, const float* b0_1,
+                                        const float* w1_1, const float* b1_1, const float* add_1, int64_t lda_1,
+                                        const float* w0_2, const float* b0_2, const float* w1_2, const float* b1_2,
+                                        const float* add_2, int64_t lda_2, const float* w_tail, const float* b_tail,
+                                        int n_tail, int relu_in_tail, float* y_tail, int64_t ld_tail, int n, void* stream) {
+  const char* who = "occ4d_resblock_chain_f32";
+  OCC4D_REQUIRE(nb >= 1 && nb <= CHAIN_MAX, "%s: nb = %d blocks (1 .. %d: split a longer run)", who, nb, CHAIN_MAX);
+  if (n == 0) return OCC4D_OK;               // (an empty batch has no storage: nothing to check)
+  ChainArgs c{};
+  c.x = x; c.ldx = ldx; c.y = y; c.ldy = ldy; c.n = n; c.nb = nb;
+  const ChainBlock given[CHAIN_MAX] = {{w0_0, b0_0, w1_0, b1_0, add_0, lda_0}, {w0_1, b0_1, w1_1, b1_1, add_1, lda_1},
+                                       {w0_2, b0_2, w1_2, b1_2, add_2, lda_2}};
+  const bool tail = w_tail != nullptr;
+  for (int i = 0; i < nb; ++i) {
+    const ChainBlock& k = c.blk[i] = given[i];
+    TrunkArgs a{};                           // the block as a launch of its own: the same checks, the same messages
+    a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.w0p = k.w0p; a.b0 = k.b0; a.w1p = k.w1p; a.b1 = k.b1;
+    a.addrows = k.addrows; a.lda = k.lda; a.n = n;
+    if (int rc = occ4d::check_trunk_args(a, who, TH)) return rc;
+    OCC4D_REQUIRE(k.w1p && k.b1 && ((uintptr_t)k.w1p % 16) == 0 && ((uintptr_t)k.b1 % 16) == 0 && ldy >= TH,
+                  "%s: second layer weights / bias missing or misaligned (block %d)", who, i);
+    if (k.addrows) {
+      if (int rc = occ4d::check_addrows_args(a, who, TH)) return rc;
+      OCC4D_REQUIRE(!tail || !spans_overlap(k.addrows, k.lda, TH, y_tail, ld_tail, n_tail, n),
+                    "%s: addrows must not alias y_tail (block %d)", who, i);
+    }
+  }
+  if (!tail) {
+    OCC4D_REQUIRE(!b_tail && !y_tail, "%s: b_tail / y_tail given without w_tail", who);
+    resblock_chain_kernel<false><<<occ4d::cdiv(n, TROWS), 512, 0, (hipStream_t)stream>>>(c);
+    return occ4d::check_launch(who);
+  }
+  c.tail = rowlin_args(y, ldy, y_tail, ld_tail, w_tail, b_tail, n_tail, relu_in_tail, nullptr, 0, nullptr, 0, n);
+  OCC4D_REQUIRE(n_tail >= 32 && n_tail % 32 == 0, "%s: n_tail = %d must be a multiple of 32", who, n_tail);
+  if (int rc = occ4d::check_rowlin_args(c.tail, who, TH, 32, n_tail, false)) return rc;
+  OCC4D_REQUIRE(!spans_overlap(y_tail, ld_tail, n_tail, x, ldx, TH, n) && !spans_overlap(y_tail, ld_tail, n_tail, y, ldy, TH, n),
+                "%s: y_tail must not alias x or y", who);
+  resblock_chain_kernel<true><<<occ4d::cdiv(n, TROWS), 512, 0, (hipStream_t)stream>>>(c);
   return occ4d::check_launch(who);
 }
 

@@ -48,6 +48,9 @@ class Selection:
     linz_shadow: bool = True          # the decoder's lin_z terms inside the trunk kernels, under their MFMAs (the post
                                       # Linear of a cross layer adds the next block's term and stores the one after as dense rows,
                                       # which the block between adds); False: six stand-alone passes (OCC4D_LINZ_PATH_STANDALONE, A/B)
+    trunk_chain: bool = True          # consecutive residual blocks of the decoder (no cross layer between them) as one launch, the rows
+                                      # in registers between them, their leading lin_z terms in one pass (where
+                                      # linz_shadow routes the terms); False: a launch per block (OCC4D_CHAIN_PATH_SEPARATE, A/B)
     logit_precision: str = 'f32'      # the d = 416 attention layers' GEMMs
     trunk_precision: str = 'f32'      # the decoder's 416-input Linear layers (residual blocks, query projection, layer3)
     train_precision: str = 'f32'      # training path: forward Linears, data gradients, pair-tensor recompute ('f32' | 'bf16x6')
@@ -92,6 +95,8 @@ class Selection:
             f |= L.PATH_FUSED_INTERP
         if not self.linz_shadow:
             f |= L.LINZ_CONSTANTS['PATH_STANDALONE']
+        if not self.trunk_chain:
+            f |= L.CHAIN_CONSTANTS['PATH_SEPARATE']
         return f
 
     def replace(self, **kw):
@@ -116,6 +121,7 @@ def _from_environment():
         trunk4=_env_flag('OCC4D_TRUNK4', '0'),
         fused_interp=_env_flag('OCC4D_FUSED_INTERP', '0'),
         linz_shadow=_env_flag('OCC4D_LINZ_SHADOW', '1'),
+        trunk_chain=_env_flag('OCC4D_TRUNK_CHAIN', '1'),
         logit_precision=os.environ.get('OCC4D_LOGIT_PRECISION', 'f32'),
         trunk_precision=os.environ.get('OCC4D_TRUNK_PRECISION', 'f32'),
         train_precision=os.environ.get('OCC4D_TRAIN_PRECISION', 'f32'),

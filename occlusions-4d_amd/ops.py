@@ -913,6 +913,68 @@ def rowlin_linz(x, w_packed, b, n_out, idx, w, term=None, term2=None, relu_in=Fa
     return o, dd
 
 
+def resblock_chain(x, blocks, out=None, tail=None):
+    """occ4d_resblock_chain_f32 (include/ext/occ4d_chain.h): 1 to 3 residual blocks over the same rows in one launch.
+    blocks: (w0_packed, b0, w1_packed, b1, addrows or None) each; tail: None or (w_packed, b, n_out, relu_in), the "rows"-
+    packed Linear applied to the final rows in the same launch.  Returns out, or (out, tail_out) with a tail."""
+    xx, ldx = _rows(_dev(x, name='x'), 'x')
+    n, d = xx.shape
+    assert d == TRUNK_WIDTH
+    o, ldo = _out(out, (n, d), x.device)
+    args = []
+    for blk in list(blocks)[:3]:
+        w0p, b0, w1p, b1, add = blk
+        aa, lda = (None, 0)
+        if add is not None:
+            aa, lda = _rows(_dev(add, name='addrows'), 'addrows')
+            assert aa.shape == (n, d)
+        args += [_ptr(w0p), _ptr(_dev(b0).contiguous()), _ptr(w1p), _ptr(_dev(b1).contiguous()), _ptr(aa), lda]
+    args += [_ptr(None), _ptr(None), _ptr(None), _ptr(None), _ptr(None), 0] * (3 - len(args) // 6)
+    t_out, targs = None, [_ptr(None), _ptr(None), 0, 0, _ptr(None), 0]
+    if tail is not None:
+        wt, bt, n_out, relu_in = tail
+        t_out, ldt = _out(None, (n, n_out), x.device)
+        targs = [_ptr(wt), _ptr(_dev(bt).contiguous()), n_out, int(relu_in), _ptr(t_out), ldt]
+    nb = len(blocks)
+    _lib.check(_launch('resblock', dict(n=n), 4.0 * n * d * d * nb, lambda: _lib.lib().occ4d_resblock_chain_f32(
+        _ptr(xx), ldx, _ptr(o), ldo, nb, *args, *targs, n, _stream())))
+    return o if tail is None else (o, t_out)
+
+
+def interp_dense(x, terms, idx, w, dense=None):
+    """occ4d_interp_dense_f32 (include/ext/occ4d_chain.h): terms = up to three (zconst, ztab) pairs or None over the lists idx
+    (n, 8) and weights w; the first is added to x in place (x may be None without it), the others are returned as dense
+    rows (None where absent): (x, dense1, dense2).  `dense`: optional (dense1, dense2) output tensors."""
+    idx = _dev(idx, torch.int32, 'idx')
+    w = _dev(w, name='w')
+    n, k = idx.shape
+    assert idx.is_contiguous() and w.is_contiguous() and w.shape == (n, k)
+    terms = list(terms) + [None] * (3 - len(terms))
+    keep, ptrs, ldz, zrows, d = [], [], 0, 0, 0
+    for t in terms:
+        if t is None:
+            ptrs.append((None, None))
+            continue
+        zc = _dev(t[0]).contiguous()
+        zt, ld = _rows(_dev(t[1], name='ztab'), 'ztab')
+        assert ldz in (0, ld) and d in (0, zt.shape[1]) and zc.numel() == zt.shape[1], 'interp_dense: one row stride and width for all tables'
+        ldz, zrows, d = ld, zt.shape[0], zt.shape[1]
+        keep += [zc, zt]
+        ptrs.append((_ptr(zc), _ptr(zt)))
+    xx, ldx = (None, 0)
+    if x is not None:
+        xx, ldx = _rows(_dev(x, name='x'), 'x')
+        assert xx is x and x.shape == (n, d)
+    outs = []
+    for i in (1, 2):
+        given = dense[i - 1] if dense is not None else None
+        outs.append(_out(given, (n, d), idx.device) if terms[i] is not None or given is not None else (None, 0))
+    _lib.check(_lib.lib().occ4d_interp_dense_f32(
+        _ptr(xx), ldx, ptrs[0][0], ptrs[0][1], ptrs[1][0], ptrs[1][1], _ptr(outs[0][0]), outs[0][1], ptrs[2][0], ptrs[2][1],
+        _ptr(outs[1][0]), outs[1][1], ldz, zrows, _ptr(idx), _ptr(w), k, n, d, _stream()))
+    return x, outs[0][0], outs[1][0]
+
+
 # --------------------------------------------------------------------------------------
 # Path-level entry points (include/occ4d.h, last section; csrc/path.hip): one call = the launch sequence of one
 # reference forward.  The nn.Module mirrors build the weight structs from their parameters (reference layout) and call

@@ -36,9 +36,11 @@ def main():
     extra = os.environ.get('OCC4D_ABLATE_EXTRA', '').split()
     for name in names:
         out = '/tmp/trunk_%s.so' % name
-        subprocess.run(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared',
-                        '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC] + VARIANTS[name] + extra +
-                       [os.path.join(CSRC, 'trunk.hip'), os.path.join(CSRC, 'error.hip'), '-o', out], check=True)
+        # (pointops.hip: trunk.hip's entry points call occ4d_interp_add_f32; -fno-honor-nans: build.py's flag for trunk.hip)
+        subprocess.run(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fno-honor-nans', '-fPIC',
+                        '-shared', '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC] + VARIANTS[name] + extra +
+                       [os.path.join(CSRC, 'trunk.hip'), os.path.join(CSRC, 'error.hip'), os.path.join(CSRC, 'pointops.hip'),
+                        '-o', out], check=True)
         lib = C.CDLL(out)
         fn = lib.occ4d_resblock_f32
         fn.restype = C.c_int
