@@ -18,7 +18,7 @@ from . import point_transformer_layer, modules, model, geometry, implicit, infer
 from . import evaluation  # noqa: F401
 from . import occlusion  # noqa: F401   (valo ids, live occlusion fractions, track id: the id histogram)
 from . import frontend  # noqa: F401   (frames -> clouds on the device: greater_clip / carla_clip)
-from . import projection  # noqa: F401   (clouds -> camera views: projection, z-buffer, visibility codes)
+from . import projection  # noqa: F401   (clouds -> camera views: projection, z-buffer, visibility codes; the decoded field ray-cast: FieldViews; the labelled objects as depth layers: ObjectLayers, object_layers, amodal_mask, visible_mask, occlusion_rate, occlusion_pairs)
 from . import components  # noqa: F401   (connected components of the decoded occupancy: Components, label, boxes_and_centroids; linked across frames: Tracker, tracks; oriented boxes: Boxes, yaw_directions, oriented_boxes)
 from . import distance  # noqa: F401   (the distance transform of the decoded occupancy: Clearance, transform, metric, signed, expand_labels)
 from . import geodesic  # noqa: F401   (shortest free-space paths over the clearance: Route, solve, grid_index, metric, paths_to_world; pulled straight into waypoints: straight, pull, polyline_length)

@@ -51,6 +51,7 @@ ADDON_HEADERS = {
     'VIEWPLAN': 'ext/occ4d_viewplan.h',         # the next best view: which unseen points each candidate viewpoint reveals, a greedy set of them (sight.plan, perform_inference(next_view=...))
     'BOXES': 'ext/occ4d_boxes.h',               # upright oriented boxes of the labelled objects: extents over a table of headings, the least rectangle (components.Boxes, perform_inference(boxes=...))
     'LINZ': 'ext/occ4d_linz.h',                 # the decoder's lin_z terms inside the trunk kernels (ops.rowlin(interp2=...), ops.resblock(addrows=...)); the opt-out bit
+    'LAYERS': 'ext/occ4d_layers.h',             # the labelled objects as depth layers in camera views: amodal and visible masks, occlusion order (projection.ObjectLayers, perform_inference(layers=...))
     'CHAIN': 'ext/occ4d_chain.h',               # consecutive residual blocks of the decoder trunk as one launch, their lin_z terms in one pass (ops.resblock_chain, ops.interp_dense); the opt-out bit
 }
 

@@ -41,6 +41,7 @@
 #include "ext/occ4d_pull.h"
 #include "ext/occ4d_viewplan.h"
 #include "ext/occ4d_boxes.h"
+#include "ext/occ4d_layers.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -60,6 +61,7 @@
 #include "pull_math.hpp"
 #include "viewplan_math.hpp"
 #include "boxes_math.hpp"
+#include "layers_math.hpp"
 #include "decoder_math.hpp"
 
 namespace fe = occ4d_frontend;
@@ -80,6 +82,7 @@ namespace sm = occ4d_sight;
 namespace pm = occ4d_pull;
 namespace vm = occ4d_viewplan;
 namespace bm = occ4d_boxes;
+namespace lm = occ4d_layers;
 
 static thread_local char g_err[512] = "";
 
@@ -1169,6 +1172,40 @@ int occ4d_boxes_choose_i32(const int32_t* extent, const int32_t* zr, const int32
     for (int j = 0; j < A; ++j) key = bm::better(key, bm::key_of(c, k, j));
     bm::write_box(c, k, key);
   }
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- layers
+// include/ext/occ4d_layers.h: the march and the rows of csrc/layers_math.hpp, PIXELS IN ORDER, every atomic add / minimum / maximum
+// of csrc/layers.hip a plain one.
+int occ4d_layers_march_i32(const int32_t* labels, int nx, int ny, int nz, int K, float x0, float sx, float y0, float sy, float z0,
+                           float sz, const float* k_inv, const float* rt_inv, int V, int H, int W, float near_depth, float step,
+                           int n_steps, int L, int32_t* label, int32_t* first, int32_t* samples, int32_t* point, int32_t* count,
+                           int32_t* table, int32_t* status, void*) {
+  lm::Args a; bool empty;
+  OCC4D_TRY(lm::check_layers(labels, nx, ny, nz, K, x0, sx, y0, sy, z0, sz, k_inv, rt_inv, V, H, W, near_depth, step, n_steps, L, label,
+                             first, samples, point, count, table, status, empty, a));
+  if (empty) return OCC4D_OK;
+  if (a.table)
+    for (int64_t i = 0; i < (int64_t)V * K * lm::COLS; ++i) a.table[i] = lm::fill_value((int)(i % lm::COLS));
+  if (a.status) a.status[0] = a.status[1] = 0;
+  for (int v = 0; v < V; ++v)
+    for (int py = 0; py < H; ++py)
+      for (int px = 0; px < W; ++px) {
+        lm::Layers s;
+        lm::march(a, v, px, py, s);
+        lm::write_pixel(a, ((int64_t)v * H + py) * W + px, s);
+        if (a.status) a.status[0] += s.count == L + 1, a.status[1] += s.count >= 1;
+        if (!a.table) continue;
+        for (int j = 0; j < L; ++j) {
+          if (s.label[j] < 0) continue;
+          int32_t* row = a.table + ((int64_t)v * K + s.label[j]) * lm::COLS;              // (0 <= label < K: owner_of's test)
+          row[OCC4D_LAYERS_AMODAL] += 1, row[OCC4D_LAYERS_VISIBLE] += j == 0;
+          row[OCC4D_LAYERS_NEAR] = std::min(row[OCC4D_LAYERS_NEAR], s.first[j]);
+          row[OCC4D_LAYERS_XMIN] = std::min(row[OCC4D_LAYERS_XMIN], (int32_t)px), row[OCC4D_LAYERS_XMAX] = std::max(row[OCC4D_LAYERS_XMAX], (int32_t)px);
+          row[OCC4D_LAYERS_YMIN] = std::min(row[OCC4D_LAYERS_YMIN], (int32_t)py), row[OCC4D_LAYERS_YMAX] = std::max(row[OCC4D_LAYERS_YMAX], (int32_t)py);
+        }
+      }
   return OCC4D_OK;
 }
 

@@ -333,7 +333,7 @@ def occlusion_groups(live_occl_row, valo_ids_pad, num_valo_ids, n_ids, edges=(0.
 def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt=False, reuse_encode=True, stats=None,
                   stats_group_fn=None, stats_occlusion=None, inst_stats=None, inst_group_fn=None, refine=None, surface=None,
                   meshes=None, views=None, images=None, components=None, objects=None, tracker=None, clearance=None,
-                  clearances=None, boxes=None, next_view=None, next_views=None, sight=None, sights=None, segments=None, parts=None, route=None, routes=None):
+                  clearances=None, layers=None, layer_images=None, boxes=None, next_view=None, next_views=None, sight=None, sights=None, segments=None, parts=None, route=None, routes=None):
     """batch: dict with 'pcl_input' (1,N,8), 'pcl_input_sem' (1,N,1-3), 'pcl_target' list of (1,T,9-11) tensors and
     batch['meta_data']['pcl_target_size'] (list of (1,) tensors), as the reference's test data loader yields them
     (data/data_greater.py:593-606, data/data_carla.py:651-661).  args: namespace with the test_args fields used
@@ -358,9 +358,14 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
     boxes: a components.Boxes, or None (needs the product its `of` names, `components` or `segments`): handed to every
     perform_inference call, so that every dict of `objects` (or `parts`) gains 'box' (K, 8) and 'dirs' (A, 4), the upright
     oriented box of every object; it takes no list of its own, as `tracker`.  components.tracks then also gives obox_centre,
-    obox_size and obox_yaw per trajectory."""
+    obox_size and obox_yaw per trajectory.
+    layers / layer_images: a projection.ObjectLayers, or None (needs the product its `of` names, `components` or `segments`), and
+    the list every output frame's result['layers'] dict is appended to: that product's objects as depth layers in the option's
+    camera views -- amodal and visible masks, occlusion rates and order (projection.amodal_mask, visible_mask, occlusion_rate,
+    occlusion_pairs, layer_depth work on the dict's arrays)."""
     chosen = products.check_clip((
-        (geodesic_mod.Route, route, routes), (sight_mod.NextView, next_view, next_views), (sight_mod.Sight, sight, sights), (components_mod.Boxes, boxes, None),
+        (geodesic_mod.Route, route, routes), (sight_mod.NextView, next_view, next_views), (sight_mod.Sight, sight, sights),
+        (projection.ObjectLayers, layers, layer_images), (components_mod.Boxes, boxes, None),
         (watershed_mod.Segments, segments, parts), (distance_mod.Clearance, clearance, clearances),
         (components_mod.Tracker, tracker, None),
         (components_mod.Components, components, objects), (projection.FieldViews, views, images), (surface_mod.Surface, surface, meshes)))

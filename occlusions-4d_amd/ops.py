@@ -2138,6 +2138,52 @@ def boxes_choose(extent, zr, dirs, out=None):
     return box
 
 
+LAYER_ARRAYS = ('label', 'first', 'samples', 'point', 'count', 'table', 'status')
+
+
+def grid_layers(labels, k, counts, mins, spacings, rt_inv, k_inv, height, width, near, step, n_steps, max_layers, want=LAYER_ARRAYS):
+    """The labelled objects of the (nx, ny, nz) = `counts` grid as depth layers in V camera views (occ4d_layers_march_i32, the rules
+    in include/ext/occ4d_layers.h): labels (n,) int32, any values -- point p belongs to object labels[p] when 0 <= labels[p] < k --;
+    mins / spacings, rt_inv, k_inv, near, step, n_steps as ops.raycast_grid takes them.  Per pixel the objects its ray passes
+    through (the OWNER of a sample is the label of its nearest grid point) in the order of first entry, at most L = max_layers of
+    them.  want: which of the seven arrays are made (the others are null in the call).
+    -> dict of device tensors: label, first, samples, point (V, H, W, L) int32 (-1 / 0 in unused layers), count (V, H, W) int32 in
+    0 .. L + 1 (L + 1: an object was dropped), table (V, k, 7) int32 = [amodal pixels, visible pixels, least first, xmin, xmax, ymin,
+    ymax] per view and object, status (2,) int32 = [pixels with a dropped object, pixels with any object].  Two launches, whatever
+    the data.  No host read."""
+    nx, ny, nz = (int(c) for c in counts)
+    n = nx * ny * nz
+    lab = _dev(labels, torch.int32, 'labels')
+    assert lab.dim() == 1 and lab.shape[0] == n, 'labels must be (%d,), got %s' % (n, tuple(lab.shape))
+    lab = lab if lab.is_contiguous() else lab.contiguous()
+    rt, kk = _dev(rt_inv, name='rt_inv'), _dev(k_inv, name='k_inv')
+    V = rt.shape[0] if rt.dim() else -1
+    assert rt.dim() in (2, 3) and rt.numel() == V * 16 and tuple(kk.shape) == tuple(rt.shape), \
+        'rt_inv / k_inv must both be (V, 16) or (V, 4, 4), got %s and %s' % (tuple(rt.shape), tuple(kk.shape))
+    rt, kk = rt.contiguous(), kk.contiguous()
+    K, H, W, L = int(k), int(height), int(width), int(max_layers)
+    want = tuple(want)
+    assert set(want) <= set(LAYER_ARRAYS), 'want = %r: names of %r' % (want, LAYER_ARRAYS)
+    shapes = dict(label=(V, H, W, L), first=(V, H, W, L), samples=(V, H, W, L), point=(V, H, W, L), count=(V, H, W),
+                  table=(V, max(K, 0), _lib.LAYERS_CONSTANTS['COLS']), status=(2,))
+    ok = K >= 0 and H >= 0 and W >= 0 and L >= 0                 # (else the library's message; nothing is allocated)
+    out = {name: torch.empty(shapes[name] if ok else (0,), dtype=torch.int32, device=lab.device) for name in LAYER_ARRAYS if name in want}
+    _lib.check(_lib.lib().occ4d_layers_march_i32(
+        _ptr(lab), nx, ny, nz, K, float(mins[0]), float(spacings[0]), float(mins[1]), float(spacings[1]), float(mins[2]),
+        float(spacings[2]), _ptr(kk), _ptr(rt), V, H, W, float(near), float(step), int(n_steps), L,
+        *(_ptr(out.get(name)) for name in LAYER_ARRAYS), _stream()))
+    if V * H * W == 0:                                           # the call was a no-op: the table and the status of no pixel
+        if 'table' in out and out['table'].numel():
+            c = _lib.LAYERS_CONSTANTS
+            fill = [2 ** 31 - 1] * c['COLS']
+            fill[c['AMODAL']] = fill[c['VISIBLE']] = 0
+            fill[c['XMAX']] = fill[c['YMAX']] = -1
+            out['table'].copy_(torch.tensor(fill, dtype=torch.int32).to(lab.device).expand_as(out['table']))
+        if 'status' in out:
+            out['status'].zero_()
+    return out
+
+
 def link_work_len(n, cap):
     """Elements of the int32 work array of occ4d_link_overlap_i32 for n grid points and `cap` pair rows (the formula of the
     header): 4 * slots + n + 2 * tiles with slots the smallest power of two >= max(2 * min(cap, n), MIN_SLOTS), at most 2^31."""

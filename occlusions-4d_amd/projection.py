@@ -205,3 +205,142 @@ def render_field(implicit_output, counts, mins, spacings, cam_RT, cam_K, height,
     depth, cell, feat = views.render(_tensor(implicit_output, device, 'implicit_output'), counts, mins, spacings, level, channel, near,
                                      far, background)
     return dict(depth=depth, cell=cell, features=feat)
+
+
+# ---------------------------------------------------------------------------------------------------------------- object layers
+LAYERS_OF = ('components', 'segments')
+MAX_LAYERS = _lib.LAYERS_CONSTANTS['MAX']              # the header's limit on max_layers (include/ext/occ4d_layers.h)
+LAYER_PIXEL_ARRAYS = ('label', 'first', 'samples', 'point', 'count')
+# the columns of the table (not the visibility codes above)
+LAYER_COLUMNS = {c: _lib.LAYERS_CONSTANTS[c] for c in ('AMODAL', 'VISIBLE', 'NEAR', 'XMIN', 'XMAX', 'YMIN', 'YMAX')}
+
+
+class ObjectLayers(products.GridProduct):
+    """The option object of perform_inference(components=..., layers=...) / evaluate_clip(..., layers=..., layer_images=[]): the
+    objects of the product `of` ('components' or 'segments') as depth layers in the views of the cameras cam_RT (V, 3, 4), cam_K
+    (3, 3) or (V, 3, 3) (include/ext/occ4d_layers.h).  Per pixel the objects its ray passes through in the order it first enters
+    them, at most max_layers of them: layer 0 is the object seen there, the later ones are those behind it -- the amodal masks,
+    the visible masks and who hides whom.  step: the march's step in depth, None = half the smallest grid spacing (march_range);
+    arrays: which of the per-pixel arrays label, first, samples, point (V, H, W, L) and count (V, H, W) come back.  The cameras are
+    inverted here, once, on the host.  The product: result['layers'] = dict(<those arrays>, table (V, K, 7) int32 = [amodal
+    pixels, visible pixels, least first, xmin, xmax, ymin, ymax] per view and object, status (2,) int32 = [pixels that dropped an
+    object, pixels with any object], march (2,) float32 = [near, step]).  K is the length of that product's table: no host read
+    of its own.  With status[0] == 0 the table is exact, otherwise its counts are lower bounds.
+    What it is NOT: the depth of a layer, near + first * step (layer_depth), is the first sample inside a labelled cell, quantised
+    to the step -- not the refined surface crossing of FieldViews; and the masks are those of the label product, not of a density."""
+    keyword, clip_list = 'layers', ('layer_images', 'one dict of layer images')
+
+    def __init__(self, cam_RT, cam_K, height, width, of='components', max_layers=4, step=None, arrays=('label', 'first', 'count')):
+        if of not in LAYERS_OF:
+            raise ValueError("ObjectLayers: of = %r must be 'components' or 'segments'" % (of,))
+        if isinstance(max_layers, bool) or not isinstance(max_layers, (int, np.integer)) or not 1 <= max_layers <= MAX_LAYERS:
+            raise ValueError('ObjectLayers: max_layers = %r must be an integer in [1, %d]' % (max_layers, MAX_LAYERS))
+        arrays = tuple(arrays)
+        if not set(arrays) <= set(LAYER_PIXEL_ARRAYS):
+            raise ValueError('ObjectLayers: arrays = %r: names of %r' % (arrays, LAYER_PIXEL_ARRAYS))
+        self.rt_inv, self.k_inv, self.rt64 = invert_cameras(cam_RT, cam_K)
+        self.height, self.width = int(height), int(width)
+        if self.height < 0 or self.width < 0:
+            raise ValueError('ObjectLayers: height = %r, width = %r' % (height, width))
+        self.of, self.max_layers, self.step = of, int(max_layers), step
+        self.arrays = tuple(a for a in LAYER_PIXEL_ARRAYS if a in arrays)
+
+    @classmethod
+    def check(cls, option, given, point_sample_mode='grid'):
+        """As GridProduct.check; the product it builds on is the instance's `of` (`needs` is a class attribute)."""
+        super().check(option, given, point_sample_mode)
+        if option.of not in LAYERS_OF:
+            raise ValueError("ObjectLayers: of = %r must be 'components' or 'segments'" % (option.of,))
+        if option.of not in given:
+            raise ValueError("layers needs %s=<a %s>: it shows that product's objects in the views"
+                             % (option.of, 'components.Components' if option.of == 'components' else 'watershed.Segments'))
+
+    def prepare(self, grid):
+        return march_range(grid.counts, grid.mins, grid.spacings, self.rt64, step=self.step)
+
+    def run(self, grid, march, made):
+        of = made[self.of]
+        return self.layers(of['labels'], of['table'].shape[0], grid.counts, grid.mins, grid.spacings, march)
+
+    def layers(self, labels, k, counts, mins, spacings, march):
+        """-> the product's dict for labels (n,) int32 on their device; march = (near, step, n_steps)."""
+        near, step, n_steps = march
+        rt_inv, k_inv = (torch.from_numpy(m).to(labels.device) for m in (self.rt_inv, self.k_inv))
+        out = ops.grid_layers(labels, k, counts, mins, spacings, rt_inv, k_inv, self.height, self.width, near, step, n_steps,
+                              self.max_layers, want=self.arrays + ('table', 'status'))
+        out['march'] = torch.tensor([near, step], dtype=torch.float32).to(labels.device)
+        return out
+
+    def __repr__(self):
+        return 'ObjectLayers(V=%d, height=%d, width=%d, of=%r, max_layers=%d, step=%r, arrays=%r)' % (
+            len(self.rt_inv), self.height, self.width, self.of, self.max_layers, self.step, self.arrays)
+
+
+def object_layers(labels, k, counts, mins, spacings, cam_RT, cam_K, height, width, max_layers=4, near=None, far=None, step=None):
+    """The stand-alone piece of ObjectLayers: labels (n,) int32 of k objects on the (nx, ny, nz) = `counts` grid whose points
+    ops.grid_points made from `mins` / `spacings`, in the views of the cameras cam_RT / cam_K.  -> dict of device tensors: label,
+    first, samples, point (V, H, W, L) int32, count (V, H, W) int32, table (V, k, 7) int32, status (2,) int32, march (2,) float32
+    = [near, step] (the rules in include/ext/occ4d_layers.h; the march's defaults in march_range).  The cameras are inverted on the
+    host (invert_cameras); nothing else is read."""
+    option = ObjectLayers(cam_RT, cam_K, height, width, max_layers=max_layers, step=step, arrays=LAYER_PIXEL_ARRAYS)
+    lab = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32))
+    lab = lab.to(device=_device(lab), dtype=torch.int32)
+    return option.layers(lab, k, counts, mins, spacings, march_range(counts, mins, spacings, option.rt64, near, far, step))
+
+
+def _is_torch(*arrays):
+    return any(isinstance(a, torch.Tensor) for a in arrays)
+
+
+def layer_depth(first, march):
+    """The depth of every layer: near + first * step in float32 -- sample `first`'s own d_i bit for bit (the product and the sum
+    rounded one after the other) --, NaN where first is -1.  first: the int32 array of the product, march: its (2,) float32 [near,
+    step]; torch tensors give a tensor on their device, numpy gives numpy."""
+    if _is_torch(first):
+        m = march if isinstance(march, torch.Tensor) else torch.as_tensor(np.asarray(march, np.float32))
+        m = m.to(device=first.device, dtype=torch.float32)
+        travelled = first.to(torch.float32) * m[1]
+        return torch.where(first >= 0, m[0] + travelled, torch.full((), float('nan'), dtype=torch.float32, device=first.device))
+    first, m = np.asarray(first), np.asarray(march, np.float32)
+    travelled = first.astype(np.float32) * m[1]
+    return np.where(first >= 0, m[0] + travelled, np.float32('nan')).astype(np.float32)
+
+
+def amodal_mask(label, k):
+    """(V, H, W) bool: the pixels object k's full extent covers, in front or behind others -- k is one of the pixel's stored layers."""
+    return (label == int(k)).any(-1) if _is_torch(label) else (np.asarray(label) == int(k)).any(-1)
+
+
+def visible_mask(label, k):
+    """(V, H, W) bool: the pixels in which object k is in front -- layer 0."""
+    return label[..., 0] == int(k)
+
+
+def occlusion_rate(table):
+    """(V, K) float32: 1 - VISIBLE / AMODAL per view and object, NaN where the object covers no pixel of the view."""
+    if _is_torch(table):
+        amodal, visible = table[..., LAYER_COLUMNS['AMODAL']].to(torch.float32), table[..., LAYER_COLUMNS['VISIBLE']].to(torch.float32)
+        return torch.where(amodal > 0, 1.0 - visible / amodal, torch.full((), float('nan'), dtype=torch.float32, device=table.device))
+    table = np.asarray(table)
+    amodal, visible = table[..., LAYER_COLUMNS['AMODAL']].astype(np.float32), table[..., LAYER_COLUMNS['VISIBLE']].astype(np.float32)
+    with np.errstate(all='ignore'):
+        return np.where(amodal > 0, np.float32(1) - visible / amodal, np.float32('nan')).astype(np.float32)
+
+
+def occlusion_pairs(label, count=None):
+    """Who hides whom: (P, 4) int64 rows (view, front = the label of layer 0, behind = the label of a later layer, pixels), unique
+    and sorted, over the pixels of label (V, H, W, L).  count is not needed (unused layers hold -1); given, only the pixels with
+    count >= 2 are looked at.  torch.unique / np.unique on packed keys; no kernel of the package."""
+    as_torch = _is_torch(label)
+    lab = label.to(torch.int64) if as_torch else torch.from_numpy(np.ascontiguousarray(label)).to(torch.int64)
+    V, H, W, L = lab.shape
+    front, behind = lab[..., :1].expand(V, H, W, max(L - 1, 0)), lab[..., 1:]
+    view = torch.arange(V, dtype=torch.int64, device=lab.device).view(V, 1, 1, 1).expand_as(behind)
+    keep = (front >= 0) & (behind >= 0)
+    if count is not None:
+        cnt = count if isinstance(count, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(count))
+        keep = keep & (cnt.to(lab.device)[..., None] >= 2)
+    base = int(lab.max().item()) + 2 if lab.numel() else 2                                 # (labels are below 2^31 / 7)
+    keys, pixels = torch.unique((view[keep] * base + front[keep]) * base + behind[keep], return_counts=True)
+    rows = torch.stack([keys // (base * base), (keys // base) % base, keys % base, pixels], dim=1)
+    return rows if as_torch else rows.numpy()
