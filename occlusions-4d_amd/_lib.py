@@ -10,50 +10,37 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libocc4d.so')
 INCLUDE = os.path.join(os.path.dirname(_HERE), 'include')
 HEADER_PATH = os.path.join(INCLUDE, 'occ4d.h')
-# The feature headers beside occ4d.h (whose symbol set and ABI_VERSION stay as they are): attribute prefix -> file.  Same
-# conventions, same parser, same two libraries.  <PREFIX>_HEADER_PATH, <PREFIX>_SIGNATURES and <PREFIX>_CONSTANTS (the header's
-# `#define OCC4D_<PREFIX>_*` without that prefix) are made from this table below; a new header is a new row here.
-FEATURE_HEADERS = {
-    'FRONTEND': 'occ4d_frontend.h',     # the clip front end (frontend.py)
-    'EVAL': 'occ4d_eval.h',             # the evaluation statistics (evaluation.EvalStats); the constants: the layout of the two arrays
-    'OCCL': 'occ4d_occl.h',             # the id histogram behind the live occlusion fractions (occlusion.py); the bin limit, the extra bins
-    'TRACK': 'occ4d_track.h',           # the running merge of the per-instance reruns (inference.perform_inference, track_mode 'all')
-    'PROJECT': 'occ4d_project.h',       # the camera projection, the z-buffer and the visibility test (projection.py)
-    'INST': 'occ4d_inst.h',             # the instance statistics (evaluation.InstanceStats): the layout of the frame table and the two arrays
-    'REFINE': 'occ4d_refine.h',         # the coarse-to-fine decode of the query grid (inference.perform_inference(refine=...))
-    'SURFACE': 'occ4d_surface.h',       # the occupancy surface as a quad mesh (surface.py, inference.perform_inference(surface=...))
-}
-# FEATURE_HEADERS is a closed list: the suite pins it as the occ4d*.h files of include/ itself, its number of rows, and
-# ALL_SIGNATURES as the sum of its tables.  Headers that came after it live in include/ext/ and are rows here: the same
-# conventions, the same parser, the same two libraries, the same <PREFIX>_HEADER_PATH / _SIGNATURES / _CONSTANTS attributes; their
-# symbols are EXTENSION_SIGNATURES, which bind() covers beside ALL_SIGNATURES.
-EXTENSION_HEADERS = {
-    'RAYCAST': 'ext/occ4d_raycast.h',   # the decoded field ray-cast into camera views (projection.render_field, perform_inference(views=...))
-}
-# EXTENSION_SIGNATURES is pinned by the suite as well (as the ray-cast's table).  Headers of include/ext/ whose prototypes take the
-# structs of occ4d.h are rows here: parsed with those structs, <PREFIX>_HEADER_PATH / _SIGNATURES attributes as above, their symbols
-# in STRUCT_EXTENSION_SIGNATURES, which bind() covers too.
-STRUCT_EXTENSION_HEADERS = {
-    'PRELUDE': 'ext/occ4d_prelude.h',   # the decoder's query prelude (inference.QueryPrelude, LocalPclResnetFC.query_prelude)
-}
-# The three tables above are pinned by the suite row for row.  ADDON_HEADERS is OPEN BY DESIGN: every later header of include/ext/
-# is a row here (parsed with occ4d.h's structs, so a prototype may use them or not): the same <PREFIX>_HEADER_PATH / _SIGNATURES /
-# _CONSTANTS attributes, its symbols in ADDON_SIGNATURES, which bind() covers too.  A test of a header checks that its symbols are
-# IN the table and in none of the other three, never that the table equals them.
-ADDON_HEADERS = {
-    'COMPONENTS': 'ext/occ4d_components.h',     # the connected components of the solid set (components.py, perform_inference(components=...))
-    'LINK': 'ext/occ4d_link.h',                 # the components of two frames linked: overlaps, tracks (components.Tracker, perform_inference(tracker=...))
-    'DISTANCE': 'ext/occ4d_distance.h',         # the distance transform of the solid set: clearance (distance.py, perform_inference(clearance=...))
-    'GEODESIC': 'ext/occ4d_geodesic.h',         # shortest free-space paths over the clearance (geodesic.py, perform_inference(route=...))
-    'WATERSHED': 'ext/occ4d_watershed.h',       # touching objects split at their necks: watershed segments (watershed.py, perform_inference(segments=...))
-    'SIGHT': 'ext/occ4d_sight.h',               # line of sight through the solid set: seen, hidden, by what (sight.py, perform_inference(sight=...))
-    'PULL': 'ext/occ4d_pull.h',                 # straight free legs: pairwise line of sight over the clearance, routes pulled into waypoints (geodesic.straight, geodesic.pull, Route(pull=True))
-    'VIEWPLAN': 'ext/occ4d_viewplan.h',         # the next best view: which unseen points each candidate viewpoint reveals, a greedy set of them (sight.plan, perform_inference(next_view=...))
-    'BOXES': 'ext/occ4d_boxes.h',               # upright oriented boxes of the labelled objects: extents over a table of headings, the least rectangle (components.Boxes, perform_inference(boxes=...))
-    'LINZ': 'ext/occ4d_linz.h',                 # the decoder's lin_z terms inside the trunk kernels (ops.rowlin(interp2=...), ops.resblock(addrows=...)); the opt-out bit
-    'LAYERS': 'ext/occ4d_layers.h',             # the labelled objects as depth layers in camera views: amodal and visible masks, occlusion order (projection.ObjectLayers, perform_inference(layers=...))
-    'CHAIN': 'ext/occ4d_chain.h',               # consecutive residual blocks of the decoder trunk as one launch, their lin_z terms in one pass (ops.resblock_chain, ops.interp_dense); the opt-out bit
-}
+# Every header beside occ4d.h (whose symbol set and ABI_VERSION stay as they are), in the order they are read: (attribute prefix,
+# path under include/, group, parsed with occ4d.h's structs).  Same conventions, same parser, same two libraries.  The loader below
+# makes <PREFIX>_HEADER_PATH, <PREFIX>_SIGNATURES and <PREFIX>_CONSTANTS (the header's `#define OCC4D_<PREFIX>_*` without that prefix)
+# from each row and adds its symbols to its group's table; a new header is a new row.
+HEADERS = (
+    ('FRONTEND', 'occ4d_frontend.h', 'feature', False),     # the clip front end (frontend.py)
+    ('EVAL', 'occ4d_eval.h', 'feature', False),             # the evaluation statistics (evaluation.EvalStats); the constants: the layout of the two arrays
+    ('OCCL', 'occ4d_occl.h', 'feature', False),             # the id histogram behind the live occlusion fractions (occlusion.py); the bin limit, the extra bins
+    ('TRACK', 'occ4d_track.h', 'feature', False),           # the running merge of the per-instance reruns (inference.perform_inference, track_mode 'all')
+    ('PROJECT', 'occ4d_project.h', 'feature', False),       # the camera projection, the z-buffer and the visibility test (projection.py)
+    ('INST', 'occ4d_inst.h', 'feature', False),             # the instance statistics (evaluation.InstanceStats): the layout of the frame table and the two arrays
+    ('REFINE', 'occ4d_refine.h', 'feature', False),         # the coarse-to-fine decode of the query grid (inference.perform_inference(refine=...))
+    ('SURFACE', 'occ4d_surface.h', 'feature', False),       # the occupancy surface as a quad mesh (surface.py, inference.perform_inference(surface=...))
+    ('RAYCAST', 'ext/occ4d_raycast.h', 'extension', False),         # the decoded field ray-cast into camera views (projection.render_field, perform_inference(views=...))
+    ('PRELUDE', 'ext/occ4d_prelude.h', 'struct_extension', True),   # the decoder's query prelude (inference.QueryPrelude, LocalPclResnetFC.query_prelude); no constants
+    ('COMPONENTS', 'ext/occ4d_components.h', 'addon', True),    # the connected components of the solid set (components.py, perform_inference(components=...))
+    ('LINK', 'ext/occ4d_link.h', 'addon', True),                # the components of two frames linked: overlaps, tracks (components.Tracker, perform_inference(tracker=...))
+    ('DISTANCE', 'ext/occ4d_distance.h', 'addon', True),        # the distance transform of the solid set: clearance (distance.py, perform_inference(clearance=...))
+    ('GEODESIC', 'ext/occ4d_geodesic.h', 'addon', True),        # shortest free-space paths over the clearance (geodesic.py, perform_inference(route=...))
+    ('WATERSHED', 'ext/occ4d_watershed.h', 'addon', True),      # touching objects split at their necks: watershed segments (watershed.py, perform_inference(segments=...))
+    ('SIGHT', 'ext/occ4d_sight.h', 'addon', True),              # line of sight through the solid set: seen, hidden, by what (sight.py, perform_inference(sight=...))
+    ('PULL', 'ext/occ4d_pull.h', 'addon', True),                # straight free legs: pairwise line of sight over the clearance, routes pulled into waypoints (geodesic.straight, geodesic.pull, Route(pull=True))
+    ('VIEWPLAN', 'ext/occ4d_viewplan.h', 'addon', True),        # the next best view: which unseen points each candidate viewpoint reveals, a greedy set of them (sight.plan, perform_inference(next_view=...))
+    ('BOXES', 'ext/occ4d_boxes.h', 'addon', True),              # upright oriented boxes of the labelled objects: extents over a table of headings, the least rectangle (components.Boxes, perform_inference(boxes=...))
+    ('LINZ', 'ext/occ4d_linz.h', 'addon', True),                # the decoder's lin_z terms inside the trunk kernels (ops.rowlin(interp2=...), ops.resblock(addrows=...)); the opt-out bit
+    ('LAYERS', 'ext/occ4d_layers.h', 'addon', True),            # the labelled objects as depth layers in camera views: amodal and visible masks, occlusion order (projection.ObjectLayers, perform_inference(layers=...))
+    ('CHAIN', 'ext/occ4d_chain.h', 'addon', True),              # consecutive residual blocks of the decoder trunk as one launch, their lin_z terms in one pass (ops.resblock_chain, ops.interp_dense); the opt-out bit
+)
+# prefix -> file, per group
+FEATURE_HEADERS, EXTENSION_HEADERS, STRUCT_EXTENSION_HEADERS, ADDON_HEADERS = (
+    {prefix: name for prefix, name, group, _ in HEADERS if group == g} for g in ('feature', 'extension', 'struct_extension', 'addon'))
 
 
 class NativeLibraryError(RuntimeError):
@@ -64,14 +51,15 @@ def _strip_comments(text):
     return re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', text, flags=re.S))
 
 
-def parse_constants(text):
+def parse_constants(text, header='include/occ4d.h'):
     """{'ABI_VERSION': 5, 'PATH_TRUNK4': 16, ...}: every `#define OCC4D_<NAME> <integer>` of the header text (the value may
-    stand in parentheses).  A define with any other value raises; one without a value (the include guard) is none."""
+    stand in parentheses).  A define with any other value raises; one without a value (the include guard) is none.  `header`
+    names the file in the error."""
     out = {}
     for name, value in re.findall(r'^[ \t]*#[ \t]*define[ \t]+OCC4D_(\w+)[ \t]+(\S.*?)[ \t]*$', _strip_comments(text), flags=re.M):
         m = re.fullmatch(r'\(\s*(-?\d+)\s*\)|(-?\d+)', value)
         if not m:
-            raise NativeLibraryError('include/occ4d.h: cannot parse `#define OCC4D_%s %s` as an integer' % (name, value))
+            raise NativeLibraryError('%s: cannot parse `#define OCC4D_%s %s` as an integer' % (header, name, value))
         out[name] = int(m.group(1) or m.group(2))
     return out
 
@@ -82,11 +70,11 @@ _POINTEES = set(_SCALARS) | {'void', 'unsigned long long', 'uint32_t'}
 _NOT_A_NAME = {'const', 'unsigned', 'signed', 'long', 'short', 'char', 'int', 'float', 'double', 'void', 'struct'}
 
 
-def _ctype(decl, structs, what, is_return=False):
-    """ctypes type of one parameter (or of the return type) `decl`; `what` names the declaration in the error."""
+def _ctype(decl, structs, what, is_return=False, header='include/occ4d.h'):
+    """ctypes type of one parameter (or of the return type) `decl`; `what` names the declaration and `header` the file in the error."""
     m = re.fullmatch(r'(?:const\s+)?(unsigned long long|\w+)\s*(\*?)\s*(\w*)', ' '.join(decl.split()))
     if not m or m.group(3) in _NOT_A_NAME or (is_return and m.group(3)):
-        raise NativeLibraryError('include/occ4d.h: cannot parse `%s` in %s' % (decl.strip(), what))
+        raise NativeLibraryError('%s: cannot parse `%s` in %s' % (header, decl.strip(), what))
     base, star = m.group(1), m.group(2)
     if not star and base in _SCALARS:
         return _SCALARS[base]
@@ -96,37 +84,38 @@ def _ctype(decl, structs, what, is_return=False):
         return C.c_char_p
     if star and base in _POINTEES:
         return C.c_void_p           # device or host: the header cannot tell, and c_void_p takes an address, byref() and arrays
-    raise NativeLibraryError('include/occ4d.h: unknown type `%s` in %s' % (decl.strip(), what))
+    raise NativeLibraryError('%s: unknown type `%s` in %s' % (header, decl.strip(), what))
 
 
-def parse_prototypes(text, structs):
+def parse_prototypes(text, structs, header='include/occ4d.h'):
     """name -> (restype, [argtypes]) of every `<type> occ4d_<name>(<parameters>);` of the header text.  `structs`: C struct name
     -> ctypes.Structure for the struct pointers.  Strict: once comments, preprocessor lines, the extern "C" braces and the
-    typedef struct bodies are gone, EVERYTHING left must be such a prototype with known types; else NativeLibraryError."""
+    typedef struct bodies are gone, EVERYTHING left must be such a prototype with known types; else NativeLibraryError, which
+    names the file as `header`."""
     text = re.sub(r'^[ \t]*#.*$', '', _strip_comments(text), flags=re.M)
     text = re.sub(r'typedef\s+struct\b[^{};]*\{[^{}]*\}\s*\w+\s*;', '', text)
     text = re.sub(r'extern\s+"C"\s*\{|^[ \t]*\}[ \t]*$', '', text, flags=re.M)
     *decls, rest = text.split(';')
     if rest.strip():
-        raise NativeLibraryError('include/occ4d.h: declaration without `;`: `%s`' % ' '.join(rest.split())[:120])
+        raise NativeLibraryError('%s: declaration without `;`: `%s`' % (header, ' '.join(rest.split())[:120]))
     out = {}
     for decl in decls:
         what = '`%s`' % ' '.join(decl.split())[:120]
         m = re.fullmatch(r'\s*([\w\s*]+?)\s*\b(occ4d_\w+)\s*\(([^()]*)\)\s*', decl)
         if not m or m.group(2) in out:
-            raise NativeLibraryError('include/occ4d.h: cannot parse the declaration %s' % what)
+            raise NativeLibraryError('%s: cannot parse the declaration %s' % (header, what))
         params = [] if m.group(3).strip() == 'void' else m.group(3).split(',')
-        out[m.group(2)] = (_ctype(m.group(1), structs, what, is_return=True), [_ctype(p, structs, what) for p in params])
+        out[m.group(2)] = (_ctype(m.group(1), structs, what, is_return=True, header=header),
+                           [_ctype(p, structs, what, header=header) for p in params])
     return out
 
 
-def _read_header(path):
+def _read_header(path, header='include/occ4d.h'):
     try:
         with open(path) as f:
             return f.read()
     except OSError as e:
-        raise NativeLibraryError('include/%s not found at %s (%s): the ctypes binding is derived from it'
-                                 % (os.path.basename(path), path, e))
+        raise NativeLibraryError('%s not found at %s (%s): the ctypes binding is derived from it' % (header, path, e))
 
 
 _HEADER = _read_header(HEADER_PATH)
@@ -184,55 +173,26 @@ _STRUCTS = {'occ4d_linear_args': LinearArgs, 'occ4d_pt_layer_weights': PtLayerWe
             'occ4d_decoder_weights': DecoderWeights}
 SIGNATURES = parse_prototypes(_HEADER, _STRUCTS)
 
-# ... and every symbol any header declares; two headers that declare the same one are an error
-ALL_SIGNATURES = dict(SIGNATURES)
-for _prefix, _name in FEATURE_HEADERS.items():
-    _path = os.path.join(INCLUDE, _name)
-    _text = _read_header(_path)
-    _table = parse_prototypes(_text, {})
-    _twice = sorted(set(_table) & set(ALL_SIGNATURES))
-    if _twice:
-        raise NativeLibraryError('include/%s declares %s, which another header declares too' % (_name, ', '.join(_twice)))
-    ALL_SIGNATURES.update(_table)
-    globals().update({_prefix + '_HEADER_PATH': _path, _prefix + '_SIGNATURES': _table,
-                      _prefix + '_CONSTANTS': {k[len(_prefix) + 1:]: v for k, v in parse_constants(_text).items()}})
-
-# ... and the extension headers' symbols, in a table of their own
-EXTENSION_SIGNATURES = {}
-for _prefix, _name in EXTENSION_HEADERS.items():
+# ... and every symbol the other headers declare, in the table of the header's group (ALL_SIGNATURES: occ4d.h and the feature
+# headers) and in _EVERY_SIGNATURE, which bind() covers; two headers that declare the same symbol, or two rows of one prefix, are
+# an error
+ALL_SIGNATURES, EXTENSION_SIGNATURES, STRUCT_EXTENSION_SIGNATURES, ADDON_SIGNATURES = dict(SIGNATURES), {}, {}, {}
+_GROUP_SIGNATURES = {'feature': ALL_SIGNATURES, 'extension': EXTENSION_SIGNATURES, 'struct_extension': STRUCT_EXTENSION_SIGNATURES,
+                     'addon': ADDON_SIGNATURES}
+_EVERY_SIGNATURE, _prefixes = dict(SIGNATURES), set()
+for _prefix, _name, _group, _with_structs in HEADERS:
     _path = os.path.join(INCLUDE, *_name.split('/'))
-    _text = _read_header(_path)
-    _table = parse_prototypes(_text, {})
-    _twice = sorted(set(_table) & (set(ALL_SIGNATURES) | set(EXTENSION_SIGNATURES)))
-    if _twice or _prefix in FEATURE_HEADERS:
+    _text = _read_header(_path, 'include/' + _name)
+    _table = parse_prototypes(_text, _STRUCTS if _with_structs else {}, 'include/' + _name)
+    _twice = sorted(set(_table) & set(_EVERY_SIGNATURE))
+    if _twice or _prefix in _prefixes:
         raise NativeLibraryError('include/%s declares %s, which another header declares too' % (_name, ', '.join(_twice) or _prefix))
-    EXTENSION_SIGNATURES.update(_table)
-    globals().update({_prefix + '_HEADER_PATH': _path, _prefix + '_SIGNATURES': _table,
-                      _prefix + '_CONSTANTS': {k[len(_prefix) + 1:]: v for k, v in parse_constants(_text).items()}})
-
-# ... and those of the extension headers that use occ4d.h's structs
-STRUCT_EXTENSION_SIGNATURES = {}
-for _prefix, _name in STRUCT_EXTENSION_HEADERS.items():
-    _path = os.path.join(INCLUDE, *_name.split('/'))
-    _table = parse_prototypes(_read_header(_path), _STRUCTS)
-    _twice = sorted(set(_table) & (set(ALL_SIGNATURES) | set(EXTENSION_SIGNATURES) | set(STRUCT_EXTENSION_SIGNATURES)))
-    if _twice or _prefix in FEATURE_HEADERS or _prefix in EXTENSION_HEADERS:
-        raise NativeLibraryError('include/%s declares %s, which another header declares too' % (_name, ', '.join(_twice) or _prefix))
-    STRUCT_EXTENSION_SIGNATURES.update(_table)
+    _EVERY_SIGNATURE.update(_table)
+    _prefixes.add(_prefix)
+    _GROUP_SIGNATURES[_group].update(_table)
     globals().update({_prefix + '_HEADER_PATH': _path, _prefix + '_SIGNATURES': _table})
-
-# ... and the open table
-ADDON_SIGNATURES = {}
-for _prefix, _name in ADDON_HEADERS.items():
-    _path = os.path.join(INCLUDE, *_name.split('/'))
-    _text = _read_header(_path)
-    _table = parse_prototypes(_text, _STRUCTS)
-    _twice = sorted(set(_table) & (set(ALL_SIGNATURES) | set(EXTENSION_SIGNATURES) | set(STRUCT_EXTENSION_SIGNATURES) | set(ADDON_SIGNATURES)))
-    if _twice or _prefix in FEATURE_HEADERS or _prefix in EXTENSION_HEADERS or _prefix in STRUCT_EXTENSION_HEADERS:
-        raise NativeLibraryError('include/%s declares %s, which another header declares too' % (_name, ', '.join(_twice) or _prefix))
-    ADDON_SIGNATURES.update(_table)
-    globals().update({_prefix + '_HEADER_PATH': _path, _prefix + '_SIGNATURES': _table,
-                      _prefix + '_CONSTANTS': {k[len(_prefix) + 1:]: v for k, v in parse_constants(_text).items()}})
+    if _group != 'struct_extension':            # (the prelude's header defines no constants and publishes no table of them)
+        globals()[_prefix + '_CONSTANTS'] = {k[len(_prefix) + 1:]: v for k, v in parse_constants(_text, 'include/' + _name).items()}
 
 _lib = None
 _twin = False            # True only after an explicit load_cpu_twin(): host pointers, no streams (cpu_twin.py)
@@ -243,10 +203,9 @@ def is_twin():
 
 
 def bind(handle, missing=None):
-    """Sets restype / argtypes of every symbol of ALL_SIGNATURES, the two extension tables and ADDON_SIGNATURES on a loaded library and returns it.  A symbol the library does
-    not export is a stale library (NativeLibraryError) unless `missing` is given: then missing(name) stands in for it."""
-    for name, (res, args) in (list(ALL_SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items())
-                              + list(STRUCT_EXTENSION_SIGNATURES.items()) + list(ADDON_SIGNATURES.items())):
+    """Sets restype / argtypes of every symbol of every header on a loaded library and returns it.  A symbol the library does not
+    export is a stale library (NativeLibraryError) unless `missing` is given: then missing(name) stands in for it."""
+    for name, (res, args) in _EVERY_SIGNATURE.items():
         try:
             fn = getattr(handle, name)
         except AttributeError:

@@ -2,22 +2,17 @@
 g++ twin take the argument contract from one source (check_layers of csrc/layers_math.hpp over csrc/contract.hpp).  Both are loaded in
 one process -- the twin as a second plain handle, never enabled -- and handed the same rejected calls, device tensors for the one
 and same-shaped host tensors for the other: the same status and the same occ4d_last_error() bytes."""
-import ctypes
-
 import pytest
 import torch
 
 import occlusions4d_amd as pk
+from contract_texts import libraries, p, rejected_test, zeros_on  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda:0')
 EINVAL = pk._lib.EINVAL
 I32, F32 = torch.int32, torch.float32
 INF, NAN = float('inf'), float('nan')
-
-
-def p(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def march(lib, z, **k):
@@ -61,36 +56,7 @@ REJECTED = [
 ]
 
 
-@pytest.fixture(scope='module')
-def libraries():
-    hip = pk._lib.lib()
-    twin = pk._lib.bind(ctypes.CDLL(pk.cpu_twin.build()), missing=lambda name: None)      # a second handle: enable() is not called
-    assert not pk.cpu_twin.enabled() and hip.occ4d_is_cpu_twin() == 0 and twin.occ4d_is_cpu_twin() == 1
-    return hip, twin
-
-
-class zeros_on:
-    """z(*shape): a zeros tensor (int32 unless dtype says so) on the device that stays alive as long as z does -- a call's pointers
-    are real memory."""
-
-    def __init__(self, device):
-        self.device, self.alive = device, []
-
-    def __call__(self, *shape, dtype=I32):
-        self.alive.append(torch.zeros(*shape, dtype=dtype, device=self.device))
-        return self.alive[-1]
-
-
-@pytest.mark.parametrize('fragment,call', REJECTED, ids=['%02d' % i for i in range(len(REJECTED))])
-def test_both_libraries_reject_with_the_same_text(libraries, fragment, call):
-    hip, twin = libraries
-    on_device, on_host = zeros_on(DEV), zeros_on('cpu')
-    rc_hip = call(hip, on_device)
-    text_hip = bytes(hip.occ4d_last_error())
-    rc_twin = call(twin, on_host)
-    text_twin = bytes(twin.occ4d_last_error())
-    assert rc_hip == rc_twin == EINVAL
-    assert text_hip == text_twin and fragment.encode() in text_hip, (text_hip, text_twin)
+test_both_libraries_reject_with_the_same_text = rejected_test(REJECTED)
 
 
 def test_the_symbol_is_in_the_open_table_only():

@@ -9,16 +9,12 @@ import pytest
 import torch
 
 import occlusions4d_amd as pk
+from contract_texts import libraries, p, rejected_test, zeros_on  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda:0')
 EINVAL = pk._lib.EINVAL
-I32 = torch.int32
 WORK = 4 * 30 + 4 + 12                 # ops.watershed_work_len(30)
-
-
-def p(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def label(L, z, **k):
@@ -60,35 +56,7 @@ REJECTED = [
 ]
 
 
-@pytest.fixture(scope='module')
-def libraries():
-    hip = pk._lib.lib()
-    twin = pk._lib.bind(ctypes.CDLL(pk.cpu_twin.build()), missing=lambda name: None)      # a second handle: enable() is not called
-    assert not pk.cpu_twin.enabled() and hip.occ4d_is_cpu_twin() == 0 and twin.occ4d_is_cpu_twin() == 1
-    return hip, twin
-
-
-class zeros_on:
-    """z(*shape): an int32 zeros tensor on the device that stays alive as long as z does -- a call's pointers are real memory."""
-
-    def __init__(self, device):
-        self.device, self.alive = device, []
-
-    def __call__(self, *shape):
-        self.alive.append(torch.zeros(*shape, dtype=I32, device=self.device))
-        return self.alive[-1]
-
-
-@pytest.mark.parametrize('fragment,call', REJECTED, ids=['%02d' % i for i in range(len(REJECTED))])
-def test_both_libraries_reject_with_the_same_text(libraries, fragment, call):
-    hip, twin = libraries
-    on_device, on_host = zeros_on(DEV), zeros_on('cpu')
-    rc_hip = call(hip, on_device)
-    text_hip = bytes(hip.occ4d_last_error())
-    rc_twin = call(twin, on_host)
-    text_twin = bytes(twin.occ4d_last_error())
-    assert rc_hip == rc_twin == EINVAL
-    assert text_hip == text_twin and fragment.encode() in text_hip, (text_hip, text_twin)
+test_both_libraries_reject_with_the_same_text = rejected_test(REJECTED)
 
 
 def test_accepted_edges_agree(libraries):
