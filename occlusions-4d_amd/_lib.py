@@ -37,6 +37,7 @@ HEADERS = (
     ('LINZ', 'ext/occ4d_linz.h', 'addon', True),                # the decoder's lin_z terms inside the trunk kernels (ops.rowlin(interp2=...), ops.resblock(addrows=...)); the opt-out bit
     ('LAYERS', 'ext/occ4d_layers.h', 'addon', True),            # the labelled objects as depth layers in camera views: amodal and visible masks, occlusion order (projection.ObjectLayers, perform_inference(layers=...))
     ('CHAIN', 'ext/occ4d_chain.h', 'addon', True),              # consecutive residual blocks of the decoder trunk as one launch, their lin_z terms in one pass (ops.resblock_chain, ops.interp_dense); the opt-out bit
+    ('SWEEP', 'ext/occ4d_sweep.h', 'addon', True),              # the decoded field scanned by a virtual lidar: ranges, incidence, class and object per ray, rows in the loader's format (sweep.FieldSweep, perform_inference(sweep=...))
 )
 # prefix -> file, per group
 FEATURE_HEADERS, EXTENSION_HEADERS, STRUCT_EXTENSION_HEADERS, ADDON_HEADERS = (

@@ -62,6 +62,7 @@
 #include "viewplan_math.hpp"
 #include "boxes_math.hpp"
 #include "layers_math.hpp"
+#include "sweep_math.hpp"
 #include "decoder_math.hpp"
 
 namespace fe = occ4d_frontend;
@@ -73,6 +74,7 @@ namespace in = occ4d_inst;
 namespace rf = occ4d_refine;
 namespace sf = occ4d_surface;
 namespace ry = occ4d_raycast;
+namespace sw = occ4d_sweep;
 namespace cc = occ4d_components;
 namespace lk = occ4d_link;
 namespace dm = occ4d_distance;
@@ -767,6 +769,25 @@ int occ4d_raycast_grid_f32(const float* field, int64_t ld, int nx, int ny, int n
   for (int v = 0; v < V; ++v)
     for (int py = 0; py < H; ++py)
       for (int px = 0; px < W; ++px) ry::pixel_item(a, v, px, py);
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- sweep
+// include/ext/occ4d_sweep.h: the item body of csrc/sweep.hip over csrc/sweep_math.hpp, rays in order.
+int occ4d_sweep_rays_f32(const float* field, int64_t ld, int nx, int ny, int nz, float x0, float sx, float y0, float sy, float z0,
+                         float sz, float level, const float* pose, const float* dirs, int V, int B, int A, int per_view,
+                         float near_range, float step, int n_steps, const float* attrs, int64_t ld_attr, int d,
+                         const int32_t* cols_host, int C, int sem_first, int n_sem, const int32_t* labels, int K,
+                         float range_background, float feat_background, float* range, float* point, int32_t* cell, int32_t* owner,
+                         float* cosine, int32_t* sem, int32_t* inst, float* feat, void*) {
+  sw::Args a; bool empty;
+  OCC4D_TRY(sw::check_sweep(field, ld, nx, ny, nz, x0, sx, y0, sy, z0, sz, level, pose, dirs, V, B, A, per_view, near_range, step, n_steps,
+                            attrs, ld_attr, d, cols_host, C, sem_first, n_sem, labels, K, range_background, feat_background, range, point,
+                            cell, owner, cosine, sem, inst, feat, empty, a));
+  if (empty || sw::writes_nothing(a)) return OCC4D_OK;
+#pragma omp parallel for collapse(2) schedule(dynamic, 64)
+  for (int v = 0; v < V; ++v)
+    for (int r = 0; r < a.R; ++r) sw::ray_item(a, v, r);
   return OCC4D_OK;
 }
 

@@ -32,6 +32,7 @@ from . import ops
 from . import products
 from . import projection
 from . import surface as surface_mod
+from . import sweep as sweep_mod
 
 _EC = _lib.EVAL_CONSTANTS
 # target columns (R; G, B follow / mark_track / semantic tag, -1 = absent) of the two data kinds (eval/inference.py:96):
@@ -333,7 +334,7 @@ def occlusion_groups(live_occl_row, valo_ids_pad, num_valo_ids, n_ids, edges=(0.
 def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt=False, reuse_encode=True, stats=None,
                   stats_group_fn=None, stats_occlusion=None, inst_stats=None, inst_group_fn=None, refine=None, surface=None,
                   meshes=None, views=None, images=None, components=None, objects=None, tracker=None, clearance=None,
-                  clearances=None, layers=None, layer_images=None, boxes=None, next_view=None, next_views=None, sight=None, sights=None, segments=None, parts=None, route=None, routes=None):
+                  clearances=None, sweep=None, sweeps=None, layers=None, layer_images=None, boxes=None, next_view=None, next_views=None, sight=None, sights=None, segments=None, parts=None, route=None, routes=None):
     """batch: dict with 'pcl_input' (1,N,8), 'pcl_input_sem' (1,N,1-3), 'pcl_target' list of (1,T,9-11) tensors and
     batch['meta_data']['pcl_target_size'] (list of (1,) tensors), as the reference's test data loader yields them
     (data/data_greater.py:593-606, data/data_carla.py:651-661).  args: namespace with the test_args fields used
@@ -362,10 +363,13 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
     layers / layer_images: a projection.ObjectLayers, or None (needs the product its `of` names, `components` or `segments`), and
     the list every output frame's result['layers'] dict is appended to: that product's objects as depth layers in the option's
     camera views -- amodal and visible masks, occlusion rates and order (projection.amodal_mask, visible_mask, occlusion_rate,
-    occlusion_pairs, layer_depth work on the dict's arrays)."""
+    occlusion_pairs, layer_depth work on the dict's arrays).
+    sweep / sweeps: a sweep.FieldSweep, or None (with of= it needs that product, `components` or `segments`), and the list every
+    output frame's result['sweep'] dict is appended to: the decoded field scanned by a virtual lidar -- ranges, incidence cosines,
+    class and object per ray, and with rows= the returns in the lidar loader's row format (sweep.rows_of)."""
     chosen = products.check_clip((
         (geodesic_mod.Route, route, routes), (sight_mod.NextView, next_view, next_views), (sight_mod.Sight, sight, sights),
-        (projection.ObjectLayers, layers, layer_images), (components_mod.Boxes, boxes, None),
+        (sweep_mod.FieldSweep, sweep, sweeps), (projection.ObjectLayers, layers, layer_images), (components_mod.Boxes, boxes, None),
         (watershed_mod.Segments, segments, parts), (distance_mod.Clearance, clearance, clearances),
         (components_mod.Tracker, tracker, None),
         (components_mod.Components, components, objects), (projection.FieldViews, views, images), (surface_mod.Surface, surface, meshes)))

@@ -511,6 +511,71 @@ def grid_layers(labels, k, counts, mins, spacings, rt_inv, k_inv, height, width,
     return out
 
 
+SWEEP_ARRAYS = ('range', 'point', 'cell', 'owner', 'cos', 'sem', 'inst', 'features')
+
+
+def sweep_rays(values, counts, mins, spacings, level, pose, dirs, shape, near, step, n_steps, per_view=False, attrs=None, channels=(),
+               sem=None, labels=None, k=0, background=0.0, feature_background=None, want=SWEEP_ARRAYS):
+    """The field `values` on the (nx, ny, nz) = `counts` grid scanned along V bundles of R = B * A rays (occ4d_sweep_rays_f32, the
+    rules in include/ext/occ4d_sweep.h): per ray the first of the n_steps samples at ranges near + i * step whose trilinear value
+    is >= level, refined against the sample before it.  values (n,): one value per grid point, x slowest, z fastest (a strided
+    column view is read in place); mins / spacings: the three floats each that ops.grid_points took for this grid; pose (V, 12) or
+    (V, 3, 4): row-major [Rm | t], sensor to the grid's world; dirs (R, 3), or with per_view (V * R, 3) / (V, R, 3): directions in
+    the sensor frame, NOT normalised on the device (the range is in units of their length); shape = (B, A).  attrs (n, d) with
+    `channels`: the columns sampled at the hit, and with sem = (first column, number of classes): the class columns; labels (n,)
+    int32 with k: an object per grid point, any values.  want: which arrays are made (the others are null in the call).
+    -> dict of device tensors, each (V, R) unless said: range fp32 (`background` where nothing is hit), point (V, R, 3) fp32 (the
+    hit position, or `background`), cell int32 (the hit cell's low corner, -1 = none), owner int32 (the cell's corner of greatest
+    value, -1), cos fp32 (the incidence cosine, 0), sem int32 (the argmax of the class columns at owner, -1; only with sem), inst
+    int32 (labels[owner] when in [0, k), else -1; only with labels), features (V, R, C) fp32 (`feature_background`, default
+    `background`).  One launch, no host read."""
+    nx, ny, nz, n = _grid(counts)
+    v = _dev(values, name='values')
+    assert v.dim() == 1 and v.shape[0] == n, 'values must be (%d,), got %s' % (n, tuple(v.shape))
+    ps, dr = _dev(pose, name='pose'), _dev(dirs, name='dirs')
+    V = ps.shape[0] if ps.dim() else -1
+    assert ps.dim() in (2, 3) and ps.numel() == V * 12, 'pose must be (V, 12) or (V, 3, 4), got %s' % (tuple(ps.shape),)
+    B, A = (int(s) for s in shape)
+    R, per_view = B * A, bool(per_view)
+    rows = V * R if per_view else R
+    assert dr.dim() in (2, 3) and dr.shape[-1] == 3 and (B < 0 or A < 0 or dr.numel() == 3 * rows), \
+        'dirs must hold %d rows of 3 (per_view = %r, V = %d, shape = %r), got %s' % (rows, per_view, V, (B, A), tuple(dr.shape))
+    ps, dr = ps.contiguous(), dr.contiguous()
+    cols = [int(c) for c in channels]
+    n_ch = len(cols)
+    sem_first, n_sem = (0, 0) if sem is None else (int(sem[0]), int(sem[1]))
+    a, ld_attr, d = None, 0, 0
+    if n_ch or n_sem:
+        assert attrs is not None, 'channels and sem need attrs'
+        a, ld_attr = _merge_rows(attrs, 'attrs')
+        assert a.shape[0] == n, 'attrs must hold %d rows, got %d' % (n, a.shape[0])
+        d = a.shape[1]
+    lab = None
+    if labels is not None:
+        lab = _dev(labels, torch.int32, 'labels')
+        assert lab.dim() == 1 and lab.shape[0] == n, 'labels must be (%d,), got %s' % (n, tuple(lab.shape))
+        lab = _contiguous(lab)
+    want = tuple(want)
+    assert set(want) <= set(SWEEP_ARRAYS), 'want = %r: names of %r' % (want, SWEEP_ARRAYS)
+    ok = B >= 0 and A >= 0                                        # (else the library's message; nothing is allocated)
+    made = dict(range=((V, R), torch.float32), point=((V, R, 3), torch.float32), cell=((V, R), torch.int32), owner=((V, R), torch.int32),
+                cos=((V, R), torch.float32), features=((V, R, n_ch), torch.float32))
+    if n_sem:
+        made['sem'] = ((V, R), torch.int32)
+    if lab is not None:
+        made['inst'] = ((V, R), torch.int32)
+    out = {name: torch.empty(made[name][0] if ok else (0,), dtype=made[name][1], device=v.device)
+           for name in SWEEP_ARRAYS if name in want and name in made}
+    arr = (C.c_int32 * n_ch)(*cols) if n_ch else None
+    fbg = background if feature_background is None else feature_background
+    _lib.check(_lib.lib().occ4d_sweep_rays_f32(
+        _ptr(v), v.stride(0) if n > 1 else 1, nx, ny, nz, float(mins[0]), float(spacings[0]), float(mins[1]), float(spacings[1]),
+        float(mins[2]), float(spacings[2]), float(level), _ptr(ps), _ptr(dr), V, B, A, int(per_view), float(near), float(step),
+        int(n_steps), _ptr(a), max(ld_attr, d), d, arr, n_ch, sem_first, n_sem, _ptr(lab), int(k), float(background), float(fbg),
+        *(_ptr(out.get(name)) if name != 'features' or n_ch else None for name in SWEEP_ARRAYS), _stream()))
+    return out
+
+
 def link_work_len(n, cap):
     """Elements of the int32 work array of occ4d_link_overlap_i32 for n grid points and `cap` pair rows (the formula of the
     header): 4 * slots + n + 2 * tiles with slots the smallest power of two >= max(2 * min(cap, n), MIN_SLOTS), at most 2^31."""
