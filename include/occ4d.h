@@ -312,7 +312,9 @@ int occ4d_pt_pair_mlp_f32(const float* aq, int64_t ld_aq, const float* kt, int64
  *   matrix launch; the forms that hide the term inside the launch are in ext/occ4d_linz.h.)
  * occ4d_rowlin_f32:  y[:, 0..n_out) = [res +] W [relu](x) + b [+ the same interpolation term], K = 416,
  *   n_out % 32 == 0 -- the Linear layers around the cross-attention (model/modules.py:61-65: layer1 merged into
- *   the query projection, layer3 + residual).  res may alias y.
+ *   the query projection, layer3 + residual).  res may alias y; y must not overlap x: the spans from the first to the last
+ *   byte of the n rows of x and of y must be disjoint (a workgroup of the half-CU kernels reads whole rows of x while
+ *   others already store theirs of y; two column slices of one wider buffer count as overlapping), else OCC4D_EINVAL.
  *
  * Packed weights (floats; occ4d_trunk_packed_floats(n_out) = (n_out / 32 + 1) * 13312 of them, the stage after
  * the last repeats stage 0 so that the kernels prefetch branch-free):

@@ -36,13 +36,31 @@ int check_trunk_args(const Args& a, const char* who, int width) {
   return OCC4D_OK;
 }
 
+// n rows of dp floats with row stride ldp from p / of dq floats with row stride ldq from q: do the two spans, each from its
+// first to its last byte, share a byte?  (Conservative: two column slices of one wider buffer count as overlapping.)
+inline bool spans_overlap(const float* p, int64_t ldp, int dp, const float* q, int64_t ldq, int dq, int n) {
+  if (!p || !q || n <= 0) return false;
+  const uintptr_t p0 = (uintptr_t)p, p1 = (uintptr_t)(p + (int64_t)(n - 1) * ldp + dp);
+  const uintptr_t q0 = (uintptr_t)q, q1 = (uintptr_t)(q + (int64_t)(n - 1) * ldq + dq);
+  return p0 < q1 && q0 < p1;
+}
+
+// ... the same for two row sets of one width d
+inline bool rows_overlap(const float* p, int64_t ldp, const float* q, int64_t ldq, int n, int d) {
+  return spans_overlap(p, ldp, d, q, ldq, d, n);
+}
+
 // ... and what the rowlin entry points add to it: n_out a multiple of the kernel's `stage` outputs, the residual rows
-// (`skip`: the rows added after the mask, which that entry point requires) and, when `masked`, the mask rows.
+// (`skip`: the rows added after the mask, which that entry point requires) and, when `masked`, the mask rows.  y must not
+// overlap x: a row tile split over several workgroups (csrc/trunk4.hip) has each of them read whole rows of x while the
+// others store their share of y, so no rowlin runs in place (the residual rows may be y: every element is read by the
+// thread that then writes it).
 template <class Args>
 int check_rowlin_args(const Args& a, const char* who, int width, int stage, int n_out, bool masked, bool skip = false) {
   if (int rc = check_trunk_args(a, who, width)) return rc;
   OCC4D_REQUIRE(n_out >= stage && n_out % stage == 0 && a.ldy >= n_out, "%s: n_out = %d must be a multiple of %d <= ldy", who,
                 n_out, stage);
+  OCC4D_REQUIRE(!spans_overlap(a.y, a.ldy, n_out, a.x, a.ldx, width, a.n), "%s: y must not overlap x", who);
   const bool res_ok = a.ldr % 4 == 0 && ((uintptr_t)a.res % 16) == 0 && a.ldr >= n_out;
   if (skip) {
     OCC4D_REQUIRE(a.res && res_ok, "%s: skip rows must be 16-byte aligned with lds %% 4 == 0 and lds >= n_out", who);
@@ -52,14 +70,6 @@ int check_rowlin_args(const Args& a, const char* who, int width, int stage, int 
   OCC4D_REQUIRE(!masked || (a.mask && a.ldm % 4 == 0 && ((uintptr_t)a.mask % 16) == 0 && a.ldm >= n_out),
                 "%s: mask rows must be 16-byte aligned with ldm %% 4 == 0 and ldm >= n_out", who);
   return OCC4D_OK;
-}
-
-// n rows of d floats with row stride ld from p / from q: do the two spans share a byte?
-inline bool rows_overlap(const float* p, int64_t ldp, const float* q, int64_t ldq, int n, int d) {
-  if (!p || !q || n <= 0) return false;
-  const uintptr_t p0 = (uintptr_t)p, p1 = (uintptr_t)(p + (int64_t)(n - 1) * ldp + d);
-  const uintptr_t q0 = (uintptr_t)q, q1 = (uintptr_t)(q + (int64_t)(n - 1) * ldq + d);
-  return p0 < q1 && q0 < p1;
 }
 
 // ... what occ4d_rowlin_linz_f32 (include/ext/occ4d_linz.h) adds to the rowlin contract: at least one of the two terms, exactly

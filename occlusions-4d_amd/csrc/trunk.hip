@@ -582,13 +582,7 @@ TrunkArgs rowlin_args(const float* x, int64_t ldx, float* y, int64_t ldy, const 
   return a;
 }
 
-// occ4d::rows_overlap for two row sets of different widths
-bool spans_overlap(const float* p, int64_t ldp, int dp, const float* q, int64_t ldq, int dq, int n) {
-  if (!p || !q || n <= 0) return false;
-  const uintptr_t p0 = (uintptr_t)p, p1 = (uintptr_t)(p + (int64_t)(n - 1) * ldp + dp);
-  const uintptr_t q0 = (uintptr_t)q, q1 = (uintptr_t)(q + (int64_t)(n - 1) * ldq + dq);
-  return p0 < q1 && q0 < p1;
-}
+using occ4d::spans_overlap;
 
 }  // namespace
 

@@ -80,11 +80,11 @@ def host(t):
     return t.detach().cpu().numpy()
 
 
-def framed(a, off, device, guard=0):
-    """-> (buffer, view): `a` (rows, cols) as the view buffer[:rows, off:off + cols] of a (rows + guard, cols + PAD) buffer whose
+def framed(a, off, device, guard=0, pad=PAD):
+    """-> (buffer, view): `a` (rows, cols) as the view buffer[:rows, off:off + cols] of a (rows + guard, cols + pad) buffer whose
     every other float holds the sentinel."""
     rows, cols = a.shape
-    buf = sentinel(rows + guard, cols + PAD)
+    buf = sentinel(rows + guard, cols + pad)
     buf[:rows, off:off + cols] = a
     buf = to_device(buf, device)
     return buf, buf[:rows, off:off + cols]
