@@ -12,12 +12,14 @@
 
 #include "common.hpp"
 #include "decoder_math.hpp"
+#include "decoder_plan.hpp"
 #include "ext/occ4d_chain.h"
 #include "ext/occ4d_linz.h"
 
 namespace {
 
 using occ4d::cdiv;
+namespace op = occ4d_plan;
 
 #define TRY(expr)                  \
   do {                             \
@@ -35,7 +37,6 @@ inline int row_step(int n) {
   const int passes = (n + ROW_CHUNK - 1) / ROW_CHUNK;
   return passes <= 1 || !balance ? ROW_CHUNK : ((n + passes - 1) / passes + 8) / 9 * 9;
 }
-constexpr int CHAIN_BLOCKS = 3;       // most residual blocks of one occ4d_resblock_chain_f32 launch
 constexpr int64_t ALIGN = 64;         // floats: every sub-buffer starts on a 256-byte boundary
 
 inline int64_t up(int64_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
@@ -75,6 +76,14 @@ struct Events {
       (void)hipEventRecord((hipEvent_t)ev->events[2 * ev->used + 1], st);
       ev->used += 1;
     }
+  }
+  // one launch (or pair of launches) of `kind` between its two events -> the launch's status
+  template <class F>
+  int timed(int kind, F&& launch) const {
+    before(kind);
+    const int rc = launch();
+    after(kind);
+    return rc;
   }
 };
 
@@ -435,20 +444,17 @@ int layer_scene(const occ4d_pt_layer_weights& w, const LayerLayout& L, const flo
 
 int rowlin_any(bool trunk4, const float* x, int64_t ldx, float* y, int64_t ldy, const float* wpk, const float* b, int n_out,
                int relu_in, const float* res, int64_t ldr, int n, const Events& E, hipStream_t st) {
-  E.before(OCC4D_PROFILE_ROWLIN);
-  const int rc = trunk4
-      ? occ4d_rowlin4_f32(x, ldx, y, ldy, wpk, b, n_out, relu_in, res, ldr, nullptr, nullptr, 0, nullptr, nullptr, 0, n, st)
-      : occ4d_rowlin_f32(x, ldx, y, ldy, wpk, b, n_out, relu_in, res, ldr, nullptr, nullptr, 0, nullptr, nullptr, 0, n, st);
-  E.after(OCC4D_PROFILE_ROWLIN);
-  return rc;
+  return E.timed(OCC4D_PROFILE_ROWLIN, [&] {
+    return trunk4
+        ? occ4d_rowlin4_f32(x, ldx, y, ldy, wpk, b, n_out, relu_in, res, ldr, nullptr, nullptr, 0, nullptr, nullptr, 0, n, st)
+        : occ4d_rowlin_f32(x, ldx, y, ldy, wpk, b, n_out, relu_in, res, ldr, nullptr, nullptr, 0, nullptr, nullptr, 0, n, st);
+  });
 }
 
 int rowlin_x6(bool f16, const float* x, int64_t ldx, float* y, int64_t ldy, const float* wpk, const float* b, int n_out,
               int relu_in, const float* res, int64_t ldr, int n, const Events& E, hipStream_t st, float prescale = 1.f) {
-  E.before(OCC4D_PROFILE_ROWLIN);
-  const int rc = split_rowlin(f16, x, ldx, y, ldy, wpk, b, n_out, relu_in, res, ldr, n, st, prescale);
-  E.after(OCC4D_PROFILE_ROWLIN);
-  return rc;
+  return E.timed(OCC4D_PROFILE_ROWLIN,
+                 [&] { return split_rowlin(f16, x, ldx, y, ldy, wpk, b, n_out, relu_in, res, ldr, n, st, prescale); });
 }
 
 // lin_z terms a decoder hands to a cross layer's post Linear (layer3 + residual, a rowlin launch): the term of the block
@@ -464,6 +470,24 @@ struct LinzTerms {
   float* dense;
   int64_t ldd;
 };
+
+// Which kernel serves the attention of k neighbours, in priority order.  A_FIRST_GEN .. A_F16W are the fused cross-attention
+// kernels (k <= 14, events of OCC4D_PROFILE_CROSS_ATTN); the `logits` forms keep the pre-softmax logits for backward.
+enum AttnKernel { A_UNFUSED, A_SELF16, A_FIRST_GEN, A_16P, A_16P_LOGITS, A_BF16X6, A_BF16X6_LOGITS, A_F16X3, A_F16W };
+AttnKernel attn_kernel(const LayerLayout& L, int k, bool logits) {
+  if (!((L.fused16p || L.fused_first || L.bf16x6) && k <= 14)) return L.fused_self16 && k == 16 ? A_SELF16 : A_UNFUSED;
+  if (L.f16w) return A_F16W;
+  if (L.bf16x6 && L.f16) return A_F16X3;
+  if (L.bf16x6) return logits ? A_BF16X6_LOGITS : A_BF16X6;
+  if (L.fused16p) return logits ? A_16P_LOGITS : A_16P;
+  return A_FIRST_GEN;
+}
+// Which kernel serves a 416-wide Linear around the attention (the merged query projection, the post Linear): the
+// split-precision row kernel, the fp32 row kernel -- with lin_z terms taken along (post Linear only) -- or the generic one.
+enum RowKernel { R_GENERIC, R_ROWS, R_ROWS_LINZ, R_X6 };
+RowKernel row_kernel(const LayerLayout& L, bool rows, bool lz) {
+  return L.x6rows ? R_X6 : !rows ? R_GENERIC : lz ? R_ROWS_LINZ : R_ROWS;
+}
 
 // The forward of one layer / block.  dry: only the workspace is counted (no pointer is dereferenced, nothing launched).
 // lz (the caller has checked that the post Linear is the fp32 row kernel): the terms that launch takes along.
@@ -511,8 +535,9 @@ int layer_forward(const occ4d_pt_layer_weights& w, const LayerLayout& L, const f
   float* agg = out;
   int64_t ld_agg = ldo;
   if (w.post_w) { agg = ws.take((int64_t)n * D); ld_agg = D; }
-  const bool fused = (L.fused16p || L.fused_first || L.bf16x6) && k <= 14;
-  OCC4D_REQUIRE(fused || !(L.bf16x6 && L.f16), "OCC4D_PATH_SPLIT_F16: the fp16 attention kernel takes k <= 14 neighbours (k = %d); "
+  const AttnKernel attn = attn_kernel(L, k, logits_out != nullptr);
+  OCC4D_REQUIRE(attn >= A_FIRST_GEN || !(L.bf16x6 && L.f16),
+                "OCC4D_PATH_SPLIT_F16: the fp16 attention kernel takes k <= 14 neighbours (k = %d); "
                 "its prepared matrices are scaled for it", k);
   const float divisor = sqrtf((float)D);          // fp32(sqrt(d)), as torch.tensor(math.sqrt(d), float32)
   const int step = row_step(n);
@@ -537,58 +562,58 @@ int layer_forward(const occ4d_pt_layer_weights& w, const LayerLayout& L, const f
     } else {
       float* ab = ws.take((int64_t)c * 2 * D);
       if (!dry) {
-        if (L.x6rows)
-          TRY(rowlin_x6(L.f16, x + (int64_t)lo * ldx, ldx, ab, 2 * D, prep + L.wq_x6, prep + L.bq, 2 * D, 0, nullptr, 0, c, E, st,
-                         L.wq_scale));
-        else if (L.wq_rows)
-          TRY(rowlin_any(L.trunk4, x + (int64_t)lo * ldx, ldx, ab, 2 * D, prep + L.wq_packed, prep + L.bq, 2 * D, 0, nullptr, 0,
-                         c, E, st));
-        else
-          TRY(lin(x + (int64_t)lo * ldx, ldx, prep + L.wq, L.Kq, prep + L.bq, ab, 2 * D, c, L.Kq, 2 * D, 0, 0, nullptr, 0, st));
+        const float* xc = x + (int64_t)lo * ldx;
+        switch (row_kernel(L, L.wq_rows, false)) {
+          case R_X6:
+            TRY(rowlin_x6(L.f16, xc, ldx, ab, 2 * D, prep + L.wq_x6, prep + L.bq, 2 * D, 0, nullptr, 0, c, E, st, L.wq_scale));
+            break;
+          case R_ROWS:
+            TRY(rowlin_any(L.trunk4, xc, ldx, ab, 2 * D, prep + L.wq_packed, prep + L.bq, 2 * D, 0, nullptr, 0, c, E, st));
+            break;
+          default:    // R_GENERIC
+            TRY(lin(xc, ldx, prep + L.wq, L.Kq, prep + L.bq, ab, 2 * D, c, L.Kq, 2 * D, 0, 0, nullptr, 0, st));
+        }
       }
       aq = ab;
     }
     float* agg_c = agg + (int64_t)lo * ld_agg;
     const float* qp = pos + (int64_t)lo * ps;
-    if (fused) {
-      if (!dry) {
-        E.before(OCC4D_PROFILE_CROSS_ATTN);
-        int rc;
-        if (L.f16w)
-          rc = occ4d_pt_cross_attn_f16w_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vtc, D, w.pos0_w, w.pos0_b,
-                                            prep + L.stream6, agg_c, ld_agg, c, m, k, D, divisor, st);
-        else if (L.bf16x6 && L.f16)
-          rc = occ4d_pt_cross_attn_f16x3_prescaled_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vtc, D, w.pos0_w,
-                                                       w.pos0_b, prep + L.stream6, agg_c, ld_agg, c, m, k, D, divisor, st);
-        else if (L.bf16x6 && logits_out)
-          rc = occ4d_pt_cross_attn_bf16x6_logits_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vtc, D, w.pos0_w, w.pos0_b,
-                                                     prep + L.stream6, agg_c, ld_agg, logits_out + (int64_t)lo * k * D,
-                                                     a_out ? a_out + (int64_t)lo * k * 2 * D : nullptr,
-                                                     pe_out ? pe_out + (int64_t)lo * k * D : nullptr, a_out ? w.pos2_b : nullptr,
-                                                     c, m, k, D, divisor, st);
-        else if (L.bf16x6)
-          rc = occ4d_pt_cross_attn_bf16x6_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vtc, D, w.pos0_w, w.pos0_b,
-                                              prep + L.stream6, agg_c, ld_agg, c, m, k, D, divisor, st);
-        else if (L.fused16p && logits_out)          // training forward: the logits of rows lo k .. stay in HBM for backward
-          rc = occ4d_pt_cross_attn16p_logits_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vtc, D, w.pos0_w, w.pos0_b,
-                                                 prep + L.stream, agg_c, ld_agg, logits_out + (int64_t)lo * k * D,
-                                                 a_out ? a_out + (int64_t)lo * k * 2 * D : nullptr,
-                                                 pe_out ? pe_out + (int64_t)lo * k * D : nullptr, a_out ? w.pos2_b : nullptr, c, m,
-                                                 k, D, divisor, occ4d::attn16p_skew(), st);
-        else if (L.fused16p)
-          rc = occ4d_pt_cross_attn16p_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vtc, D, w.pos0_w, w.pos0_b,
-                                          prep + L.stream, agg_c, ld_agg, c, m, k, D, divisor, occ4d::attn16p_skew(), st);
-        else
-          rc = occ4d_pt_cross_attn_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vt, D, w.pos0_w, w.pos0_b, prep + L.wp,
-                                       w.attn2_w, w.attn2_b, w.pos2_w, w.pos2_b, agg_c, ld_agg, c, m, k, D, divisor, st);
-        E.after(OCC4D_PROFILE_CROSS_ATTN);
-        TRY(rc);
+    // the training forward's side outputs of rows lo .. (the `logits` kernels): the logits stay in HBM for backward
+    float* lg = logits_out ? logits_out + (int64_t)lo * k * D : nullptr;
+    float* ao = a_out ? a_out + (int64_t)lo * k * 2 * D : nullptr;
+    float* po = pe_out ? pe_out + (int64_t)lo * k * D : nullptr;
+    const float* ab2 = a_out ? w.pos2_b : nullptr;
+    const float *s6 = prep + L.stream6, *s16 = prep + L.stream, *p0w = w.pos0_w, *p0b = w.pos0_b;
+    const auto launch = [&]() -> int {
+      switch (attn) {
+        case A_F16W:
+          return occ4d_pt_cross_attn_f16w_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vtc, D, p0w, p0b, s6, agg_c, ld_agg, c,
+                                              m, k, D, divisor, st);
+        case A_F16X3:
+          return occ4d_pt_cross_attn_f16x3_prescaled_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vtc, D, p0w, p0b, s6, agg_c,
+                                                         ld_agg, c, m, k, D, divisor, st);
+        case A_BF16X6_LOGITS:
+          return occ4d_pt_cross_attn_bf16x6_logits_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vtc, D, p0w, p0b, s6, agg_c,
+                                                       ld_agg, lg, ao, po, ab2, c, m, k, D, divisor, st);
+        case A_BF16X6:
+          return occ4d_pt_cross_attn_bf16x6_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vtc, D, p0w, p0b, s6, agg_c, ld_agg,
+                                                c, m, k, D, divisor, st);
+        case A_16P_LOGITS:
+          return occ4d_pt_cross_attn16p_logits_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vtc, D, p0w, p0b, s16, agg_c,
+                                                   ld_agg, lg, ao, po, ab2, c, m, k, D, divisor, occ4d::attn16p_skew(), st);
+        case A_16P:
+          return occ4d_pt_cross_attn16p_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vtc, D, p0w, p0b, s16, agg_c, ld_agg, c,
+                                            m, k, D, divisor, occ4d::attn16p_skew(), st);
+        case A_FIRST_GEN:
+          return occ4d_pt_cross_attn_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vt, D, p0w, p0b, prep + L.wp, w.attn2_w,
+                                         w.attn2_b, w.pos2_w, w.pos2_b, agg_c, ld_agg, c, m, k, D, divisor, st);
+        default:    // A_SELF16, the encoder's widths, 16 neighbours: one kernel, no pair tensor in HBM (csrc/selfattn16.hip)
+          return occ4d_pt_self_attn16_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vt, D, p0w, p0b, prep + L.wp, w.attn2_w,
+                                          w.pos2_w, w.pos2_b, agg_c, ld_agg, c, m, k, D, divisor, st);
       }
-    } else if (L.fused_self16 && k == 16) {
-      // the encoder's widths, 16 neighbours: one kernel, no pair tensor in HBM (csrc/selfattn16.hip)
-      if (!dry)
-        TRY(occ4d_pt_self_attn16_f32(aq, 2 * D, qp, ps, pos2, p2s, idx, kt, 2 * D, vt, D, w.pos0_w, w.pos0_b, prep + L.wp,
-                                     w.attn2_w, w.pos2_w, w.pos2_b, agg_c, ld_agg, c, m, k, D, divisor, st));
+    };
+    if (attn != A_UNFUSED) {
+      if (!dry) TRY(attn == A_SELF16 ? launch() : E.timed(OCC4D_PROFILE_CROSS_ATTN, launch));
     } else {
       // unfused chain: r = relu(P1 (p_i - p_j) + c1); hid = relu(aq_i - kt_j + Wp r); logits = W2 hid + b2; pe = P2 r + c2
       const int64_t rows = (int64_t)c * k;
@@ -611,19 +636,23 @@ int layer_forward(const occ4d_pt_layer_weights& w, const LayerLayout& L, const f
     ws.release(cmark);
   }
   if (w.post_w && !dry) {
-    if (L.x6rows)
-      TRY(rowlin_x6(L.f16, agg, D, out, ldo, prep + L.w3_x6, w.post_b, w.d_out, 0, x, ldx, n, E, st));
-    else if (L.w3_rows && lz) {
-      E.before(OCC4D_PROFILE_ROWLIN);
-      const int rc = occ4d_rowlin_linz_f32(agg, D, out, ldo, prep + L.w3_packed, w.post_b, w.d_out, 0, x, ldx, lz->zconst,
-                                           lz->ztab, lz->zconst2, lz->ztab2, lz->ldz, lz->zrows, lz->zidx, lz->zw, lz->kz,
-                                           lz->dense, lz->ldd, n, st);
-      E.after(OCC4D_PROFILE_ROWLIN);
-      TRY(rc);
-    } else if (L.w3_rows)
-      TRY(rowlin_any(L.trunk4, agg, D, out, ldo, prep + L.w3_packed, w.post_b, w.d_out, 0, x, ldx, n, E, st));
-    else
-      TRY(lin(agg, D, w.post_w, D, w.post_b, out, ldo, n, D, w.d_out, 0, 0, x, ldx, st));
+    switch (row_kernel(L, L.w3_rows, lz != nullptr)) {
+      case R_X6:
+        TRY(rowlin_x6(L.f16, agg, D, out, ldo, prep + L.w3_x6, w.post_b, w.d_out, 0, x, ldx, n, E, st));
+        break;
+      case R_ROWS_LINZ:
+        TRY(E.timed(OCC4D_PROFILE_ROWLIN, [&] {
+          return occ4d_rowlin_linz_f32(agg, D, out, ldo, prep + L.w3_packed, w.post_b, w.d_out, 0, x, ldx, lz->zconst, lz->ztab,
+                                       lz->zconst2, lz->ztab2, lz->ldz, lz->zrows, lz->zidx, lz->zw, lz->kz, lz->dense, lz->ldd,
+                                       n, st);
+        }));
+        break;
+      case R_ROWS:
+        TRY(rowlin_any(L.trunk4, agg, D, out, ldo, prep + L.w3_packed, w.post_b, w.d_out, 0, x, ldx, n, E, st));
+        break;
+      case R_GENERIC:
+        TRY(lin(agg, D, w.post_w, D, w.post_b, out, ldo, n, D, w.d_out, 0, 0, x, ldx, st));
+    }
   }
   ws.release(mark);
   return OCC4D_OK;
@@ -808,140 +837,101 @@ int decoder_forward(const occ4d_decoder_weights& w, const DecoderLayout& L, cons
       if (pe) TRY(query_embed(w, q, qs, c, pe, x, ldx, st));
       else if (!x_given) TRY(occ4d::copy_rows(x, ldx, pre->x0 + (int64_t)lo * pre->ld_x0, pre->ld_x0, c, H, st));
     }
-    // Where the lin_z term of block i (x += lin_z[i](features_query), the exact-in-R form of DESIGN.md 4 (ii)) is added
-    // (DESIGN.md 6e).  On the fp32 row-resident trunk, for a cross layer j behind block b - 1 whose post Linear is the
-    // fp32 row kernel: the term of block b rides in that launch (added to its output rows), and where no cross layer
-    // sits behind block b, the same launch stores the term of block b + 1 as dense rows, which block b's launch adds
-    // from loads under its last chunk.  Every other term (the leading blocks of the published layouts; k_local != 8; the
-    // penult output; trunk4; the split-precision trunks; OCC4D_LINZ_PATH_STANDALONE) is a pass in front of its block: the
-    // stand-alone one, or the joint pass in front of a chain of blocks (below), which stores the later blocks' terms as
-    // dense rows too.  All placements add the same s last onto the same row: one result, bit for bit.
-    // OCC4D_PATH_FUSED_INTERP (the exposed gathers in the block's epilogue, measured neutral) is accepted and selects
-    // nothing: what it moved is where the default puts it now, hidden.
-    const bool linz = !(flags & OCC4D_LINZ_PATH_STANDALONE) && L.resblock && !L.trunk4 && !L.x6trunk && !penult &&
-                      w.k_local == 8 && (int64_t)m * L.nB * H < ((int64_t)1 << 30) && (int64_t)c * H < ((int64_t)1 << 30);
-    bool in_rowlin[OCC4D_MAX_BLOCKS + 2] = {}, as_dense[OCC4D_MAX_BLOCKS + 2] = {};
-    bool any_dense = false;
-    for (int j = 0; linz && j < L.nC; ++j) {
-      const int b = w.cross_after[j] + 1;
+    // What runs, and where every lin_z term is added: decided by plan_chunk (csrc/decoder_plan.hpp, which documents the
+    // routing); from here on the plan is walked.  Workspace is taken in dry and real mode alike.
+    op::Inputs in{};
+    in.nB = L.nB; in.nC = L.nC;
+    in.resblock = L.resblock; in.trunk4 = L.trunk4; in.x6trunk = L.x6trunk; in.f16block = L.f16block;
+    for (int j = 0; j < L.nC; ++j) {
       const LayerLayout& lc = L.cl[j];
-      if (b >= L.nB || !w.cross[j].post_w || !lc.w3_rows || lc.x6rows || lc.trunk4) continue;
-      in_rowlin[b] = true;
-      const bool cross_behind_b = j + 1 < L.nC && w.cross_after[j + 1] == b;
-      if (b + 1 < L.nB && !cross_behind_b) as_dense[b + 1] = any_dense = true;
+      in.cross_after[j] = w.cross_after[j];
+      in.post_rows_ok[j] = w.cross[j].post_w && lc.w3_rows && !lc.x6rows && !lc.trunk4;
+      in.tail_ok[j] = lc.wq_rows && !lc.x6rows && !lc.trunk4;
+      in.D[j] = lc.D;
     }
-    float* dense = any_dense ? ws.take((int64_t)c * H) : nullptr;
+    in.flags = flags; in.k_local = w.k_local; in.H = H; in.m = m; in.c = c;
+    in.penult_given = penult != nullptr; in.chain_tail = chain_tail(); in.one_pass = row_step(c) >= c;
+    const op::ChunkPlan P = op::plan_chunk(in);
+    float* dense = P.any_dense ? ws.take((int64_t)c * H) : nullptr;
     const int64_t ldz = (int64_t)L.nB * H;
-    // Consecutive blocks with no cross layer between them run as ONE launch (occ4d_resblock_chain_f32), at
-    // most CHAIN_BLOCKS of them, where the terms are routed at all (`linz`) and OCC4D_CHAIN_PATH_SEPARATE is not set.  The
-    // term of a chained block other than the first must arrive as dense rows: from the post Linear in front of the chain
-    // (as_dense, as before) or from one occ4d_interp_dense_f32 pass in front of it, which also adds the first block's
-    // term.  With chain_tail the cross layer's merged query projection behind the chain runs in the chain's launch too.
-    const bool chain = linz && !(flags & OCC4D_CHAIN_PATH_SEPARATE);
-    int next_cross = 0;
-    for (int i = 0; i < L.nB;) {
-      const auto cross_behind = [&](int b) { return next_cross < L.nC && w.cross_after[next_cross] == b; };
-      int e = i;
-      while (chain && e - i + 1 < CHAIN_BLOCKS && e + 1 < L.nB && !cross_behind(e)) ++e;
-      const int nb = e - i + 1;
-      const bool cross = cross_behind(e);
+    const auto zc = [&](int t) { return t < 0 ? nullptr : scene + S.zconst + (int64_t)t * H; };
+    const auto zt = [&](int t) { return t < 0 ? nullptr : scene + S.ztab + (int64_t)t * H; };
+    for (int r = 0; r < P.n_runs; ++r) {
+      const op::Run& R = P.run[r];
+      const int i = R.first;
       const int64_t cmark = ws.mark();
-      float* aq = nullptr;
-      int n_tail = 0;
-      if (chain && chain_tail() && cross) {
-        const LayerLayout& lc = L.cl[next_cross];
-        if (lc.wq_rows && !lc.x6rows && !lc.trunk4 && row_step(c) >= c) {
-          n_tail = 2 * lc.D;
-          aq = ws.take((int64_t)c * n_tail);
-        }
-      }
+      float* aq = R.n_tail ? ws.take((int64_t)c * R.n_tail) : nullptr;
       const int64_t tmark = ws.mark();           // (the dense rows of this run are released before the cross layer)
-      // which terms the pass in front of the run forms: slot 0 = the first block's (added to x), slots 1, 2 = dense rows
-      const bool first = !in_rowlin[i] && !as_dense[i];
-      const float* addp[CHAIN_BLOCKS] = {};
-      int slot_term[3] = {first ? i : -1, -1, -1};
-      float* slot_rows[3] = {first ? x : nullptr, nullptr, nullptr};
-      bool dense_free = any_dense && !as_dense[i + 1];     // (the post Linear's dense rows are consumed by the run behind it)
-      int slots = 0;
-      for (int k = i; k <= e; ++k) {
-        if (as_dense[k + 1]) { addp[k - i] = dense; continue; }
-        if (k == e) continue;
-        float* rows = dense_free ? dense : ws.take((int64_t)c * H);
-        dense_free = false;
-        ++slots;
-        slot_term[slots] = k + 1; slot_rows[slots] = rows; addp[k - i] = rows;
-      }
+      float* fresh[op::CHAIN_BLOCKS] = {};
+      for (int k = 0; k < R.n_fresh; ++k) fresh[k] = ws.take((int64_t)c * H);
+      const auto rows = [&](int where) {
+        return where == op::ROWS_X ? x : where == op::ROWS_DENSE ? dense : where >= 0 ? fresh[where] : nullptr;
+      };
       if (!dry) {
-        const auto zc = [&](int t) { return t < 0 ? nullptr : scene + S.zconst + (int64_t)t * H; };
-        const auto zt = [&](int t) { return t < 0 ? nullptr : scene + S.ztab + (int64_t)t * H; };
-        if (slots)
-          TRY(occ4d_interp_dense_f32(slot_rows[0], ldx, zc(slot_term[0]), zt(slot_term[0]), zc(slot_term[1]), zt(slot_term[1]),
-                                     slot_rows[1], H, zc(slot_term[2]), zt(slot_term[2]), slot_rows[2], H, ldz, m, idx8, w8,
+        const int* term = R.slot_term;
+        if (R.pass == op::PASS_INTERP_DENSE)
+          TRY(occ4d_interp_dense_f32(rows(R.slot_rows[0]), ldx, zc(term[0]), zt(term[0]), zc(term[1]), zt(term[1]),
+                                     rows(R.slot_rows[1]), H, zc(term[2]), zt(term[2]), rows(R.slot_rows[2]), H, ldz, m, idx8, w8,
                                      w.k_local, c, H, st));
-        else if (first)
+        else if (R.pass == op::PASS_INTERP_ADD)
           TRY(occ4d_interp_add_f32(x, ldx, zc(i), zt(i), ldz, idx8, w8, c, w.k_local, H, st));
-        if (nb > 1 || aq) {
-          const LayerLayout* lc = aq ? &L.cl[next_cross] : nullptr;
-          const float* lprep = aq ? prep + L.cross[next_cross] : nullptr;
+        const float *b0 = w.fc0_b[i], *b1 = w.fc1_b[i];
+        const auto launch = [&]() -> int {
+          // block k of the run on the fp32 row-resident kernels: its packed fc_0, fc_0's bias, its packed fc_1, fc_1's bias
           const auto blk = [&](int k, int what) -> const float* {
-            if (i + k > e) return nullptr;
+            if (k >= R.nb) return nullptr;
             return what == 0 ? prep + L.w0p[i + k] : what == 1 ? w.fc0_b[i + k] : what == 2 ? prep + L.w1p[i + k] : w.fc1_b[i + k];
           };
-          E.before(OCC4D_PROFILE_RESBLOCK);
-          const int rc = occ4d_resblock_chain_f32(
-              x, ldx, x, ldx, nb, blk(0, 0), blk(0, 1), blk(0, 2), blk(0, 3), addp[0], H, blk(1, 0), blk(1, 1), blk(1, 2),
-              blk(1, 3), addp[1], H, blk(2, 0), blk(2, 1), blk(2, 2), blk(2, 3), addp[2], H, aq ? lprep + lc->wq_packed : nullptr,
-              aq ? lprep + lc->bq : nullptr, n_tail, 0, aq, n_tail, c, st);
-          E.after(OCC4D_PROFILE_RESBLOCK);
-          TRY(rc);
-        } else if (L.f16block) {
-          // x = x + fc_1(relu(fc_0(relu(x)))) in place, one launch, h in registers
-          E.before(OCC4D_PROFILE_RESBLOCK);
-          const int rc = occ4d_resblock_f16x3_f32(x, ldx, x, ldx, prep + L.w0x[i], w.fc0_b[i], w.fc1_b[i], c, st);
-          E.after(OCC4D_PROFILE_RESBLOCK);
-          TRY(rc);
-        } else if (L.x6trunk) {
-          // h = fc_0(relu(x)); x = x + fc_1(relu(h)): two split-precision launches, h through the workspace
-          E.before(OCC4D_PROFILE_RESBLOCK);
-          int rc = split_rowlin(L.f16, x, ldx, hbuf, H, prep + L.w0x[i], w.fc0_b[i], H, 1, nullptr, 0, c, st);
-          if (!rc) rc = split_rowlin(L.f16, hbuf, H, x, ldx, prep + L.w1x[i], w.fc1_b[i], H, 1, x, ldx, c, st);
-          E.after(OCC4D_PROFILE_RESBLOCK);
-          TRY(rc);
-        } else if (L.resblock) {
-          E.before(OCC4D_PROFILE_RESBLOCK);
-          const int rc = L.trunk4
-              ? occ4d_resblock4_f32(x, ldx, x, ldx, prep + L.w0p[i], w.fc0_b[i], prep + L.w1p[i], w.fc1_b[i], nullptr,
-                                    nullptr, 0, nullptr, nullptr, 0, c, st)
-              : addp[0]             // (the next block's term, left as dense rows by the cross layer in front of this block)
-              ? occ4d_resblock_addrows_f32(x, ldx, x, ldx, prep + L.w0p[i], w.fc0_b[i], prep + L.w1p[i], w.fc1_b[i], addp[0], H,
-                                           c, st)
-              : occ4d_resblock_f32(x, ldx, x, ldx, prep + L.w0p[i], w.fc0_b[i], prep + L.w1p[i], w.fc1_b[i], nullptr,
-                                   nullptr, 0, nullptr, nullptr, 0, c, st);
-          E.after(OCC4D_PROFILE_RESBLOCK);
-          TRY(rc);
-        } else {
-          TRY(lin(x, ldx, w.fc0_w[i], H, w.fc0_b[i], hbuf, H, c, H, H, act, 0, nullptr, 0, st));
-          TRY(lin(hbuf, H, w.fc1_w[i], H, w.fc1_b[i], x, ldx, c, H, H, act, 0, x, ldx, st));
-        }
+          int rc;
+          switch (R.kernel) {
+            case op::K_CHAIN: {
+              const LayerLayout* lc = aq ? &L.cl[R.cross] : nullptr;
+              const float* lprep = aq ? prep + L.cross[R.cross] : nullptr;
+              return occ4d_resblock_chain_f32(
+                  x, ldx, x, ldx, R.nb, blk(0, 0), blk(0, 1), blk(0, 2), blk(0, 3), rows(R.addrows[0]), H, blk(1, 0), blk(1, 1),
+                  blk(1, 2), blk(1, 3), rows(R.addrows[1]), H, blk(2, 0), blk(2, 1), blk(2, 2), blk(2, 3), rows(R.addrows[2]), H,
+                  aq ? lprep + lc->wq_packed : nullptr, aq ? lprep + lc->bq : nullptr, R.n_tail, 0, aq, R.n_tail, c, st);
+            }
+            case op::K_F16_BLOCK:         // x = x + fc_1(relu(fc_0(relu(x)))) in place, one launch, h in registers
+              return occ4d_resblock_f16x3_f32(x, ldx, x, ldx, prep + L.w0x[i], b0, b1, c, st);
+            case op::K_SPLIT_PAIR:        // h = fc_0(relu(x)); x = x + fc_1(relu(h)): two split-precision launches
+              rc = split_rowlin(L.f16, x, ldx, hbuf, H, prep + L.w0x[i], b0, H, 1, nullptr, 0, c, st);
+              return rc ? rc : split_rowlin(L.f16, hbuf, H, x, ldx, prep + L.w1x[i], b1, H, 1, x, ldx, c, st);
+            case op::K_RESBLOCK4:
+              return occ4d_resblock4_f32(x, ldx, x, ldx, blk(0, 0), b0, blk(0, 2), b1, nullptr, nullptr, 0, nullptr, nullptr, 0, c,
+                                         st);
+            case op::K_RESBLOCK_ADDROWS:  // (the next block's term, left as dense rows by the cross layer in front of this block)
+              return occ4d_resblock_addrows_f32(x, ldx, x, ldx, blk(0, 0), b0, blk(0, 2), b1, rows(R.addrows[0]), H, c, st);
+            case op::K_RESBLOCK:
+              return occ4d_resblock_f32(x, ldx, x, ldx, blk(0, 0), b0, blk(0, 2), b1, nullptr, nullptr, 0, nullptr, nullptr, 0, c,
+                                        st);
+            case op::K_GENERIC_PAIR:
+              rc = lin(x, ldx, w.fc0_w[i], H, b0, hbuf, H, c, H, H, act, 0, nullptr, 0, st);
+              return rc ? rc : lin(hbuf, H, w.fc1_w[i], H, b1, x, ldx, c, H, H, act, 0, x, ldx, st);
+          }
+          return OCC4D_OK;
+        };
+        // (the generic pair is two plain Linears, no residual-block kernel: no launch event)
+        TRY(R.kernel == op::K_GENERIC_PAIR ? launch() : E.timed(OCC4D_PROFILE_RESBLOCK, launch));
       }
       ws.release(tmark);
-      if (cross) {
-        const int j = next_cross++;
+      if (R.cross >= 0) {
+        const int j = R.cross;
+        const bool with_lz = !dry && R.post_add >= 0;
         LinzTerms lz{};
-        if (!dry && in_rowlin[e + 1]) {
-          lz.zconst = scene + S.zconst + (int64_t)(e + 1) * H; lz.ztab = scene + S.ztab + (int64_t)(e + 1) * H;
-          if (as_dense[e + 2]) {
-            lz.zconst2 = scene + S.zconst + (int64_t)(e + 2) * H; lz.ztab2 = scene + S.ztab + (int64_t)(e + 2) * H;
+        if (with_lz) {
+          lz.zconst = zc(R.post_add); lz.ztab = zt(R.post_add);
+          if (R.post_dense >= 0) {
+            lz.zconst2 = zc(R.post_dense); lz.ztab2 = zt(R.post_dense);
             lz.dense = dense; lz.ldd = H;
           }
           lz.ldz = ldz; lz.zrows = m; lz.zidx = idx8; lz.zw = w8; lz.kz = w.k_local;
         }
         TRY(layer_forward(w.cross[j], L.cl[j], prep ? prep + L.cross[j] : nullptr, x, ldx, q, qs, c, nullptr, 0, xyz, 3, m,
                           w.k_cross, idx_att, scene ? scene + S.layer[j] : nullptr, x, ldx, ws, E, st, dry, nullptr, nullptr,
-                          nullptr, !dry && in_rowlin[e + 1] ? &lz : nullptr, n_tail != 0, aq));
+                          nullptr, with_lz ? &lz : nullptr, R.n_tail != 0, aq));
       }
       ws.release(cmark);
-      i = e + 1;
     }
     if (!dry)
       TRY(lin(x, ldx, w.lin_out_w, H, w.lin_out_b, out + (int64_t)lo * ld_out, ld_out, c, H, w.d_out, act, 0, nullptr, 0, st));
