@@ -25,8 +25,9 @@ from . import geodesic  # noqa: F401   (shortest free-space paths over the clear
 from . import watershed  # noqa: F401   (touching objects split at their necks: Segments, split)
 from . import sight  # noqa: F401   (line of sight through the decoded occupancy: Sight, look, grid_origin, codes, by_label; the next best view: NextView, plan, cells_to_world)
 from . import sweep  # noqa: F401   (the decoded field scanned by a virtual lidar: FieldSweep, cast, lidar_directions, directions_to, poses, march_range, rows_of, residual)
+from . import evidence  # noqa: F401   (measured returns carved into the query grid: Evidence, carve, classify, observe, by_label, rates and the six codes)
 from . import cpu_twin  # noqa: F401   (explicit opt-in only: pk.cpu_twin.enable(); never a fallback)
 
 __all__ = ['configs', 'kernels', 'ops', 'point_transformer_layer', 'modules', 'model', 'geometry', 'implicit',
            'inference', 'distributed', 'autograd', 'training', 'evaluation', 'occlusion', 'frontend', 'projection', 'surface',
-           'components', 'distance', 'geodesic', 'watershed', 'sight', 'sweep']
+           'components', 'distance', 'geodesic', 'watershed', 'sight', 'sweep', 'evidence']

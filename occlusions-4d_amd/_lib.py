@@ -38,6 +38,7 @@ HEADERS = (
     ('LAYERS', 'ext/occ4d_layers.h', 'addon', True),            # the labelled objects as depth layers in camera views: amodal and visible masks, occlusion order (projection.ObjectLayers, perform_inference(layers=...))
     ('CHAIN', 'ext/occ4d_chain.h', 'addon', True),              # consecutive residual blocks of the decoder trunk as one launch, their lin_z terms in one pass (ops.resblock_chain, ops.interp_dense); the opt-out bit
     ('SWEEP', 'ext/occ4d_sweep.h', 'addon', True),              # the decoded field scanned by a virtual lidar: ranges, incidence, class and object per ray, rows in the loader's format (sweep.FieldSweep, perform_inference(sweep=...))
+    ('EVIDENCE', 'ext/occ4d_evidence.h', 'addon', True),        # measured returns carved into the grid: hits, passed cells, the six codes of prediction against evidence (evidence.Evidence, perform_inference(evidence=...))
 )
 # prefix -> file, per group
 FEATURE_HEADERS, EXTENSION_HEADERS, STRUCT_EXTENSION_HEADERS, ADDON_HEADERS = (

@@ -42,6 +42,7 @@
 #include "ext/occ4d_viewplan.h"
 #include "ext/occ4d_boxes.h"
 #include "ext/occ4d_layers.h"
+#include "ext/occ4d_evidence.h"
 // csrc/, the HIP library's own source: each feature's per-element arithmetic, item bodies and argument contracts (contract.hpp)
 #include "frontend_math.hpp"
 #include "eval_math.hpp"
@@ -63,6 +64,7 @@
 #include "boxes_math.hpp"
 #include "layers_math.hpp"
 #include "sweep_math.hpp"
+#include "evidence_math.hpp"
 #include "decoder_math.hpp"
 
 namespace fe = occ4d_frontend;
@@ -75,6 +77,7 @@ namespace rf = occ4d_refine;
 namespace sf = occ4d_surface;
 namespace ry = occ4d_raycast;
 namespace sw = occ4d_sweep;
+namespace ed = occ4d_evidence;
 namespace cc = occ4d_components;
 namespace lk = occ4d_link;
 namespace dm = occ4d_distance;
@@ -788,6 +791,44 @@ int occ4d_sweep_rays_f32(const float* field, int64_t ld, int nx, int ny, int nz,
 #pragma omp parallel for collapse(2) schedule(dynamic, 64)
   for (int v = 0; v < V; ++v)
     for (int r = 0; r < a.R; ++r) sw::ray_item(a, v, r);
+  return OCC4D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- evidence
+// include/ext/occ4d_evidence.h: the body of a return and the code of a cell of csrc/evidence_math.hpp, RETURNS AND CELLS IN ORDER,
+// the atomics spelled as plain memory operations (one thread).
+namespace {
+struct PlainMarks {
+  uint32_t* words;
+  int32_t *hits, *passes;
+  void hit(int32_t flat) const { hits[flat] += 1; }
+  void pass(int32_t flat) const {
+    words[flat >> 5] |= 1u << (flat & 31);
+    if (passes) passes[flat] += 1;
+  }
+  void arrive(int32_t flat) const { pass(flat); }
+};
+}  // namespace
+int occ4d_evidence_carve_f32(const float* returns, int64_t ld_returns, int64_t R, const int32_t* sensor, const int32_t* origins, int V,
+                             int nx, int ny, int nz, float x0, float sx, float y0, float sy, float z0, float sz, uint32_t* passed,
+                             int32_t* hits, int32_t* passes, int32_t* status, void*) {
+  ed::CarveArgs a;
+  OCC4D_TRY(ed::check_carve(returns, ld_returns, R, sensor, origins, V, nx, ny, nz, x0, sx, y0, sy, z0, sz, passed, hits, passes, status, a));
+  for (int64_t p = 0; p < a.points; ++p) hits[p] = 0;
+  for (int64_t p = 0; passes && p < a.points; ++p) passes[p] = 0;
+  for (int64_t w = 0; w < a.words; ++w) passed[w] = 0u;
+  for (int k = 0; k < 4; ++k) status[k] = 0;
+  const PlainMarks marks{passed, hits, passes};
+  for (int64_t r = 0; r < R; ++r) status[ed::return_item(a, r, marks)] += 1;
+  return OCC4D_OK;
+}
+int occ4d_evidence_classify_f32(const float* field, int64_t ld, float level, const float* mask, int64_t ld_mask, float mask_level,
+                                int64_t n, const uint32_t* passed, const int32_t* passes, int min_pass, const int32_t* hits,
+                                int32_t* code, int64_t* totals, void*) {
+  ed::ClassifyArgs a;
+  OCC4D_TRY(ed::check_classify(field, ld, level, mask, ld_mask, mask_level, n, passed, passes, min_pass, hits, code, totals, a));
+  for (int k = 0; k < 6; ++k) totals[k] = 0;
+  for (int64_t p = 0; p < n; ++p) totals[code[p] = ed::code_of(a, p)] += 1;
   return OCC4D_OK;
 }
 

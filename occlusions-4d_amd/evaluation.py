@@ -33,6 +33,7 @@ from . import products
 from . import projection
 from . import surface as surface_mod
 from . import sweep as sweep_mod
+from . import evidence as evidence_mod
 
 _EC = _lib.EVAL_CONSTANTS
 # target columns (R; G, B follow / mark_track / semantic tag, -1 = absent) of the two data kinds (eval/inference.py:96):
@@ -334,7 +335,7 @@ def occlusion_groups(live_occl_row, valo_ids_pad, num_valo_ids, n_ids, edges=(0.
 def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt=False, reuse_encode=True, stats=None,
                   stats_group_fn=None, stats_occlusion=None, inst_stats=None, inst_group_fn=None, refine=None, surface=None,
                   meshes=None, views=None, images=None, components=None, objects=None, tracker=None, clearance=None,
-                  clearances=None, sweep=None, sweeps=None, layers=None, layer_images=None, boxes=None, next_view=None, next_views=None, sight=None, sights=None, segments=None, parts=None, route=None, routes=None):
+                  clearances=None, evidence=None, evidences=None, sweep=None, sweeps=None, layers=None, layer_images=None, boxes=None, next_view=None, next_views=None, sight=None, sights=None, segments=None, parts=None, route=None, routes=None):
     """batch: dict with 'pcl_input' (1,N,8), 'pcl_input_sem' (1,N,1-3), 'pcl_target' list of (1,T,9-11) tensors and
     batch['meta_data']['pcl_target_size'] (list of (1,) tensors), as the reference's test data loader yields them
     (data/data_greater.py:593-606, data/data_carla.py:651-661).  args: namespace with the test_args fields used
@@ -366,10 +367,14 @@ def evaluate_clip(batch, networks, device, args, data_kind, logger=None, save_gt
     occlusion_pairs, layer_depth work on the dict's arrays).
     sweep / sweeps: a sweep.FieldSweep, or None (with of= it needs that product, `components` or `segments`), and the list every
     output frame's result['sweep'] dict is appended to: the decoded field scanned by a virtual lidar -- ranges, incidence cosines,
-    class and object per ray, and with rows= the returns in the lidar loader's row format (sweep.rows_of)."""
+    class and object per ray, and with rows= the returns in the lidar loader's row format (sweep.rows_of).
+    evidence / evidences: an evidence.Evidence, or None, and the list every output frame's result['evidence'] dict is appended to:
+    the option's measured returns carved into the grid and crossed with the predicted solid set -- code, hits[, passes], totals,
+    status (evidence.rates, evidence.by_label).  ONE option for every output frame: the returns are timeless, the caller selects
+    the rows that bear on the clip."""
     chosen = products.check_clip((
         (geodesic_mod.Route, route, routes), (sight_mod.NextView, next_view, next_views), (sight_mod.Sight, sight, sights),
-        (sweep_mod.FieldSweep, sweep, sweeps), (projection.ObjectLayers, layers, layer_images), (components_mod.Boxes, boxes, None),
+        (evidence_mod.Evidence, evidence, evidences), (sweep_mod.FieldSweep, sweep, sweeps), (projection.ObjectLayers, layers, layer_images), (components_mod.Boxes, boxes, None),
         (watershed_mod.Segments, segments, parts), (distance_mod.Clearance, clearance, clearances),
         (components_mod.Tracker, tracker, None),
         (components_mod.Components, components, objects), (projection.FieldViews, views, images), (surface_mod.Surface, surface, meshes)))

@@ -576,6 +576,64 @@ def sweep_rays(values, counts, mins, spacings, level, pose, dirs, shape, near, s
     return out
 
 
+def grid_carve(returns, origins, counts, mins, spacings, sensor=None, counts_too=False):
+    """Measured returns carved into the (nx, ny, nz) = `counts` grid (occ4d_evidence_carve_f32, the rules in include/ext/
+    occ4d_evidence.h): returns (R, >= 3) float32 world points on the device, a row-strided view is read in place; origins (V, 3) int32
+    lattice cells ON THE DEVICE, 1 <= V <= 4096, any values (the kernel checks what it reads); mins / spacings: the three floats each
+    that ops.grid_points took for this grid; sensor (R,) int32 on the device or None = every return belongs to sensor 0;
+    counts_too: also how many walks passed each cell.  -> (passed (ceil(n / 32),)
+    int32, bit p % 32 of word p // 32 = a ray passed through cell p; hits (n,) int32; passes (n,) int32 or None; status (4,) int32 =
+    [carved, dropped for the sensor, dropped as not finite / too far, dropped outside the grid]), on the device.  Two launches, no
+    host read."""
+    nx, ny, nz, n = _grid(counts)
+    ret = _dev(returns, name='returns')
+    assert ret.dim() == 2 and ret.shape[1] >= 3, 'returns must be (R, >= 3), got %s' % (tuple(ret.shape),)
+    if ret.stride(1) != 1 or (ret.shape[0] > 1 and ret.stride(0) < 3):
+        ret = ret.contiguous()
+    R = int(ret.shape[0])
+    ld = ret.stride(0) if R > 1 else max(int(ret.shape[1]), 3)
+    org = _dev(origins, torch.int32, 'origins')
+    assert org.dim() == 2 and org.shape[1] == 3, 'origins must be (V, 3), got %s' % (tuple(org.shape),)
+    org = _contiguous(org)
+    sen = None
+    if sensor is not None:
+        sen = _dev(sensor, torch.int32, 'sensor')
+        assert tuple(sen.shape) == (R,), 'sensor must be (%d,), got %s' % (R, tuple(sen.shape))
+        sen = _contiguous(sen)
+    size = max(n, 0)
+    passed = torch.empty(((size + 31) // 32,), dtype=torch.int32, device=ret.device)
+    hits = torch.empty((size,), dtype=torch.int32, device=ret.device)
+    passes = torch.empty((size,), dtype=torch.int32, device=ret.device) if counts_too else None
+    status = torch.empty((4,), dtype=torch.int32, device=ret.device)
+    _lib.check(_lib.lib().occ4d_evidence_carve_f32(
+        _ptr(ret), ld, R, _ptr(sen), _ptr(org), int(org.shape[0]), nx, ny, nz, float(mins[0]), float(spacings[0]), float(mins[1]),
+        float(spacings[1]), float(mins[2]), float(spacings[2]), _ptr(passed), _ptr(hits), _ptr(passes), _ptr(status), _stream()))
+    return passed, hits, passes, status
+
+
+def grid_evidence(values, level, hits, passed=None, passes=None, min_pass=1, mask=None, mask_level=0.0):
+    """The six codes of prediction against evidence (occ4d_evidence_classify_f32, STATE, SOLID and CODE of include/ext/
+    occ4d_evidence.h): values (n,), a strided column view is read in place, solid where values >= level (with mask (n,) also mask
+    >= mask_level); hits (n,) int32 and passed (ceil(n / 32),) int32 from ops.grid_carve -- or passes (n,) int32, then a cell is FREE
+    from min_pass walks on.  -> (code (n,) int32, totals (6,) int64: the histogram of code), on the device.  Two launches, no host
+    read."""
+    n = int(values.shape[0])
+    v, ld = _inst_column(values, n, 'values')
+    m, ld_mask = (None, 0) if mask is None else _inst_column(mask, n, 'mask')
+    h = _dev(hits, torch.int32, 'hits')
+    assert tuple(h.shape) == (n,) and h.is_contiguous(), 'hits must be a contiguous (%d,) tensor, got %s' % (n, tuple(h.shape))
+    words = None if passed is None else _bit_words(passed, n, 'passed')
+    ps = None
+    if passes is not None:
+        ps = _dev(passes, torch.int32, 'passes')
+        assert tuple(ps.shape) == (n,) and ps.is_contiguous(), 'passes must be a contiguous (%d,) tensor, got %s' % (n, tuple(ps.shape))
+    code = torch.empty((n,), dtype=torch.int32, device=v.device)
+    totals = torch.empty((6,), dtype=torch.int64, device=v.device)
+    _lib.check(_lib.lib().occ4d_evidence_classify_f32(_ptr(v), ld, float(level), _ptr(m), ld_mask, float(mask_level), n, _ptr(words),
+                                                      _ptr(ps), int(min_pass), _ptr(h), _ptr(code), _ptr(totals), _stream()))
+    return code, totals
+
+
 def link_work_len(n, cap):
     """Elements of the int32 work array of occ4d_link_overlap_i32 for n grid points and `cap` pair rows (the formula of the
     header): 4 * slots + n + 2 * tiles with slots the smallest power of two >= max(2 * min(cap, n), MIN_SLOTS), at most 2^31."""

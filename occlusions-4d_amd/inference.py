@@ -28,6 +28,7 @@ from . import geodesic as geodesic_mod
 from . import watershed as watershed_mod
 from . import sight as sight_mod
 from . import sweep as sweep_mod
+from . import evidence as evidence_mod
 
 
 def get_track_idx(color_mode):
@@ -189,7 +190,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
                       density_threshold=0.5, data_kind='', cube_mode=4, compress_air=False,
                       encoded=None, return_encoded=False, neighbour_lists=None, stats=None, stats_target=None,
                       stats_group=None, track_merge='device', inst_stats=None, inst_group=None, refine=None, surface=None,
-                      views=None, components=None, route=None, sweep=None, layers=None, boxes=None, next_view=None, sight=None, segments=None, tracker=None, clearance=None):
+                      views=None, components=None, route=None, evidence=None, sweep=None, layers=None, boxes=None, next_view=None, sight=None, segments=None, tracker=None, clearance=None):
     """One encode of the input point-cloud video + decode of all query points of one output frame.  Returns
     dict(output_solid, output_air, pcl_abstract, features_global, implicit_output, points_query) of float32 numpy arrays, and
     gt_solid / gt_air when `pcl_target_frame` is given.  The keywords from `encoded` on are extensions whose defaults give the
@@ -224,7 +225,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     dependence of a row on its place in the mini-batch decode_refined reproduces; under another kernels.Selection only within
     the mini-batch-split bound, 1e-5.)
 
-    Grid products.  `surface`, `views`, `components`, `tracker`, `clearance`, `segments`, `boxes`, `layers`, `sweep`, `sight`, `next_view`, `route`: option objects (products.GridProduct), or
+    Grid products.  `surface`, `views`, `components`, `tracker`, `clearance`, `segments`, `boxes`, `layers`, `sweep`, `evidence`, `sight`, `next_view`, `route`: option objects (products.GridProduct), or
     None = nothing is called and no key is added.  point_sample_mode 'grid' only (ValueError).  Each turns the same squashed (N, G)
     array -- in track_mode 'all' merged, under `refine` expanded -- into more arrays on the device, which come back with the others,
     under the one host wait; the option class describes its arguments and its arrays.  They are checked, and run, in this order:
@@ -259,6 +260,12 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     its class (predict_segmentation) and its object (the option's `of` names the label product, `components` or `segments`, which
     has to be given: ValueError), and with rows= the returns as rows in the lidar loader's format (include/ext/occ4d_sweep.h;
     sweep.rows_of trims them).  Uniform samples with the refinement of `views`, not an exact intersection.  Runs after `layers`.
+    `evidence` (in the signature in front of `sweep`): an evidence.Evidence -> result['evidence'] = dict(code, hits[, passes], totals,
+    status): the option's measured returns carved into the grid -- the cells between a sensor and its return are measured free, the
+    return's cell is hit, the rest is unknown -- crossed with density >= level into six codes per query: a predicted solid in
+    measured free space is CONTRADICTED, a return in predicted air MISSED, a predicted solid no ray reached COMPLETED
+    (include/ext/occ4d_evidence.h; evidence.rates, evidence.by_label).  The returns are taken as given and are timeless.  Needs no
+    other product.  Runs after `sweep`.
     `next_view` (in the signature in front of `sight`: the suite pins the last four names): a sight.NextView; needs `sight`
     (ValueError) -> result['next_view'] = dict(gain, picks, pick_gain, status): of the queries that call's sensors do not see, how
     many each candidate viewpoint would see, and a greedy choice of up to k of them that together see the most.
@@ -271,7 +278,7 @@ def perform_inference(pcl_input, pcl_input_sem, pcl_target_frame, networks, devi
     assert track_merge in ('device', 'host'), track_merge
     slots = ((surface_nets.Surface, surface), (projection.FieldViews, views), (components_mod.Components, components),
              (components_mod.Tracker, tracker), (distance_mod.Clearance, clearance), (watershed_mod.Segments, segments),
-             (components_mod.Boxes, boxes), (projection.ObjectLayers, layers), (sweep_mod.FieldSweep, sweep), (sight_mod.Sight, sight), (sight_mod.NextView, next_view), (geodesic_mod.Route, route))
+             (components_mod.Boxes, boxes), (projection.ObjectLayers, layers), (sweep_mod.FieldSweep, sweep), (evidence_mod.Evidence, evidence), (sight_mod.Sight, sight), (sight_mod.NextView, next_view), (geodesic_mod.Route, route))
     grid = None                               # the very floats the query grid is generated from
     if point_sample_mode == 'grid' and (refine is not None or any(option is not None for _, option in slots)):
         grid = products.Grid(geometry.grid_frame(num_sample, min_z, cube_bounds, data_kind, cube_mode), density_threshold,

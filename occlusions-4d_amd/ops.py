@@ -18,8 +18,8 @@ from ._plumbing import (_RAW_STREAM, _TensorPointer, _dev, _inst_column, _int32_
 # the wrappers of the grid products live in grid_ops.py; callers reach them as ops.<name>, looked up at call time
 from .grid_ops import (LAYER_ARRAYS, SWEEP_ARRAYS, _min_iou_fraction, boxes_choose, components_match, components_overlap,  # noqa: F401
                        components_work_len, distance_tile_width, geodesic_default_rounds, geodesic_pull, geodesic_trace,
-                       geodesic_work_len, grid_blocked_bits, grid_box_extents, grid_components, grid_distance, grid_geodesic,
-                       grid_layers, grid_segments, grid_sight, grid_solid_bits, grid_visible, grid_watershed, link_work_len,
+                       geodesic_work_len, grid_blocked_bits, grid_box_extents, grid_carve, grid_components, grid_distance, grid_evidence,
+                       grid_geodesic, grid_layers, grid_segments, grid_sight, grid_solid_bits, grid_visible, grid_watershed, link_work_len,
                        raycast_grid, sweep_rays, viewplan_greedy, viewplan_work_len, watershed_work_len)
 
 

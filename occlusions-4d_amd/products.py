@@ -1,4 +1,4 @@
-"""The grid products of perform_inference: what its options surface, views, components, tracker, clearance, segments, boxes (components.Boxes), layers (projection.ObjectLayers), sweep (sweep.FieldSweep), sight,
+"""The grid products of perform_inference: what its options surface, views, components, tracker, clearance, segments, boxes (components.Boxes), layers (projection.ObjectLayers), sweep (sweep.FieldSweep), evidence (evidence.Evidence), sight,
 next_view and route have in common.
 Each of them turns the squashed (N, G) output of a point_sample_mode='grid' call into more device tensors, which come home under the
 call's one host wait.  An option class derives from GridProduct and says which keyword it answers to, what it needs and how it
